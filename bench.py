@@ -10,19 +10,24 @@ N > 1 (one rank per GPU under torch.distributed.run; `python bench.py --gpus N` 
 sequence is sharded into contiguous K-frame chunks (weak scaling); every rank runs the state-independent heavy phase
 of its chunk at once, the recurrent Kalman state (76.8 KB) goes rank r -> r+1 by RCCL send/recv before the scan.
 
-Timing: W untimed warm-up steps, then the K-step pass is repeated until --min-seconds are timed; every repetition is
-exactly K steps bracketed by barrier + torch.cuda.synchronize() on both sides, MAX over ranks; the line reports the
-MEDIAN repetition.
+Timing: W untimed warm-up steps, then ONE timed pass of exactly K steps (--steps), bracketed by barrier +
+torch.cuda.synchronize() on both sides, MAX over ranks.  --min-seconds S repeats the K-step pass until S seconds are
+timed and reports the MEDIAN repetition.
 
-OUTPUT.  The LAST stdout line is ONE compact JSON object (< 4 KB, no prose; `compact_line`): the contract fields,
-`roofline` of the step's dominant kernel (executed MFMA FLOPs / HIP-event time of its launches; `traffic` = PMC bytes
-per launch quoted from profiles/), `cpu_baseline` (the torch-CPU restatement on config 1's 16 frames), and one number
-each for the side measurements (value_streamed, parity, Kalman rooflines, config 5, config 2, multi-rank extras).
-Everything else -- per-kernel tables, telemetry, notes -- goes to the sidecar file gpurun_out/bench_detail.json
-(`--detail PATH`; bench_extra.py holds the code of those blocks).  `--config c2` / `--config c5` print those
-configurations alone.
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: set-up, warm-up, the timed
+pass, the outputs of --dump-outputs DIR (the records of the last timed pass, DIR/records.npy), the line.  Everything
+the benchmark measures BESIDE the headline runs with --full only: `roofline` of the step's dominant kernel (executed
+MFMA FLOPs / HIP-event time of its launches; `traffic` = PMC bytes per launch quoted from profiles/), `cpu_baseline`
+(the torch-CPU restatement on config 1's 16 frames), the side measurements (value_streamed, parity, Kalman rooflines,
+config 5, config 2, the f16x3 mode, multi-rank extras) and the GPU telemetry; bench_extra.py holds their code.
+
+OUTPUT.  The LAST stdout line is ONE compact JSON object (< 4 KB, no prose; `compact_line`): the contract fields and
+one number per side measurement that ran.  The full result -- per-kernel tables, telemetry, notes -- goes to the
+sidecar file --detail PATH (with --full by default bench_out/bench_detail.json).  `--config c2` / `--config c5` print
+those configurations alone.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -40,6 +45,8 @@ from bench_extra import (PEAK_F32_MFMA_TFLOPS, PEAK_HBM_GBS, Telemetry, auto_bat
                          per_kernel_profile, pipeline_io_bytes, timed_repetitions)
 
 COMPACT_LIMIT = 4096     # bytes; the driver reads a bounded tail of stdout (BENCH_r05: a 21 KB line was not parsed)
+DEFAULT_DETAIL = os.path.join(ROOT, 'bench_out', 'bench_detail.json')   # --full's sidecar unless --detail names one
+DUMP_LIMIT = 64 * 1000 * 1000                                           # bytes of --dump-outputs, all ranks together
 
 
 def _pick(d, *ks):
@@ -140,17 +147,18 @@ def _json_safe(o):
 
 
 def emit(out, args):
-    """Full result -> sidecar file; compact line -> the LAST line of stdout."""
+    """Full result -> sidecar file (if args.detail names one); compact line -> the LAST line of stdout."""
     out = _json_safe(out)
     path = args.detail
-    try:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, 'w') as f:
-            json.dump(out, f, indent=1, allow_nan=False)
-            f.write('\n')
-        out['detail_file'] = os.path.relpath(path, ROOT) if os.path.abspath(path).startswith(ROOT) else path
-    except OSError as e:
-        sys.stderr.write('bench.py: could not write %s: %s\n' % (path, e))
+    if path:
+        try:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, 'w') as f:
+                json.dump(out, f, indent=1, allow_nan=False)
+                f.write('\n')
+            out['detail_file'] = os.path.relpath(path, ROOT) if os.path.abspath(path).startswith(ROOT) else path
+        except OSError as e:
+            sys.stderr.write('bench.py: could not write %s: %s\n' % (path, e))
     sys.stdout.flush()
     print(compact_line(out), flush=True)
 
@@ -167,8 +175,15 @@ def parse():
     ap.add_argument('--batch', type=int, default=0,
                     help='frames per tower launch; 0 = auto: the size in 15..32 that splits --steps with the least '
                          'ragged tail (the rate is flat over that range; 17 when --steps is a multiple of 17)')
-    ap.add_argument('--min-seconds', type=float, default=2.0,
-                    help='repeat the K-step pass until this much time has been measured (median reported)')
+    ap.add_argument('--min-seconds', type=float, default=None,
+                    help='repeat the K-step pass until this much time has been measured (median reported); default: '
+                         'one pass of exactly --steps steps (the side measurements of --full, --config c2|c5: 2.0)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every measurement beside the headline (rooflines, per-kernel table, CPU baseline, '
+                         'other modes and configurations, multi-rank extras, telemetry) and write the --detail sidecar')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the records of the last timed pass as DIR/records.npy (float32 '
+                         '[K,h,w,4]; a seeded sample of frames when over 64 MB); multi-rank: records_rank<r>.npy')
     ap.add_argument('--sequences', type=int, default=4, help='c5: independent sequences per scan launch')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-host-streamed', action='store_true',
@@ -198,9 +213,16 @@ def parse():
                          'winograd_f43_eight_wave=0 (recorded in the line as graph_options)')
     ap.add_argument('--height', type=int, default=480)
     ap.add_argument('--width', type=int, default=640)
-    ap.add_argument('--detail', default=os.path.join(ROOT, 'gpurun_out', 'bench_detail.json'),
-                    help='sidecar file for the full result (per-kernel tables, telemetry, notes); stdout gets the compact line')
-    return ap.parse_args()
+    ap.add_argument('--detail', default=None,
+                    help='sidecar file for the full result (per-kernel tables, telemetry, notes); stdout gets the compact '
+                         'line (default: none; with --full %s)' % os.path.relpath(DEFAULT_DETAIL, ROOT))
+    args = ap.parse_args()
+    args.headline_min_seconds = args.min_seconds or 0.0
+    if args.min_seconds is None:
+        args.min_seconds = 2.0
+    if args.full and args.detail is None:
+        args.detail = DEFAULT_DETAIL
+    return args
 
 
 def self_launch(args):
@@ -251,6 +273,42 @@ def cpu_baseline(frames, W, T4, steps):
             'deduplicated_sample': '%d frames, towers once per frame, %.1f s' % (nd, dt_d)}, np.stack(recs)
 
 
+def synthetic_frames(T, H, W, start):
+    """= synthetic_sequence(T, H, W, seed=1, start=start), generated in slices on a few host threads (frame t depends
+    only on (seed, t): the array is the same; one thread spends ~12 ms per 480x640 frame, seconds for a long --steps)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from kfnet_amd.synth import synthetic_sequence
+    n = max(1, min(16, os.cpu_count() or 1, T // 16))
+    if n == 1:
+        return synthetic_sequence(T, H, W, seed=1, start=start)
+    out = np.empty((T, H, W, 3), dtype=np.uint8)
+
+    def part(i):
+        lo, hi = T * i // n, T * (i + 1) // n
+        out[lo:hi] = synthetic_sequence(hi - lo, H, W, seed=1, start=start + lo)
+    with ThreadPoolExecutor(n) as ex:
+        list(ex.map(part, range(n)))
+    return out
+
+
+def dump_outputs(path, records, rank, world):
+    """--dump-outputs: what the timed path hands its caller, the records [K,h,w,4] (x, y, z, confidence) of the last
+    timed pass, as float32 DIR/records.npy (records_rank<r>.npy per rank when world > 1).  Over DUMP_LIMIT / world
+    bytes: a fixed seeded sample of frames that always holds the last one, with its frame indices in
+    <name>_frames.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    rec = records.float().cpu().numpy()
+    name = 'records' if world == 1 else 'records_rank%d' % rank
+    K = rec.shape[0]
+    cap = max(1, DUMP_LIMIT // world // (rec[0].nbytes + 8)) if K else 0
+    if K > cap:
+        rng = np.random.default_rng(1234)
+        idx = np.sort(np.append(rng.choice(K - 1, cap - 1, replace=False), K - 1))
+        rec = rec[idx]
+        np.save(os.path.join(path, name + '_frames.npy'), idx.astype(np.float64))
+    np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(rec, dtype=np.float32))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ and args.config == 'c3':
@@ -299,7 +357,7 @@ def main():
     # (synthetic frames are generated per rank from the global frame index)
     lo = rank * K
     need_prev = 1 if needs_state(lo, 500) else 0
-    frames_all = synthetic_sequence(K + need_prev, args.height, args.width, seed=1, start=lo - need_prev)
+    frames_all = synthetic_frames(K + need_prev, args.height, args.width, start=lo - need_prev)
     gopts = {}
     for kv in args.graph_option:
         name, _, val = kv.partition('=')
@@ -321,10 +379,15 @@ def main():
         # (the full chunk: the send/recv pairing rule is a function of the chunk boundaries)
         run_chunk(eng, dev_frames, lo, rank, world, link, dev_prev)
         torch.cuda.synchronize()
-    tele = Telemetry(dev_index)
-    with tele:
-        times = timed_repetitions(lambda: run_chunk(eng, dev_frames, lo, rank, world, link, dev_prev),
-                                  dist, device, backend, args.min_seconds)
+    tele = Telemetry(dev_index) if args.full else None
+    last = {}
+
+    def timed_pass():
+        last['records'] = run_chunk(eng, dev_frames, lo, rank, world, link, dev_prev)
+    with tele if tele is not None else contextlib.nullcontext():
+        times = timed_repetitions(timed_pass, dist, device, backend, args.headline_min_seconds)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last['records'], rank, world)
     elapsed = float(np.median(times))
     # what every rank actually ran on: its device, and the (rank, nranks) its C-ABI RCCL communicator reports
     # (kfn_comm_rank; None when the hand-off goes through torch.distributed), all-gathered for the line
@@ -369,191 +432,194 @@ def main():
         'rccl_ranks': [ri['rccl'] for ri in ranks_info],
         'rank_devices': [ri['device'] for ri in ranks_info],
         'self_launched': bool(os.environ.get('KFN_BENCH_SELF_LAUNCHED')),
-        'gpu_telemetry_rank0': tele.summary(),
     }
-    # ---- collective extras of a multi-rank run (every rank takes part; rank 0 reports) -------------------
-    # The headline numbers are complete at this point.  The extras below are further collectives (event-timed chains, the
-    # block-cyclic pass, config 4): should one of them hang on a fabric this build has never run on (no multi-GPU box was
-    # available to it), a watchdog on every rank ends the process after KFN_BENCH_EXTRAS_DEADLINE seconds -- rank 0 prints the
-    # line it has, marked -- instead of leaving the driver without any line.
-    watchdog = None
-    if dist is not None:
-        import threading
-        deadline = float(os.environ.get('KFN_BENCH_EXTRAS_DEADLINE', '300'))
+    if tele is not None:
+        out['gpu_telemetry_rank0'] = tele.summary()
+    if args.full:
+        # ---- collective extras of a multi-rank run (every rank takes part; rank 0 reports) -------------------
+        # The headline numbers are complete at this point.  The extras below are further collectives (event-timed chains, the
+        # block-cyclic pass, config 4): should one of them hang on a fabric this build has never run on (no multi-GPU box was
+        # available to it), a watchdog on every rank ends the process after KFN_BENCH_EXTRAS_DEADLINE seconds -- rank 0 prints the
+        # line it has, marked -- instead of leaving the driver without any line.
+        watchdog = None
+        if dist is not None:
+            import threading
+            deadline = float(os.environ.get('KFN_BENCH_EXTRAS_DEADLINE', '300'))
 
-        def bail():
-            if rank == 0:
-                out['multi_rank_extras'] = ('TIMED OUT after %.0f s: handoff / sharding_cyclic / config4_2048_frames and the '
-                                            'rank-0 rooflines are missing from this line; the headline fields are complete' % deadline)
-                out['watchdog_fired'] = True
-                emit(out, args)
-            os._exit(3)
-        watchdog = threading.Timer(deadline, bail)
-        watchdog.daemon = True
-        watchdog.start()
-    if dist is not None:
-        extras_ok = [True]
+            def bail():
+                if rank == 0:
+                    out['multi_rank_extras'] = ('TIMED OUT after %.0f s: handoff / sharding_cyclic / config4_2048_frames and the '
+                                                'rank-0 rooflines are missing from this line; the headline fields are complete' % deadline)
+                    out['watchdog_fired'] = True
+                    emit(out, args)
+                os._exit(3)
+            watchdog = threading.Timer(deadline, bail)
+            watchdog.daemon = True
+            watchdog.start()
+        if dist is not None:
+            extras_ok = [True]
 
-        def extra(key, fn):
-            """An extra is a sequence of collectives: a rank that failed inside one must not walk into the next while its
-            peers are still in the previous (mispaired send/recv).  Every rank reports its outcome, all-reduced (MIN) after
-            each extra; after the first failure anywhere, every rank skips the rest.  (A rank that dies INSIDE a collective
-            leaves the others waiting: that case is the watchdog's.)"""
-            if not extras_ok[0]:
-                out[key] = {'error': 'skipped: an earlier multi-rank extra failed on some rank'}
-                return
-            ok = 1
-            try:
-                out[key] = fn()
-            except Exception as e:      # noqa: BLE001
-                out[key] = {'error': '%s: %s' % (type(e).__name__, e)}
-                ok = 0
-            flag = torch.tensor([ok], device=device if backend == 'nccl' else 'cpu', dtype=torch.int32)
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            if int(flag.item()) == 0:
-                extras_ok[0] = False
-                if ok:
-                    out[key] = dict(out[key] if isinstance(out[key], dict) else {}, error='failed on another rank')
-        extra('handoff', lambda: chain_timing(lambda timer: run_chunk(eng, dev_frames, lo, rank, world, link, dev_prev, timer=timer),
-                                              dist, device, world))
-        out['sharding'] = 'contiguous'       # of the headline `value`; the block-cyclic alternative is measured beside it
-        extra('sharding_cyclic', lambda: cyclic_sharding_block(args, eng, rank, world, K, link, dist, device, backend))
-        if world == 8 and K < 256 and not args.no_config3 and args.conv_operands == 'f32':
-            extra('config4_2048_frames', lambda: config4_literal(args, Wt, T4, rank, world, link, dist, device, backend, dev_index))
-    if watchdog is not None:
-        watchdog.cancel()
+            def extra(key, fn):
+                """An extra is a sequence of collectives: a rank that failed inside one must not walk into the next while its
+                peers are still in the previous (mispaired send/recv).  Every rank reports its outcome, all-reduced (MIN) after
+                each extra; after the first failure anywhere, every rank skips the rest.  (A rank that dies INSIDE a collective
+                leaves the others waiting: that case is the watchdog's.)"""
+                if not extras_ok[0]:
+                    out[key] = {'error': 'skipped: an earlier multi-rank extra failed on some rank'}
+                    return
+                ok = 1
+                try:
+                    out[key] = fn()
+                except Exception as e:      # noqa: BLE001
+                    out[key] = {'error': '%s: %s' % (type(e).__name__, e)}
+                    ok = 0
+                flag = torch.tensor([ok], device=device if backend == 'nccl' else 'cpu', dtype=torch.int32)
+                dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+                if int(flag.item()) == 0:
+                    extras_ok[0] = False
+                    if ok:
+                        out[key] = dict(out[key] if isinstance(out[key], dict) else {}, error='failed on another rank')
+            extra('handoff', lambda: chain_timing(lambda timer: run_chunk(eng, dev_frames, lo, rank, world, link, dev_prev, timer=timer),
+                                                  dist, device, world))
+            out['sharding'] = 'contiguous'       # of the headline `value`; the block-cyclic alternative is measured beside it
+            extra('sharding_cyclic', lambda: cyclic_sharding_block(args, eng, rank, world, K, link, dist, device, backend))
+            if world == 8 and K < 256 and not args.no_config3 and args.conv_operands == 'f32':
+                extra('config4_2048_frames', lambda: config4_literal(args, Wt, T4, rank, world, link, dist, device, backend, dev_index))
+        if watchdog is not None:
+            watchdog.cancel()
+        if rank == 0:
+            rows = per_kernel_profile(eng, dev_frames)
+            heavy_ms = sum(r[3] for r in rows)
+            by_kernel = {}
+            for r in rows:
+                k = by_kernel.setdefault(r[1], [0, 0.0, 0.0, 0.0])
+                k[0] += 1; k[1] += r[2]; k[2] += r[3]; k[3] += r[4]
+            # dominant kernel = the instantiation with the largest share of the step time
+            dom = max(by_kernel, key=lambda k: by_kernel[k][2])
+            n_dom, fl_dom, ms_dom, ex_dom = by_kernel[dom]
+            tf = fl_dom / (ms_dom * 1e-3) / 1e12
+            tf_exec = ex_dom / (ms_dom * 1e-3) / 1e12
+            conv_ms = sum(v[2] for k, v in by_kernel.items() if k.startswith('conv_mfma_kernel'))
+            conv_fl = sum(v[1] for k, v in by_kernel.items() if k.startswith('conv_mfma_kernel'))
+            # algorithmic HBM bytes of one launch of the dominant kernel: its input and output tensors once, its weights once
+            # (averaged over its launches of a batch, at the tower batch the PMC passes sampled so that it compares with them)
+            def alg_bytes(batch):
+                tot, n = 0.0, 0
+                for op in eng.heavy_ops:
+                    if hasattr(op, 'kernel_name') and op.kernel_name(eng.lib) == dom and hasattr(op, 'x') and hasattr(op, 'y'):
+                        esz = {'f32': 4, 'f16': 2, 'u8': 1}
+                        act = sum(float(np.prod(t.shape[1:])) * esz[t.dtype] for t in (op.x, op.y))
+                        tot += act * batch + float(np.prod(op.kernel.shape)) * 4
+                        n += 1
+                return int(tot / n) if n else None
+            traffic = None
+            tpath, tj = latest_pmc_traffic()
+            traffic = tj.get(dom)
+            if traffic is not None:
+                traffic = dict(traffic, algorithmic_bytes_per_launch=alg_bytes((tj.get('__sampled__') or {}).get('tower_batch', 32)))
+                # NOT measured by this run: PMC counters need their own rocprofv3 passes (tools/profile_round.sh)
+                traffic = dict(traffic, quoted_from=os.path.relpath(tpath, ROOT), sampled=tj.get('__sampled__', {
+                    'command': 'bench.py --steps 64 --batch 32', 'tower_batch': 32}), this_run_tower_batch=B)
+            out['roofline'] = {
+                'kernel': dom, 'bound': 'mfma',
+                # FLOPs the fp32 MFMA pipe actually executes in this kernel / its time.  For the direct implicit GEMM
+                # that IS the algorithmic (nominal dense) FLOP count of SURVEY App. C; the Winograd kernels execute
+                # 16/36 (F(2x2,3x3)) or 9/36 (F(4x4,3x3)) of it, so the hardware-utilisation number is reported here and
+                # the algorithmic rate beside it.
+                'achieved': round(tf_exec, 2), 'peak': PEAK_F32_MFMA_TFLOPS,
+                'unit': 'TFLOP/s', 'frac': round(tf_exec / PEAK_F32_MFMA_TFLOPS, 4),
+                'traffic': traffic,
+                'algorithmic_tflops': round(tf, 2),      # a rate (nominal FLOPs / time), NOT a fraction of the peak
+                'note': ('wino3_kernel / wino2_kernel = single-kernel Winograd F(2x2,3x3), wino4b_kernel / wino4_kernel = F(4x4,3x3) on eight / four waves '
+                         '(kfn_conv2d_winograd_fused, fp32; the waves of a workgroup share one input transform through LDS): '
+                         'achieved = FLOPs the MFMAs execute (16/36 resp. 9/36 of the nominal direct-convolution FLOPs + tile-block '
+                         'padding) / time, algorithmic_* counts the nominal FLOPs of SURVEY App. C and may exceed the MFMA peak; '
+                         'traffic = PMC HBM-side bytes per launch, averaged over the launches of a batch like avg_launch_ms. '
+                         'conv_mfma_kernel<TM,TN,WM,WN,BK,MODE,PREC>: MODE 0 direct implicit GEMM, 1 transposed, 2 the 16 GEMMs of the '
+                         'two-kernel Winograd form, 3 conv0 with the cost volume in the loader'),
+                'launches_per_batch': n_dom,
+                'algorithmic_gflop_per_launch_avg': round(fl_dom / n_dom / 1e9, 3),
+                'executed_gflop_per_launch_avg': round(ex_dom / n_dom / 1e9, 3),
+                'avg_launch_ms': round(ms_dom / n_dom, 4),
+                'share_of_step_time': round(ms_dom / heavy_ms, 4),
+                'all_conv_mfma_algorithmic_tflops': round(conv_fl / (conv_ms * 1e-3) / 1e12, 2) if conv_ms else None,
+                'all_conv_mfma_share_of_step_time': round(conv_ms / heavy_ms, 4),
+            }
+            out['kernels_ms_per_batch'] = {k: {'launches': v[0], 'ms': round(v[2], 4),
+                                               'tflops': round(v[1] / (v[2] * 1e-3) / 1e12, 2) if v[1] else None,
+                                               'executed_tflops': round(v[3] / (v[2] * 1e-3) / 1e12, 2) if v[3] else None}
+                                           for k, v in sorted(by_kernel.items(), key=lambda kv: -kv[1][2])}
+            out['per_kernel_ms_per_batch'] = {r[0] + ('#%d' % i): round(r[3], 4) for i, r in enumerate(rows)}
+            top = sorted(rows, key=lambda r: -r[3])[:6]
+            io_b = pipeline_io_bytes(eng)
+            out['pipeline_hbm'] = {
+                'algorithmic_bytes_per_frame': int(io_b / B),
+                'achieved_GBs': round(io_b / B * fps / 1e9, 1), 'peak': PEAK_HBM_GBS,
+                'frac_of_hbm_roofline': round(io_b / B * fps / 1e9 / PEAK_HBM_GBS, 4),
+                'note': 'layer-by-layer fp32 activation + weight traffic / frame time: the path is MFMA-bound, not HBM-bound'}
+            if eng.tuned:
+                out['autotuned_tile_config'] = {k.split('@')[0]: v[0] for k, v in eng.tuned.items()}
+            out['top_layers'] = [{'op': r[0], 'ms': round(r[3], 3),
+                                  'tflops': round(r[2] / (r[3] * 1e-3) / 1e12, 1) if r[2] else None} for r in top]
+            if not args.no_kalman_roofline:
+                out['roofline_kalman'] = kalman_roofline(device)                        # S = 256 x T = 64
+                out['roofline_kalman_T256'] = kalman_roofline(device, S=256, T=256)     # SURVEY 8(d)'s default shape
+                out['roofline_kalman_fuse'] = kalman_fuse_roofline(device)
+            single_480 = world == 1 and (args.height, args.width) == (480, 640) and args.conv_operands == 'f32'
+            if single_480 and not args.no_config3:
+                # the literal 256-frame pass of BASELINE configs[2], and on the same engine / sequence the two
+                # transfer-inclusive forms: frames from pinned host memory, and PNG files -> coord_<i>.npy files
+                c3, extra = config3_literal(args, Wt, T4, synthetic_transform(), device, dev_index)
+                if K < 256:
+                    out['config3_256_frames'] = c3
+                out.update(extra)
+            elif world == 1 and not args.no_host_streamed:
+                out['host_streamed'] = host_streamed(eng, frames_all[need_prev:], dev_frames)
+            if world == 1 and not args.no_cpu_baseline:
+                host_frames = frames_all[need_prev:need_prev + max(args.cpu_steps, 2)]
+                if host_frames.shape[0] < max(args.cpu_steps, 2):     # --steps below config 1's 16 frames
+                    host_frames = synthetic_sequence(max(args.cpu_steps, 2), args.height, args.width, seed=1)
+                cb, cpu_recs = cpu_baseline(host_frames, Wt, T4, args.cpu_steps)
+                cb['sample_is_config1'] = bool(args.cpu_steps == 16)
+                out['cpu_baseline'] = cb
+                gpu_recs = eng.process(eng.upload_frames(host_frames[:args.cpu_steps]), t0=0).cpu().numpy()
+                out['parity_vs_cpu_restatement'] = {
+                    'frames': int(args.cpu_steps),
+                    'coord_max_abs': float(np.abs(gpu_recs[..., :3] - cpu_recs[..., :3]).max()),
+                    'conf_max_rel': float((np.abs(gpu_recs[..., 3] - cpu_recs[..., 3]) / np.abs(cpu_recs[..., 3])).max()),
+                    'tolerance': 'coord max-abs <= 1e-4, confidence max-rel <= 1e-4'}
+                out['speedup_vs_cpu_baseline'] = round(fps / cb['value'], 1)
+                if not args.no_alt_modes and args.conv_operands == 'f32':
+                    # NOT the headline: same workload with every wide forward conv evaluated as
+                    # hi*hi + hi*lo + lo*hi of fp16-split operands on the fp16 MFMA (fp32 accumulate)
+                    eng2 = KFNetEngine(Wt, image_size=(args.height, args.width), batch=B, transform=T4, reset_period=500,
+                                       max_chunk=max(K, Wm, B, args.cpu_steps), device=str(device), conv_operands='f16x3')
+                    eng2.process(dev_frames[:min(Wm, K)], t0=0)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    eng2.process(dev_frames, t0=0)
+                    torch.cuda.synchronize()
+                    dt2 = time.perf_counter() - t0
+                    g2 = eng2.process(eng2.upload_frames(host_frames[:args.cpu_steps]), t0=0).cpu().numpy()
+                    del eng2
+                    out['alt_mode_f16x3'] = {
+                        'value': round(K / dt2, 3), 'unit': 'frames/s',
+                        'dtype': 'f32 emulated: operands split into fp16 hi+lo, 3 fp16-MFMA products, f32 accumulate',
+                        'coord_max_abs_vs_cpu': float(np.abs(g2[..., :3] - cpu_recs[..., :3]).max()),
+                        'conf_max_rel_vs_cpu': float((np.abs(g2[..., 3] - cpu_recs[..., 3]) / np.abs(cpu_recs[..., 3])).max()),
+                        'note': 'opt-in (KFNetEngine(conv_operands="f16x3")); reported beside, never as, the fp32 headline value'}
+            if single_480 and not args.no_extra_configs:
+                # BASELINE configs[4] and configs[1] inside the driver's one line (VERDICT r3 Next #1)
+                del eng
+                torch.cuda.empty_cache()
+                c5 = measure_c5(args, device, T=64, min_seconds=2.0, with_parity=True)
+                out['config5_960x540'] = {k: c5[k] for k in ('value', 'unit', 'ms_per_step', 'dtype', 'steps', 'repetitions', 'config',
+                                                              'roofline', 'gpu_telemetry', 'kernels_ms_per_batch', 'tolerance',
+                                                              'parity_vs_fp32_path') if k in c5}
+                c2 = measure_c2(args, device, min_seconds=1.0, min_steps=50)
+                out['config2_single_frame'] = {k: c2[k] for k in ('value', 'unit', 'ms_per_step', 'dtype', 'config', 'latency_ms',
+                                                                   'roofline', 'per_layer_batch1')}
     if rank == 0:
-        rows = per_kernel_profile(eng, dev_frames)
-        heavy_ms = sum(r[3] for r in rows)
-        by_kernel = {}
-        for r in rows:
-            k = by_kernel.setdefault(r[1], [0, 0.0, 0.0, 0.0])
-            k[0] += 1; k[1] += r[2]; k[2] += r[3]; k[3] += r[4]
-        # dominant kernel = the instantiation with the largest share of the step time
-        dom = max(by_kernel, key=lambda k: by_kernel[k][2])
-        n_dom, fl_dom, ms_dom, ex_dom = by_kernel[dom]
-        tf = fl_dom / (ms_dom * 1e-3) / 1e12
-        tf_exec = ex_dom / (ms_dom * 1e-3) / 1e12
-        conv_ms = sum(v[2] for k, v in by_kernel.items() if k.startswith('conv_mfma_kernel'))
-        conv_fl = sum(v[1] for k, v in by_kernel.items() if k.startswith('conv_mfma_kernel'))
-        # algorithmic HBM bytes of one launch of the dominant kernel: its input and output tensors once, its weights once
-        # (averaged over its launches of a batch, at the tower batch the PMC passes sampled so that it compares with them)
-        def alg_bytes(batch):
-            tot, n = 0.0, 0
-            for op in eng.heavy_ops:
-                if hasattr(op, 'kernel_name') and op.kernel_name(eng.lib) == dom and hasattr(op, 'x') and hasattr(op, 'y'):
-                    esz = {'f32': 4, 'f16': 2, 'u8': 1}
-                    act = sum(float(np.prod(t.shape[1:])) * esz[t.dtype] for t in (op.x, op.y))
-                    tot += act * batch + float(np.prod(op.kernel.shape)) * 4
-                    n += 1
-            return int(tot / n) if n else None
-        traffic = None
-        tpath, tj = latest_pmc_traffic()
-        traffic = tj.get(dom)
-        if traffic is not None:
-            traffic = dict(traffic, algorithmic_bytes_per_launch=alg_bytes((tj.get('__sampled__') or {}).get('tower_batch', 32)))
-            # NOT measured by this run: PMC counters need their own rocprofv3 passes (tools/profile_round.sh)
-            traffic = dict(traffic, quoted_from=os.path.relpath(tpath, ROOT), sampled=tj.get('__sampled__', {
-                'command': 'bench.py --steps 64 --batch 32', 'tower_batch': 32}), this_run_tower_batch=B)
-        out['roofline'] = {
-            'kernel': dom, 'bound': 'mfma',
-            # FLOPs the fp32 MFMA pipe actually executes in this kernel / its time.  For the direct implicit GEMM
-            # that IS the algorithmic (nominal dense) FLOP count of SURVEY App. C; the Winograd kernels execute
-            # 16/36 (F(2x2,3x3)) or 9/36 (F(4x4,3x3)) of it, so the hardware-utilisation number is reported here and
-            # the algorithmic rate beside it.
-            'achieved': round(tf_exec, 2), 'peak': PEAK_F32_MFMA_TFLOPS,
-            'unit': 'TFLOP/s', 'frac': round(tf_exec / PEAK_F32_MFMA_TFLOPS, 4),
-            'traffic': traffic,
-            'algorithmic_tflops': round(tf, 2),      # a rate (nominal FLOPs / time), NOT a fraction of the peak
-            'note': ('wino3_kernel / wino2_kernel = single-kernel Winograd F(2x2,3x3), wino4b_kernel / wino4_kernel = F(4x4,3x3) on eight / four waves '
-                     '(kfn_conv2d_winograd_fused, fp32; the waves of a workgroup share one input transform through LDS): '
-                     'achieved = FLOPs the MFMAs execute (16/36 resp. 9/36 of the nominal direct-convolution FLOPs + tile-block '
-                     'padding) / time, algorithmic_* counts the nominal FLOPs of SURVEY App. C and may exceed the MFMA peak; '
-                     'traffic = PMC HBM-side bytes per launch, averaged over the launches of a batch like avg_launch_ms. '
-                     'conv_mfma_kernel<TM,TN,WM,WN,BK,MODE,PREC>: MODE 0 direct implicit GEMM, 1 transposed, 2 the 16 GEMMs of the '
-                     'two-kernel Winograd form, 3 conv0 with the cost volume in the loader'),
-            'launches_per_batch': n_dom,
-            'algorithmic_gflop_per_launch_avg': round(fl_dom / n_dom / 1e9, 3),
-            'executed_gflop_per_launch_avg': round(ex_dom / n_dom / 1e9, 3),
-            'avg_launch_ms': round(ms_dom / n_dom, 4),
-            'share_of_step_time': round(ms_dom / heavy_ms, 4),
-            'all_conv_mfma_algorithmic_tflops': round(conv_fl / (conv_ms * 1e-3) / 1e12, 2) if conv_ms else None,
-            'all_conv_mfma_share_of_step_time': round(conv_ms / heavy_ms, 4),
-        }
-        out['kernels_ms_per_batch'] = {k: {'launches': v[0], 'ms': round(v[2], 4),
-                                           'tflops': round(v[1] / (v[2] * 1e-3) / 1e12, 2) if v[1] else None,
-                                           'executed_tflops': round(v[3] / (v[2] * 1e-3) / 1e12, 2) if v[3] else None}
-                                       for k, v in sorted(by_kernel.items(), key=lambda kv: -kv[1][2])}
-        out['per_kernel_ms_per_batch'] = {r[0] + ('#%d' % i): round(r[3], 4) for i, r in enumerate(rows)}
-        top = sorted(rows, key=lambda r: -r[3])[:6]
-        io_b = pipeline_io_bytes(eng)
-        out['pipeline_hbm'] = {
-            'algorithmic_bytes_per_frame': int(io_b / B),
-            'achieved_GBs': round(io_b / B * fps / 1e9, 1), 'peak': PEAK_HBM_GBS,
-            'frac_of_hbm_roofline': round(io_b / B * fps / 1e9 / PEAK_HBM_GBS, 4),
-            'note': 'layer-by-layer fp32 activation + weight traffic / frame time: the path is MFMA-bound, not HBM-bound'}
-        if eng.tuned:
-            out['autotuned_tile_config'] = {k.split('@')[0]: v[0] for k, v in eng.tuned.items()}
-        out['top_layers'] = [{'op': r[0], 'ms': round(r[3], 3),
-                              'tflops': round(r[2] / (r[3] * 1e-3) / 1e12, 1) if r[2] else None} for r in top]
-        if not args.no_kalman_roofline:
-            out['roofline_kalman'] = kalman_roofline(device)                        # S = 256 x T = 64
-            out['roofline_kalman_T256'] = kalman_roofline(device, S=256, T=256)     # SURVEY 8(d)'s default shape
-            out['roofline_kalman_fuse'] = kalman_fuse_roofline(device)
-        single_480 = world == 1 and (args.height, args.width) == (480, 640) and args.conv_operands == 'f32'
-        if single_480 and not args.no_config3:
-            # the literal 256-frame pass of BASELINE configs[2], and on the same engine / sequence the two
-            # transfer-inclusive forms: frames from pinned host memory, and PNG files -> coord_<i>.npy files
-            c3, extra = config3_literal(args, Wt, T4, synthetic_transform(), device, dev_index)
-            if K < 256:
-                out['config3_256_frames'] = c3
-            out.update(extra)
-        elif world == 1 and not args.no_host_streamed:
-            out['host_streamed'] = host_streamed(eng, frames_all[need_prev:], dev_frames)
-        if world == 1 and not args.no_cpu_baseline:
-            host_frames = frames_all[need_prev:need_prev + max(args.cpu_steps, 2)]
-            if host_frames.shape[0] < max(args.cpu_steps, 2):     # --steps below config 1's 16 frames
-                host_frames = synthetic_sequence(max(args.cpu_steps, 2), args.height, args.width, seed=1)
-            cb, cpu_recs = cpu_baseline(host_frames, Wt, T4, args.cpu_steps)
-            cb['sample_is_config1'] = bool(args.cpu_steps == 16)
-            out['cpu_baseline'] = cb
-            gpu_recs = eng.process(eng.upload_frames(host_frames[:args.cpu_steps]), t0=0).cpu().numpy()
-            out['parity_vs_cpu_restatement'] = {
-                'frames': int(args.cpu_steps),
-                'coord_max_abs': float(np.abs(gpu_recs[..., :3] - cpu_recs[..., :3]).max()),
-                'conf_max_rel': float((np.abs(gpu_recs[..., 3] - cpu_recs[..., 3]) / np.abs(cpu_recs[..., 3])).max()),
-                'tolerance': 'coord max-abs <= 1e-4, confidence max-rel <= 1e-4'}
-            out['speedup_vs_cpu_baseline'] = round(fps / cb['value'], 1)
-            if not args.no_alt_modes and args.conv_operands == 'f32':
-                # NOT the headline: same workload with every wide forward conv evaluated as
-                # hi*hi + hi*lo + lo*hi of fp16-split operands on the fp16 MFMA (fp32 accumulate)
-                eng2 = KFNetEngine(Wt, image_size=(args.height, args.width), batch=B, transform=T4, reset_period=500,
-                                   max_chunk=max(K, Wm, B, args.cpu_steps), device=str(device), conv_operands='f16x3')
-                eng2.process(dev_frames[:min(Wm, K)], t0=0)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                eng2.process(dev_frames, t0=0)
-                torch.cuda.synchronize()
-                dt2 = time.perf_counter() - t0
-                g2 = eng2.process(eng2.upload_frames(host_frames[:args.cpu_steps]), t0=0).cpu().numpy()
-                del eng2
-                out['alt_mode_f16x3'] = {
-                    'value': round(K / dt2, 3), 'unit': 'frames/s',
-                    'dtype': 'f32 emulated: operands split into fp16 hi+lo, 3 fp16-MFMA products, f32 accumulate',
-                    'coord_max_abs_vs_cpu': float(np.abs(g2[..., :3] - cpu_recs[..., :3]).max()),
-                    'conf_max_rel_vs_cpu': float((np.abs(g2[..., 3] - cpu_recs[..., 3]) / np.abs(cpu_recs[..., 3])).max()),
-                    'note': 'opt-in (KFNetEngine(conv_operands="f16x3")); reported beside, never as, the fp32 headline value'}
-        if single_480 and not args.no_extra_configs:
-            # BASELINE configs[4] and configs[1] inside the driver's one line (VERDICT r3 Next #1)
-            del eng
-            torch.cuda.empty_cache()
-            c5 = measure_c5(args, device, T=64, min_seconds=2.0, with_parity=True)
-            out['config5_960x540'] = {k: c5[k] for k in ('value', 'unit', 'ms_per_step', 'dtype', 'steps', 'repetitions', 'config',
-                                                          'roofline', 'gpu_telemetry', 'kernels_ms_per_batch', 'tolerance',
-                                                          'parity_vs_fp32_path') if k in c5}
-            c2 = measure_c2(args, device, min_seconds=1.0, min_steps=50)
-            out['config2_single_frame'] = {k: c2[k] for k in ('value', 'unit', 'ms_per_step', 'dtype', 'config', 'latency_ms',
-                                                               'roofline', 'per_layer_batch1')}
         emit(out, args)
     if link is not None:
         link.close()

@@ -91,14 +91,14 @@ def test_two_rank_state_transfer_over_rccl(tmp_path):
            '--master-addr', '127.0.0.1', '--master-port', str(_free_port()), str(script)]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
-    # ... and the benchmark's own two-rank form on the same two GPUs: the plain command the driver would run, which
-    # must end on the production transport and report RCCL's OWN view of the communicator (Next #4d)
+    # ... and the benchmark's own two-rank form on the same two GPUs (with --full: the hand-off timing is a side
+    # measurement), which must end on the production transport and report RCCL's OWN view of the communicator (Next #4d)
     import json
     env = dict(os.environ)
     env.pop('WORLD_SIZE', None)
     env.pop('RANK', None)
     b = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '8', '--warmup', '2',
-                        '--min-seconds', '0.5', '--no-kalman-roofline', '--detail', str(tmp_path / 'detail.json')],
+                        '--min-seconds', '0.5', '--no-kalman-roofline', '--full', '--detail', str(tmp_path / 'detail.json')],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env, cwd=ROOT)
     assert b.returncode == 0, b.stderr[-3000:]
     compact = json.loads(b.stdout.strip().splitlines()[-1])

@@ -704,6 +704,39 @@ def test_bench_compact_line_fits_the_drivers_reader(tmp_path, capsys):
     assert src.count("__name__ == '__main__'") == 1 and src.rstrip().endswith('main()')
 
 
+def test_bench_dump_outputs_and_plain_run_defaults(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 records, all of them under the size cap; past it a seeded frame sample that holds the
+    last frame, the same on every run, with its indices.  A plain run times exactly --steps steps and writes no sidecar;
+    --full writes one and keeps the 2 s side measurements; the seeded frames are those of synthetic_sequence."""
+    import sys
+    import torch
+    from kfnet_amd.synth import synthetic_sequence
+    bench, _ = _load_bench()
+    rec = torch.arange(40 * 6 * 8 * 4, dtype=torch.float32).reshape(40, 6, 8, 4)
+    bench.dump_outputs(str(tmp_path / 'all'), rec, 0, 1)
+    assert os.listdir(tmp_path / 'all') == ['records.npy']
+    got = np.load(tmp_path / 'all' / 'records.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, rec.numpy())
+    bench.DUMP_LIMIT = 2 * 5 * (6 * 8 * 4 * 4 + 8)        # five frames per rank of two
+    for d in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / d), rec, 1, 2)
+    assert sorted(os.listdir(tmp_path / 's1')) == ['records_rank1.npy', 'records_rank1_frames.npy']
+    idx = np.load(tmp_path / 's1' / 'records_rank1_frames.npy')
+    assert idx.dtype == np.float64 and len(idx) == 5 and idx[-1] == 39 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / 's2' / 'records_rank1_frames.npy'))
+    assert np.array_equal(np.load(tmp_path / 's1' / 'records_rank1.npy'), rec.numpy()[idx.astype(int)])
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse()
+    assert a.headline_min_seconds == 0 and a.detail is None and not a.full and a.min_seconds == 2.0
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full'])
+    a = bench.parse()
+    assert a.full and a.headline_min_seconds == 0 and a.detail == bench.DEFAULT_DETAIL and a.min_seconds == 2.0
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--min-seconds', '0.5'])
+    assert bench.parse().headline_min_seconds == 0.5
+    for T, start in ((1, 0), (35, 4), (50, 300)):
+        assert np.array_equal(bench.synthetic_frames(T, 16, 24, start), synthetic_sequence(T, 16, 24, seed=1, start=start))
+
+
 def test_f43_split_k_is_chosen_for_single_frames_only():
     """BASELINE configs[1] (one 480x640 frame): SCoordNet's conv4b / conv5 / conv6 launch 160 / 80 / 40 F(4x4,3x3) workgroups on
     256 CUs -- Network.conv splits their input channels (WinogradF43ConvOp.best_k_split) so that the launch fills the chip; every
