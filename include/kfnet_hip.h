@@ -43,8 +43,9 @@ extern "C" {
  * kfn_abi_version() == KFN_ABI_VERSION once after loading the library.
  * 6 (round 5): split-K Winograd entry points, kfn_winograd_lds_bytes.  7 (round 5): kfn_decode_png_rgb8.
  * 8 (round 6): KFN_WINO_FORM_S2_F42, kfn_apply_transform / kfn_pixel_map / kfn_bilinear_sampler.
- * 9 (round 6): kfn_conv_desc.x_layout / y_layout (KFN_LAYOUT_C16).  10 (round 6): kfn_kalman_arith_probe. */
-#define KFN_ABI_VERSION 10
+ * 9 (round 6): kfn_conv_desc.x_layout / y_layout (KFN_LAYOUT_C16).  10 (round 6): kfn_kalman_arith_probe.
+ * 11: camera poses -- kfn_pnp_desc, kfn_pnp_scratch_bytes, kfn_pnp_ransac, kfn_pnp_hypotheses. */
+#define KFN_ABI_VERSION 11
 
 const char* kfn_last_error(void);
 int kfn_abi_version(void);
@@ -516,6 +517,54 @@ int kfn_bilinear_sampler(const float* imgs, int ld_img, int B, int Hs, int Ws, i
 /* ---- Network.concat fallback (cnn_wrapper/network.py:316-318): strided channel copy -- */
 int kfn_copy_channels(const float* src, int ld_src, float* dst, int ld_dst, int P, int C,
                       void* stream);
+
+/* ---- camera poses: batched RANSAC-PnP on the scan's records (ABI 11) -----------------------------------------------
+ * No reference counterpart on the device: the reference hands coord_<i>.npy to an external PnP program (README.md:132-138)
+ * that it does not ship.  records [B,h,w,ld] = (x, y, z, 1/sigma) in the scene frame (the scan's output, ld >= 4 floats per
+ * cell); one camera-to-world pose per frame, everything on the device (DESIGN.md "Camera poses" fixes each step):
+ *   correspondence   cell (r, c) observes image pixel (cell_stride*c, cell_stride*r) with pinhole intrinsics fx, fy, u, v;
+ *                    it is a candidate iff 1/sigma > min_confidence and x, y, z are finite; candidates in raster order
+ *   sampling         h = lowbias32(seed ^ frame*0x9E3779B1 ^ hyp*0x85EBCA77 ^ draw*0xC2B2AE3D), frame = t0 + b (global),
+ *                    candidate (uint64(h) * n) >> 32; draws continue to 4 distinct indices, at most 16 draws
+ *   hypothesis       P3P (Grunert's quartic, fp64) on the first three, the fourth picks the solution; no real solution or a
+ *                    point behind the camera: invalid
+ *   scoring          inlier iff camera-frame Z > 0 and the reprojection error < inlier_px full-resolution pixels (fp32)
+ *   selection        most inliers, ties to the lowest hypothesis index
+ *   refinement       refine_iters Gauss-Newton steps (so(3) + translation) over the inliers of the current pose, fp64
+ *                    normal equations in a fixed order; a step is kept only if it lowers the cost over that inlier set
+ * Results are bit-identical from launch to launch, and a frame's pose does not depend on the batch it is solved in. */
+#define KFN_PNP_OK 0
+#define KFN_PNP_TOO_FEW_POINTS 1     /* fewer than min_points candidates */
+#define KFN_PNP_NO_HYPOTHESIS 2      /* no hypothesis survived sampling and P3P */
+#define KFN_PNP_MAX_HYPOTHESES 1024
+typedef struct kfn_pnp_desc {
+  int32_t struct_size;     /* = sizeof(kfn_pnp_desc) as the caller compiled it; grows at its end like kfn_conv_desc */
+  int32_t B, h, w;         /* frames, grid rows, grid columns (h * w <= 32768) */
+  int32_t ld;              /* floats per cell in `records`, >= 4 */
+  int32_t t0;              /* global index of frame 0 of this call (the sampling counter) */
+  uint32_t seed;
+  int32_t hypotheses;      /* 1 .. KFN_PNP_MAX_HYPOTHESES */
+  int32_t refine_iters;    /* Gauss-Newton iterations, 0 .. 100 */
+  int32_t min_points;      /* fewer candidates: KFN_PNP_TOO_FEW_POINTS; >= 4 */
+  float fx, fy, u, v;      /* pinhole intrinsics of the full-resolution image */
+  int32_t cell_stride;     /* pixels per grid cell (8) */
+  float min_confidence;    /* 20, as tools/io.confident_points */
+  float inlier_px;         /* 10 */
+} kfn_pnp_desc;
+/* kfn_pnp_desc d = KFN_PNP_DESC_INIT;  -- zero everything, set struct_size */
+#define KFN_PNP_DESC_INIT {(int32_t)sizeof(kfn_pnp_desc)}
+
+/* Bytes of the caller's scratch for a ransac call on `desc` (hypothesis poses and counts). */
+int kfn_pnp_scratch_bytes(const kfn_pnp_desc* desc, size_t* bytes);
+int kfn_pnp_ransac(const kfn_pnp_desc* desc, const float* records,
+                   float* poses,          /* [B,16] camera-to-world, row-major; NaN where status != KFN_PNP_OK */
+                   int32_t* info,         /* [B,4] = (status, candidates, final inliers, best hypothesis or -1) */
+                   void* scratch,         /* the scratch-bytes query's size, 16-byte aligned */
+                   void* stream);
+/* Probe of the first two stages, for tests: samples [B,H,4] candidate indices (-1: no 4 distinct in 16 draws, or too few
+ * candidates), hyp_poses [B,H,12] = [R | t] world-to-camera in fp32 (NaN: invalid), counts [B,H] inliers (-1: invalid). */
+int kfn_pnp_hypotheses(const kfn_pnp_desc* desc, const float* records, int32_t* samples, float* hyp_poses, int32_t* counts,
+                       void* stream);
 
 /* ---- multi-GPU: rank -> rank hand-off of the recurrent state (RCCL point-to-point) ----
  * No reference counterpart (the reference is single-device: KFNet/train.py:375 is its only

@@ -20,6 +20,8 @@ raw (untransformed, ungated) KF state fed back, NIS gate on the output only.
 When label_list.txt is present the reference's per-frame log line (losses, accuracies, median
 distance errors in cm, NIS-in-band fraction) and the final summary are printed
 (kfnet_amd/KFNet/metrics.py).  Not reproduced: --show plotting.
+`--pose` (single process only) also solves every frame's camera pose on the device (kfnet_amd/KFNet/pnp.py) and writes
+`pose_<i>.txt` next to each `coord_<i>.npy`.
 """
 import argparse
 import os
@@ -267,7 +269,13 @@ def main(argv=None):
     ap.add_argument('--sharding', choices=['contiguous', 'cyclic'], default='contiguous',
                     help='multi-process runs: contiguous chunks per rank, or blocks of --block frames dealt round-robin')
     ap.add_argument('--block', type=int, default=32, help='--sharding cyclic: frames per block')
+    ap.add_argument('--pose', action='store_true', help='also write pose_<i>.txt (RANSAC-PnP on the device; single process)')
     a = ap.parse_args(argv)
+    world = int(os.environ.get('WORLD_SIZE', '1'))
+    if a.pose and world > 1:
+        print('--pose is not supported in the sharded run (WORLD_SIZE=%d): run single-process '
+              '(python -m kfnet_amd.KFNet.eval --gpu N ... --pose)' % world, file=sys.stderr)
+        return 2
     if a.scene not in SCENES:
         print('Invalid scene:', a.scene)   # KFNet/train.py:142-144
         return 1
@@ -281,7 +289,6 @@ def main(argv=None):
         W = load_npz(snapshot)
     import torch
     size = (a.height, a.width)
-    world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     if world > 1:
         return _main_sharded(a, W, size, rank, world)
@@ -291,7 +298,10 @@ def main(argv=None):
         from ..synth import synthetic_sequence, synthetic_transform
         frames = synthetic_sequence(a.synthetic, a.height, a.width)
         transform = np.linalg.inv(synthetic_transform())
-        eval(None, transform, W, a.output_folder, a.NIS, image_size=size, frames=frames, batch=a.batch, device=device)
+        records = eval(None, transform, W, a.output_folder, a.NIS, image_size=size, frames=frames, batch=a.batch,
+                       device=device)
+        if a.pose:
+            write_poses(records, a.output_folder)
         return 0
     image_list = os.path.join(a.input_folder, 'image_list.txt')
     transform_file = os.path.join(a.input_folder, 'transform.txt')
@@ -304,10 +314,27 @@ def main(argv=None):
     label_paths = read_lines(label_list) if os.path.exists(label_list) else None
     if label_paths is not None:
         assert len(image_paths) == len(label_paths)   # KFNet/eval.py:37
-    eval(image_paths, get_transform(transform_file), W, a.output_folder, a.NIS, image_size=size, batch=a.batch,
-         label_paths=label_paths, device=device,
-         metrics_sequence_length=M_TEST_SEQUENCE_LENGTH.get(a.scene, 1000))
+    out = eval(image_paths, get_transform(transform_file), W, a.output_folder, a.NIS, image_size=size, batch=a.batch,
+               label_paths=label_paths, device=device,
+               metrics_sequence_length=M_TEST_SEQUENCE_LENGTH.get(a.scene, 1000))
+    if a.pose:
+        write_poses(out[0] if label_paths is not None else out, a.output_folder)
     return 0
+
+
+def write_poses(records, output_folder, batch=64):
+    """--pose: camera-to-world poses of the in-memory records [T,h,w,4] (KFNetDataSpec intrinsics), pose_<i>.txt next
+    to coord_<i>.npy.  Returns (poses [T,4,4], info [T,4])."""
+    from .KFNet import KFNetDataSpec
+    from .pnp import PnPSolver, solve_in_batches, write_pose
+    spec = KFNetDataSpec()
+    solver = PnPSolver(records.shape[1], records.shape[2], spec.focal_x, spec.focal_y, spec.u, spec.v)
+    poses, info = solve_in_batches(solver, records, batch)
+    if output_folder and os.path.isdir(output_folder):
+        for i in range(records.shape[0]):
+            write_pose(os.path.join(output_folder, 'pose_%d.txt' % i), poses[i])
+    print('poses: %d of %d frames solved' % (int((info[:, 0] == 0).sum()), records.shape[0]))
+    return poses, info
 
 
 def _main_sharded(a, W, size, rank, world):

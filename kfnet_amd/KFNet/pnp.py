@@ -1,0 +1,205 @@
+"""Camera poses from the scene-coordinate maps: batched RANSAC-PnP on the device (kfn_pnp_ransac, ABI 11).
+
+The reference hands its `coord_<i>.npy` maps to an external PnP program (README.md:81-84,132-138) that it ships only as
+a git-lfs pointer; this module is that last stage, with the reference's command-line shape:
+
+    python -m kfnet_amd.KFNet.pnp <coord_file_list> <output_folder> [--gt <pose_list>] [--thread_num N]
+                                  [--focal_x F --focal_y F --u U --v V] [--hypotheses 256] [--batch 64]
+
+writes one `pose_<i>.txt` (4x4 camera-to-world, the 7-Scenes `frame-*.pose.txt` format; NaN where no pose was found)
+per listed map, i = the map's position in the list.  With --gt (one pose file per map) it prints every frame's rotation
+and translation error, their medians and the share of frames within 5 cm / 5 degrees.  The geometry (cell (r, c)
+observes pixel (8c, 8r)), the candidate rule and the sampling are fixed in DESIGN.md "Camera poses".
+"""
+import argparse
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+
+from .. import _lib
+from ..tools.io import read_lines
+
+STATUS_NAMES = {_lib.PNP_OK: 'ok', _lib.PNP_TOO_FEW_POINTS: 'too few points', _lib.PNP_NO_HYPOTHESIS: 'no hypothesis'}
+
+
+class PnPSolver(object):
+    """RANSAC-PnP over [B,h,w,>=4] records (x, y, z, 1/sigma) of an h x w grid.  Intrinsics default to KFNetDataSpec
+    (fx = fy = 525, u = 320, v = 240).  `solve` returns camera-to-world poses [B,4,4] (NaN on failure) and info [B,4] =
+    (status, candidates, final inliers, best hypothesis): numpy in, numpy out; a CUDA tensor in, tensors out (no sync)."""
+
+    def __init__(self, h, w, fx=525., fy=525., u=320., v=240., hypotheses=256, refine_iters=10, min_points=16, seed=0,
+                 min_confidence=20., inlier_px=10., cell_stride=8):
+        if not 1 <= int(hypotheses) <= _lib.PNP_MAX_HYPOTHESES:
+            raise ValueError('hypotheses must be in 1..%d' % _lib.PNP_MAX_HYPOTHESES)
+        self.h, self.w = int(h), int(w)
+        self.fx, self.fy, self.u, self.v = float(fx), float(fy), float(u), float(v)
+        self.hypotheses, self.refine_iters, self.min_points = int(hypotheses), int(refine_iters), int(min_points)
+        self.seed, self.min_confidence, self.inlier_px = int(seed) & 0xFFFFFFFF, float(min_confidence), float(inlier_px)
+        self.cell_stride = int(cell_stride)
+        self._scratch = None
+
+    def desc(self, B, t0=0, ld=4):
+        return _lib.PnPDesc(B=B, h=self.h, w=self.w, ld=ld, t0=t0, seed=self.seed, hypotheses=self.hypotheses,
+                            refine_iters=self.refine_iters, min_points=self.min_points, fx=self.fx, fy=self.fy, u=self.u,
+                            v=self.v, cell_stride=self.cell_stride, min_confidence=self.min_confidence,
+                            inlier_px=self.inlier_px)
+
+    def _device_records(self, records):
+        import torch
+        host = not isinstance(records, torch.Tensor)
+        if host:
+            records = torch.from_numpy(np.ascontiguousarray(records, dtype=np.float32)).cuda()
+        if records.dtype != torch.float32 or not records.is_cuda:
+            raise TypeError('records must be float32 on a CUDA (HIP) device')
+        if records.dim() != 4 or tuple(records.shape[1:3]) != (self.h, self.w) or records.shape[3] < 4:
+            raise ValueError('records must be [B,%d,%d,>=4], got %s' % (self.h, self.w, tuple(records.shape)))
+        records = records.contiguous()
+        return records, host
+
+    def solve(self, records, t0=0):
+        import torch
+        lib = _lib.load()
+        rec, host = self._device_records(records)
+        B = rec.shape[0]
+        d = self.desc(B, t0, rec.shape[3])
+        nbytes = C.c_size_t()
+        _lib.check(lib.kfn_pnp_scratch_bytes(C.byref(d), C.byref(nbytes)), 'kfn_pnp_scratch_bytes')
+        if self._scratch is None or self._scratch.numel() < nbytes.value or self._scratch.device != rec.device:
+            self._scratch = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=rec.device)
+        poses = torch.empty((B, 4, 4), dtype=torch.float32, device=rec.device)
+        info = torch.empty((B, 4), dtype=torch.int32, device=rec.device)
+        stream = torch.cuda.current_stream(rec.device).cuda_stream
+        _lib.check(lib.kfn_pnp_ransac(C.byref(d), rec.data_ptr(), poses.data_ptr(), info.data_ptr(),
+                                      self._scratch.data_ptr(), stream), 'kfn_pnp_ransac')
+        if host:
+            return poses.cpu().numpy(), info.cpu().numpy()
+        return poses, info
+
+    def hypotheses_probe(self, records, t0=0):
+        """kfn_pnp_hypotheses: (samples [B,H,4], hypothesis poses [B,H,12] = [R | t] world-to-camera, counts [B,H]) as
+        numpy arrays -- the sampled and scored hypotheses before selection."""
+        import torch
+        lib = _lib.load()
+        rec, _ = self._device_records(records)
+        B, H = rec.shape[0], self.hypotheses
+        d = self.desc(B, t0, rec.shape[3])
+        samples = torch.empty((B, H, 4), dtype=torch.int32, device=rec.device)
+        hp = torch.empty((B, H, 12), dtype=torch.float32, device=rec.device)
+        counts = torch.empty((B, H), dtype=torch.int32, device=rec.device)
+        _lib.check(lib.kfn_pnp_hypotheses(C.byref(d), rec.data_ptr(), samples.data_ptr(), hp.data_ptr(), counts.data_ptr(),
+                                          torch.cuda.current_stream(rec.device).cuda_stream), 'kfn_pnp_hypotheses')
+        return samples.cpu().numpy(), hp.cpu().numpy(), counts.cpu().numpy()
+
+
+def read_pose(path):
+    """A 7-Scenes `frame-*.pose.txt`: 4x4 camera-to-world, whitespace separated."""
+    T = np.loadtxt(path, dtype=np.float64)
+    if T.shape != (4, 4):
+        raise ValueError('%s: expected a 4x4 pose, got %s' % (path, T.shape))
+    return T
+
+
+def write_pose(path, T):
+    T = np.asarray(T, dtype=np.float64).reshape(4, 4)
+    with open(path, 'w') as f:
+        for row in T:
+            f.write('\t'.join('%.9e' % x for x in row) + '\t\n')
+
+
+def pose_errors(est, gt):
+    """(rotation error in degrees, camera-centre distance in metres) of camera-to-world poses [..,4,4]; NaN poses give
+    NaN.  Rotation: the angle of M = R_est^T R_gt, i.e. arccos((tr(M) - 1) / 2), evaluated as atan2(|sin|, cos) with
+    sin from the skew part of M -- the same angle, but resolved near 0, where the arccos of a cosine computed from fp32
+    poses cannot tell 0.01 degrees from 0."""
+    est = np.asarray(est, dtype=np.float64)
+    gt = np.asarray(gt, dtype=np.float64)
+    M = np.einsum('...ji,...jk->...ik', est[..., :3, :3], gt[..., :3, :3])
+    cos = (np.trace(M, axis1=-2, axis2=-1) - 1.0) / 2.0
+    sk = np.stack([M[..., 2, 1] - M[..., 1, 2], M[..., 0, 2] - M[..., 2, 0], M[..., 1, 0] - M[..., 0, 1]], axis=-1)
+    sin = np.linalg.norm(sk, axis=-1) / 2.0
+    rot = np.degrees(np.arctan2(sin, cos))
+    trans = np.linalg.norm(est[..., :3, 3] - gt[..., :3, 3], axis=-1)
+    return rot, trans
+
+
+def solve_in_batches(solver, records, batch=64, t0=0):
+    """records [T,h,w,4] (numpy) -> (poses [T,4,4], info [T,4]); frame k is solved as global frame t0 + k."""
+    T = records.shape[0]
+    poses = np.full((T, 4, 4), np.nan, np.float32)
+    info = np.zeros((T, 4), np.int32)
+    for lo in range(0, T, batch):
+        p, i = solver.solve(records[lo:lo + batch], t0=t0 + lo)
+        poses[lo:lo + batch], info[lo:lo + batch] = p, i
+    return poses, info
+
+
+def summarize(rot, trans):
+    """Median rotation (deg) and translation (m) errors and the share of frames within 5 cm / 5 degrees (a failed frame
+    counts as outside)."""
+    ok = np.isfinite(rot) & np.isfinite(trans)
+    within = float(np.mean(ok & (np.nan_to_num(rot, nan=np.inf) < 5.0) & (np.nan_to_num(trans, nan=np.inf) < 0.05)))
+    rot_f = np.where(ok, rot, np.inf)
+    trans_f = np.where(ok, trans, np.inf)
+    return float(np.median(rot_f)), float(np.median(trans_f)), within
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('coord_file_list', help='text file: one coord_<i>.npy path per line')
+    ap.add_argument('output_folder', help='pose_<i>.txt files are written here')
+    ap.add_argument('--gt', default='', help='text file: one ground-truth frame-*.pose.txt path per line')
+    ap.add_argument('--thread_num', type=int, default=8, help='threads that read the coordinate files')
+    ap.add_argument('--focal_x', type=float, default=525.)
+    ap.add_argument('--focal_y', type=float, default=525.)
+    ap.add_argument('--u', type=float, default=320.)
+    ap.add_argument('--v', type=float, default=240.)
+    ap.add_argument('--hypotheses', type=int, default=256)
+    ap.add_argument('--batch', type=int, default=64, help='frames per kfn_pnp_ransac launch')
+    ap.add_argument('--refine_iters', type=int, default=10)
+    ap.add_argument('--inlier_px', type=float, default=10.)
+    ap.add_argument('--min_confidence', type=float, default=20.)
+    ap.add_argument('--seed', type=int, default=0)
+    a = ap.parse_args(argv)
+    paths = read_lines(a.coord_file_list)
+    paths = [p for p in paths if p]
+    if not paths:
+        print('no coordinate files listed in', a.coord_file_list)
+        return 1
+    gt_paths = None
+    if a.gt:
+        gt_paths = [p for p in read_lines(a.gt) if p]
+        if len(gt_paths) != len(paths):
+            print('--gt lists %d poses for %d coordinate files' % (len(gt_paths), len(paths)))
+            return 1
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, a.thread_num)) as ex:
+        records = list(ex.map(lambda p: np.load(p).astype(np.float32, copy=False), paths))
+    h, w = records[0].shape[:2]
+    for p, r in zip(paths, records):
+        if r.shape != (h, w, 4):
+            print('%s: expected a [%d,%d,4] map, got %s' % (p, h, w, r.shape))
+            return 1
+    solver = PnPSolver(h, w, a.focal_x, a.focal_y, a.u, a.v, hypotheses=a.hypotheses, refine_iters=a.refine_iters,
+                       seed=a.seed, min_confidence=a.min_confidence, inlier_px=a.inlier_px)
+    poses, info = solve_in_batches(solver, np.stack(records), max(1, a.batch))
+    os.makedirs(a.output_folder, exist_ok=True)
+    for i in range(len(paths)):
+        write_pose(os.path.join(a.output_folder, 'pose_%d.txt' % i), poses[i])
+    failed = int((info[:, 0] != _lib.PNP_OK).sum())
+    print('%d poses written to %s (%d frames without a pose)' % (len(paths), a.output_folder, failed))
+    if gt_paths is not None:
+        gt = np.stack([read_pose(p) for p in gt_paths])
+        rot, trans = pose_errors(poses, gt)
+        for i in range(len(paths)):
+            print('frame %d: %s, %d inliers of %d, rotation error %.4f deg, translation error %.4f m'
+                  % (i, STATUS_NAMES.get(int(info[i, 0]), '?'), info[i, 2], info[i, 1], rot[i], trans[i]))
+        mr, mt, within = summarize(rot, trans)
+        print('median rotation error: %.4f deg, median translation error: %.4f m, within 5cm/5deg: %.1f %%'
+              % (mr, mt, 100.0 * within))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

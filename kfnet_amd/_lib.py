@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libkfnet_hip.so')
 
 KFN_OK = 0
-ABI_VERSION = 10
+ABI_VERSION = 11
 COMM_ID_BYTES = 128
 EPI_NONE, EPI_L2NORM, EPI_EXP_CH3, EPI_EXP_1E2 = 0, 1, 2, 3
 OPERAND_F32, OPERAND_F16, OPERAND_F16X3 = 0, 1, 2
@@ -23,6 +23,8 @@ CFG_256x64, CFG_256x256, CFG_256x256_W8 = 12, 13, 14
 WINO_FORM_F43_FOUR_WAVE, WINO_FORM_F43_EIGHT_WAVE = 2, 3   # kfn_conv_desc.wino_form for kfn_conv2d_winograd_f43
 WINO_FORM_S2_EIGHT_WAVE = 4                                # ... for kfn_conv2d_winograd_s2
 WINO_FORM_S2_F42 = 5                                       # ... its polyphase + F(4,2) form (wino_s2c_kernel)
+PNP_OK, PNP_TOO_FEW_POINTS, PNP_NO_HYPOTHESIS = 0, 1, 2      # kfn_pnp_ransac info[:, 0] (KFN_PNP_*)
+PNP_MAX_HYPOTHESES = 1024
 CFG_AUTO, CFG_160x128, CFG_128x128, CFG_128x64, CFG_128x32, CFG_64x64, CFG_256x32, CFG_192x64 = 0, 1, 2, 3, 4, 5, 6, 7
 
 
@@ -50,6 +52,19 @@ class KalmanDesc(C.Structure):
                 ('t0', C.c_int32), ('reset_period', C.c_int32),
                 ('min_uncertainty', C.c_float), ('nis_gate', C.c_float),
                 ('has_transform', C.c_int32), ('transform', C.c_float * 12)]
+
+
+class PnPDesc(C.Structure):
+    """kfn_pnp_desc (include/kfnet_hip.h, ABI 11); `struct_size` is filled in here, as for ConvDesc."""
+    _fields_ = [('struct_size', C.c_int32), ('B', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('ld', C.c_int32),
+                ('t0', C.c_int32), ('seed', C.c_uint32), ('hypotheses', C.c_int32), ('refine_iters', C.c_int32),
+                ('min_points', C.c_int32), ('fx', C.c_float), ('fy', C.c_float), ('u', C.c_float), ('v', C.c_float),
+                ('cell_stride', C.c_int32), ('min_confidence', C.c_float), ('inlier_px', C.c_float)]
+
+    def __init__(self, *args, **kw):
+        super(PnPDesc, self).__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(PnPDesc)
 
 
 # name -> (restype, argtypes); every symbol declared in include/kfnet_hip.h
@@ -115,6 +130,9 @@ SYMBOLS = {
     'kfn_pixel_map': (_i, [_vp, _i, _i, _i, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
     'kfn_bilinear_sampler': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
     'kfn_decode_png_rgb8': (_i, [C.POINTER(C.c_char_p), _i, _i, _i, _vp, C.POINTER(_i), _i]),
+    'kfn_pnp_scratch_bytes': (_i, [C.POINTER(PnPDesc), C.POINTER(_sz)]),
+    'kfn_pnp_ransac': (_i, [C.POINTER(PnPDesc), _vp, _vp, _vp, _vp, _vp]),
+    'kfn_pnp_hypotheses': (_i, [C.POINTER(PnPDesc), _vp, _vp, _vp, _vp, _vp]),
     'kfn_comm_available': (_i, []),
     'kfn_comm_unique_id': (_i, [_vp, _sz]),
     'kfn_comm_init': (_i, [C.POINTER(_vp), _i, _i, _vp, _i]),
