@@ -21,22 +21,18 @@
 #include <type_traits>
 #include <cstdlib>
 
+namespace {
+
 // fp16-activation kernels: pin the issue order of the main loop (one sched_barrier per MFMA slot).  Without it hipcc
 // re-clusters the stage -- 8 MFMAs, then ALL fragment reads of the next chunk in one burst with the LDS stores and
 // global loads behind them, then a wait for those reads in front of the next MFMA -- which exposes one LDS round trip
-// per chunk (tools/mb/build_hot.sh builds the A/B library with -DKFN_F16_PIN=0).
-#ifndef KFN_F16_PIN
-#define KFN_F16_PIN 1
-#endif
-// position of the stage barrier inside the last k-chunk of a stage: after J / KFN_F16_BAR_DIV of its J MFMAs (fp16-activation
+// per chunk.
+constexpr bool F16_PIN = true;
+// position of the stage barrier inside the last k-chunk of a stage: after J / F16_BAR_DIV of its J MFMAs (fp16-activation
 // kernels; everything else keeps J / 2).  The fragment reads of the next stage follow the barrier and are covered by the rest.
 // Same-box A/B on the eight-wave 256x256 tile (profiles/r04_c5_layer_microbench.log, conv2b / 3b / 4b / 5, TFLOP/s):
 // J/2 with both operands on LDS-DMA 1090 / 1153 / 1188 / 1201, J/4: 1123 / 1180 / 1197 / 1215.
-#ifndef KFN_F16_BAR_DIV
-#define KFN_F16_BAR_DIV 4
-#endif
-
-namespace {
+constexpr int F16_BAR_DIV = 4;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -162,8 +158,8 @@ constexpr int PREC_F32_N16 = 3;
 //   _XY both.  k-step 16 or 32 (= 32 / 64 channels per stage).
 constexpr int PREC_F16_X = 4, PREC_F16_Y = 5, PREC_F16_XY = 6;
 // PREC_F16_XY_BDMA: as _XY, with the WEIGHT tile going global -> LDS directly (`buffer_load_dwordx4 ... lds`): no
-// staging registers and no ds_write_b128 for two thirds of the operand bytes (timing builds without LDS stores run
-// 25-30 % faster: tools/mb/build_hot.sh).  A lane's 16 bytes land at wave base + lane*16, so the XOR swizzle of the
+// staging registers and no ds_write_b128 for two thirds of the operand bytes (timing builds without LDS stores ran
+// 25-30 % faster).  A lane's 16 bytes land at wave base + lane*16, so the XOR swizzle of the
 // LDS rows moves to the SOURCE address (lane (row, slot q) fetches logical quad q ^ sw(row)); three B buffers: the
 // transfer for stage s+2 is issued in stage s, behind the LDS stores of A -- loads return in order, so the wait the
 // compiler places in front of the next stage's A stores also covers it, one stage before its barrier.
@@ -497,9 +493,6 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN > 8 ? 1 : 2)) void conv_mfma
   // Issue the global loads of the stage the iterator points at (all-OOB = zeros once the
   // iterator has run off the end: keeps the loop body branch-free).
   auto load_one = [&](int k, bool live, unsigned adelta, unsigned bdelta, int ky, int kx, int tap) {
-#if defined(KFN_CONV_HOT) && (KFN_CONV_HOT & 8)   // timing experiment only: no global loads in the main loop
-    if (TAP_INNER && ld_ci > 0) return;
-#endif
     if (WINO && k < AP * NSRC) {
       // per-lane: the source pixel's offset (or OOB for zero padding); uniform: channel offset; a stream
       // that has run off the end reads through a descriptor with num_records = 0 (scalar select)
@@ -513,11 +506,7 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN > 8 ? 1 : 2)) void conv_mfma
         ga[k] = buf_load_s(rsA, a_ok2[CVOL ? i : 0] ? a_off[i] : OOB, adelta);
       }
     } else if (X16 && k < AP * NSRC) {   // fp16 activations: the quad's 8 channels are one 16-byte load
-#if defined(KFN_CONV_HOT) && (KFN_CONV_HOT & 1)   // timing experiment only (tools/mb/build_hot.sh): every A load hits a 64 KiB window
-      ga[k] = buf_load_s(rsA, a_shift + (a_off[k] & 0xFFF0u), 0u);   // inside the tensor: the descriptor is based a_shift below it
-#else
       ga[k] = buf_load_s(rsA, a_ok[k] ? a_off[k] : OOB, adelta);
-#endif
     } else if (F16 && k < AP * NSRC) {   // two consecutive float4 = the 8 channels of one fp16 quad
       const int i = k / NSRC;
       if (TRANSPOSED) {
@@ -546,11 +535,7 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN > 8 ? 1 : 2)) void conv_mfma
       // f16x3: the packed weights are [hi | lo], lo starts w_lo_bytes after hi
       const unsigned part_off = (X3 && (kk % NPART)) ? p.w_lo_bytes : 0u;
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(b_ptr, 0, live ? (int)p.w_bytes : 0, 0x00020000);
-#if defined(KFN_CONV_HOT) && (KFN_CONV_HOT & 2)   // timing experiment only: every B load re-reads the first K chunk
-      gb[kk] = buf_load_s(rs, b_off[i], part_off);
-#else
       gb[kk] = buf_load_s(rs, b_off[i], (F16 ? bdelta >> 1 : bdelta) + part_off);
-#endif
     }
   };
 
@@ -558,9 +543,6 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN > 8 ? 1 : 2)) void conv_mfma
   // because RPP is a multiple of 16 rows.
   const int wr_off = r0 * BK + ((q ^ swz<BK>(r0)) * 4);
   auto store_one = [&](int k, int buf) {
-#if defined(KFN_CONV_HOT) && (KFN_CONV_HOT & 4)   // timing experiment only: no LDS stores in the main loop (stale operands)
-    if (TAP_INNER && n_stages > 2 && buf >= 0) return;
-#endif
     if (k < AP) {
       const int i = k;
       f32x4 v;
@@ -735,7 +717,7 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN > 8 ? 1 : 2)) void conv_mfma
         constexpr int n_dma = (c == 0 && !ADMA) ? NDMA : 0;     // behind the A stores of the same chunk (see PREC_F16_XY_BDMA)
         constexpr int n_ld = (c == LOADC) ? NLD : 0;
         constexpr int n_side = n_rd + n_st + n_dma + n_ld;
-        constexpr int JB = (TAP_INNER ? J / KFN_F16_BAR_DIV : J / 2) > 0 ? (TAP_INNER ? J / KFN_F16_BAR_DIV : J / 2) : 1;   // MFMAs of the last chunk in front of the barrier
+        constexpr int JB = (TAP_INNER ? J / F16_BAR_DIV : J / 2) > 0 ? (TAP_INNER ? J / F16_BAR_DIV : J / 2) : 1;   // MFMAs of the last chunk in front of the barrier
         constexpr int jspan = last ? JB : J;  // in the last chunk side ops ride in front of the barrier
         static_for<J>([&](auto jc) {
           constexpr int j = decltype(jc)::value;
@@ -775,7 +757,7 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN > 8 ? 1 : 2)) void conv_mfma
             else if constexpr (k < n_rd + n_st + n_dma) dma_one(k - n_rd - n_st, live, bdelta, bcur == 0 ? 2 : bcur - 1);
             else load_one(k - n_rd - n_st - n_dma, live, adelta, bdelta, ky, kx, tp);
           });
-          if constexpr (KFN_F16_PIN != 0 && TAP_INNER) __builtin_amdgcn_sched_barrier(0);
+          if constexpr (F16_PIN && TAP_INNER) __builtin_amdgcn_sched_barrier(0);
         });
       });
       advance();
@@ -942,7 +924,7 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN > 8 ? 1 : 2)) void conv_mfma
       const int n = n0 + ch * 8;
       // rows past M fail the range check; chunks past Cout (a partial last column tile) are dropped here
       const unsigned voff = (n < p.Cout) ? (unsigned)row * row_b16 + (unsigned)n * 2u : OOB;
-      __builtin_amdgcn_raw_buffer_store_b128(v, rsY16, voff, 0, KFN_NT_STORE_AUX);
+      __builtin_amdgcn_raw_buffer_store_b128(v, rsY16, voff, 0, 0);
     }
     return;
   }

@@ -25,11 +25,6 @@
 // touched again by this launch; the [h,w,4] state never leaves LDS).
 #include "kfn_common.h"
 
-// 1 = the scan kernel's buffer descriptors are forced into SGPRs (v_readfirstlane), 0 = as hipcc makes them (waterfall loops)
-#ifndef KFN_SCAN_UNIFORM_SRD
-#define KFN_SCAN_UNIFORM_SRD 1
-#endif
-
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -107,9 +102,6 @@ __device__ __forceinline__ float div_rn_normal(float a, float b) {
   const float q = __builtin_fmaf(f4, f1, f3);
   return __builtin_amdgcn_div_fixupf(q, b, a);
 }
-#ifndef KFN_KALMAN_LEAN
-#define KFN_KALMAN_LEAN 1
-#endif
 template <bool LEAN>
 __device__ __forceinline__ float k_sqrt(float x) {
   if constexpr (LEAN) return sqrt_rn_normal(x);
@@ -121,7 +113,7 @@ __device__ __forceinline__ float k_div(float a, float b) {
   else return a / b;
 }
 
-template <bool NT = false, bool DBG = true, bool LEAN = (KFN_KALMAN_LEAN != 0)>
+template <bool NT = false, bool DBG = true, bool LEAN = true>
 __device__ __forceinline__ f32x4 fuse_pixel(const KalmanArgs& a_in, const f32x4* st, const PixIn& in, int p, int x, int y,
                                             size_t off, bool reset, int W, float xmax, float ymax,
                                             float eps2, bool want_nis, bool valid = true, f32x4* rec_out = nullptr) {
@@ -237,7 +229,7 @@ __device__ __forceinline__ f32x4 fuse_pixel(const KalmanArgs& a_in, const f32x4*
 // so the production 60x80 form stays as measured in the profiles.  false = buffer descriptors with scalar frame / slot
 // offsets (below): no per-slot registers, which is what lets the single-buffer forms of the larger grids run without spills
 // (68x120, S = 256: 0.720 against 0.43 for rounds 1-4's form).
-template <int KT, int PPT, bool DBL, int D, bool NT, bool DBG, bool PTR = false, bool LEAN = (KFN_KALMAN_LEAN != 0)>
+template <int KT, int PPT, bool DBL, int D, bool NT, bool DBG, bool PTR = false, bool LEAN = true>
 __global__ __launch_bounds__(KT) void kalman_scan_kernel(KalmanArgs a) {
   static_assert(D >= 1 && D <= PPT && PPT % D == 0, "ring slots are compile-time constants");
   extern __shared__ __attribute__((aligned(16))) float smem_k[];
@@ -271,16 +263,12 @@ __global__ __launch_bounds__(KT) void kalman_scan_kernel(KalmanArgs a) {
   //  60x80 descriptor form 0.613 -> 0.661 (profiles/r05_kalman_srd_ab.log).  The first build of this returned WRONG records
   //  in the single-buffer forms: that was the 16-byte-store hazard of kfn_common.h buffer_store_b128 -- without the
   //  waterfall loop nothing separated the record store from the next write of its data registers -- and with the padded
-  //  store every form is bit-identical to rounds 1-4's kernel again.  KFN_SCAN_UNIFORM_SRD=0 builds the waterfall form.)
-#if KFN_SCAN_UNIFORM_SRD
+  //  store every form is bit-identical to rounds 1-4's kernel again.)
   auto uniform = [](auto* q) {       // the pointer's two halves through v_readfirstlane: the descriptor is built in SGPRs
     const uintptr_t v = reinterpret_cast<uintptr_t>(q);
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
     return reinterpret_cast<decltype(q)>((uintptr_t)lo | ((uintptr_t)hi << 32));
   };
-#else
-  auto uniform = [](auto* q) { return q; };
-#endif
   const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc(uniform(const_cast<f32x2*>(a.flow + seq_px)), 0, T * HW * 8, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc(uniform(const_cast<float*>(a.sigma_t + seq_px)), 0, T * HW * 4, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsM = __builtin_amdgcn_make_buffer_rsrc(uniform(const_cast<f32x4*>(a.meas + seq_px)), 0, T * HW * 16, 0x00020000);
@@ -464,31 +452,18 @@ __global__ __launch_bounds__(256) void kalman_fuse2_kernel(const f32x4* __restri
   }
 }
 
-// The form launched for grids whose two state copies fit the LDS (up to 5 120 pixels: 60x80 and below).  Build-time
-// switches of the A/B builds (tools/mb/kalman_mb.hip instantiates every combination in one binary).
-#ifndef KFN_SCAN_KT
-#define KFN_SCAN_KT 1024
-#define KFN_SCAN_PPT 5
-#endif
-#ifndef KFN_SCAN_DEPTH
-#define KFN_SCAN_DEPTH KFN_SCAN_PPT
-#endif
-#ifndef KFN_SCAN_BIG_DEPTH
-#define KFN_SCAN_BIG_DEPTH 2
-#endif
-#ifndef KFN_SCAN_NT
-#define KFN_SCAN_NT 1
-#endif
+// The form launched for grids whose two state copies fit the LDS (up to 5 120 pixels: 60x80 and below).  The alternatives
+// are instantiations of the same templates: tools/mb/kalman_mb.hip times them in one binary.
+constexpr int SCAN_KT = 1024, SCAN_PPT = 5, SCAN_DEPTH = SCAN_PPT;
+constexpr int SCAN_BIG_DEPTH = 2;   // input-ring depth of the 1024 x 8 single-buffer form
+constexpr bool SCAN_NT = true;      // non-temporal record stores and input loads
 // fuse kernel: 256 threads x 4 pixels, non-temporal, ONE trip per thread (measured, tools/mb/kalman_mb, P = 78.6 M / 314.6 M
 // pixels: rounds 1-4's 256 x 1 grid-stride form 0.623 / 0.622 of 8 TB/s; 256 x 4 nt capped at 4096 blocks 0.773 / 0.703;
 // 512 x 4 nt 0.738 / 0.680; 256 x 4 nt one trip 0.786 / 0.750)
-#ifndef KFN_FUSE_BLOCK
-#define KFN_FUSE_BLOCK 256
-#define KFN_FUSE_U 4
-#define KFN_FUSE_NT 1
-#endif
+constexpr int FUSE_BLOCK = 256, FUSE_U = 4;
+constexpr bool FUSE_NT = true;
 
-template <int KT, int PPT, bool DBL, int D, bool NT, bool DBG, bool PTR = false, bool LEAN = (KFN_KALMAN_LEAN != 0)>
+template <int KT, int PPT, bool DBL, int D, bool NT, bool DBG, bool PTR = false, bool LEAN = true>
 int launch_scan_dbg(const KalmanArgs& a, hipStream_t stream) {
   const size_t smem = (size_t)a.d.H * a.d.W * sizeof(f32x4) * (DBL ? 2 : 1);
   auto kern = kalman_scan_kernel<KT, PPT, DBL, D, NT, DBG, PTR, LEAN>;
@@ -587,15 +562,15 @@ extern "C" int kfn_kalman_scan_ex(const kfn_kalman_desc* d, const float* flow_xy
   // 768 threads (12 wavefronts, 170-VGPR budget) x 7 pixels cover the 60x80 grid without
   // register spills; larger grids fall back to 1024 threads and the single-buffer form.
   const bool dbl = (size_t)HW * 32 <= 160 * 1024;  // two LDS copies of the state fit
-  constexpr bool NT = KFN_SCAN_NT != 0;
-  if (dbl && HW <= KFN_SCAN_KT * KFN_SCAN_PPT)
-    return launch_scan<KFN_SCAN_KT, KFN_SCAN_PPT, true, KFN_SCAN_DEPTH, NT, 768, 7, 1>(a, s);
+  constexpr bool NT = SCAN_NT;
+  if (dbl && HW <= SCAN_KT * SCAN_PPT)
+    return launch_scan<SCAN_KT, SCAN_PPT, true, SCAN_DEPTH, NT, 768, 7, 1>(a, s);
   // single LDS copy (config 5's 68x120 = 8160-pixel grid takes the second line): the new states of a frame wait in
   // registers for the mid-frame barrier -- 1024 threads keep that to PPT <= 10 float4 per thread beside a two-deep input
   // ring.  Measured (tools/mb/kalman_mb, 68x120, S = 256 x T = 32 / S = 4 x T = 64): rounds 1-4's 512 x 16 with the loads at
   // the frame start 0.867 / 1.011 ms; 1024 x 8 with D = 2 0.793 / 0.914; D = 4 0.796 / 0.968; 768 x 11 D = 1 0.787 / 1.064.
   if (HW <= 1024 * 6) return launch_scan<1024, 6, false, 2, NT, 512, 12, 1>(a, s);
-  if (HW <= 1024 * 8) return launch_scan<1024, 8, false, KFN_SCAN_BIG_DEPTH, NT, 512, 16, 1>(a, s);
+  if (HW <= 1024 * 8) return launch_scan<1024, 8, false, SCAN_BIG_DEPTH, NT, 512, 16, 1>(a, s);
   return launch_scan<1024, 10, false, 1, NT, 512, 20, 1>(a, s);
 }
 
@@ -610,10 +585,10 @@ extern "C" int kfn_kalman_fuse(const float* pred, const float* meas, float* out,
   KFN_REQUIRE(pred && meas && out && P > 0, "kfn_kalman_fuse: bad argument");
   KFN_REQUIRE(((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(meas) |
                 reinterpret_cast<uintptr_t>(out)) & 15) == 0, "kfn_kalman_fuse: misaligned buffer");
-  constexpr int PER = KFN_FUSE_BLOCK * KFN_FUSE_U;
+  constexpr int PER = FUSE_BLOCK * FUSE_U;
   const long blocks = (P + PER - 1) / PER;      // one trip per thread (the kernel's loop runs once)
   KFN_REQUIRE(blocks < (1L << 31), "kfn_kalman_fuse: P=%ld too large for one launch", P);
-  hipLaunchKernelGGL((kalman_fuse_kernel<KFN_FUSE_BLOCK, KFN_FUSE_U, KFN_FUSE_NT != 0>), dim3((unsigned)blocks), dim3(KFN_FUSE_BLOCK), 0,
+  hipLaunchKernelGGL((kalman_fuse_kernel<FUSE_BLOCK, FUSE_U, FUSE_NT>), dim3((unsigned)blocks), dim3(FUSE_BLOCK), 0,
                      (hipStream_t)stream, reinterpret_cast<const f32x4*>(pred), reinterpret_cast<const f32x4*>(meas),
                      reinterpret_cast<f32x4*>(out), opt_nis, P);
   KFN_LAUNCH_CHECK("kalman_fuse_kernel");

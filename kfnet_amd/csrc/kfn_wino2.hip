@@ -26,9 +26,6 @@
 // 8 positions ahead and half a stage of staging loads + LDS writes (for the stage after next) are
 // slotted behind the MFMAs of the current chunk.
 #include "kfn_common.h"
-#ifndef KFN_WINO2_DBG
-#define KFN_WINO2_DBG 0
-#endif
 #include <type_traits>
 #include <cstdlib>
 
@@ -74,7 +71,6 @@ struct Wino2Args {
   int tiles_m, tiles_n;
   int relu;
   int wide_store;     // Cout, ldy multiples of 4 and y 16-byte aligned: LDS-transposed 16-byte stores
-  int dbg;            // timing experiments only (KFN_WINO2_DBG): 1 = every A row read from row 0, 2 = every B fragment = fragment 0
   unsigned long long x_bytes;
   unsigned long long y_bytes;
   unsigned u_bytes;
@@ -251,7 +247,7 @@ __global__ __launch_bounds__(64, 1) void wino2_kernel(Wino2Args p) {
     const int sc = s < n_stages ? s : n_stages - 1;
     if constexpr (k < NMAIN) {
       const bool ok = (rowmask >> k) & 1u;
-      const int soff = (p.dbg & 1) ? sc * (KS * 4) : (k < first_rows ? base_first : base_second) + k * row_stride + sc * (KS * 4);
+      const int soff = (k < first_rows ? base_first : base_second) + k * row_stride + sc * (KS * 4);
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a_ptr, 0, ok ? a_records : 0, 0x00020000);
       ra[k % NHALF] = bload(rs, voff_main, ok ? (unsigned)soff : 0u);
     } else {
@@ -274,7 +270,7 @@ __global__ __launch_bounds__(64, 1) void wino2_kernel(Wino2Args p) {
   auto b_load = [&](auto gc, int qidx) __attribute__((always_inline)) {
     constexpr int g = decltype(gc)::value;
     const int qc = qidx < q_last ? qidx : q_last;     // past the end: re-read the last slice (never used)
-    bq[g % NB] = bload(rsU, voff_b, (p.dbg & 2) ? 0u : (unsigned)qc * b_step);
+    bq[g % NB] = bload(rsU, voff_b, (unsigned)qc * b_step);
   };
   // patch read (r, c) of chunk `chunk` from buffer `buf` into v[4*r + c]
   auto v_read = [&](auto ic, f32x2 (&v)[32], auto buf_c, auto chunk_c) __attribute__((always_inline)) {
@@ -436,7 +432,7 @@ __global__ __launch_bounds__(64, 1) void wino2_kernel(Wino2Args p) {
       const int oy = 2 * ty + a;
       const bool row_in = vr0 + trow < p.vrows && oy < p.H;        // uniform
       const unsigned soff = (unsigned)(((img_rel * p.H + oy) * p.W + ox0 + 8 * hx) * pix_bytes);
-      kfn::buffer_store_b128<KFN_NT_STORE_AUX>(v, rsY, row_in ? voff_h[hx] : OOBV, soff);
+      kfn::buffer_store_b128<0>(v, rsY, row_in ? voff_h[hx] : OOBV, soff);
     }
     return;
   } else {
@@ -527,10 +523,6 @@ extern "C" int kfn_conv2d_winograd_fused(const kfn_conv_desc* d, const float* x,
   a.tiles_m = (int)tiles_m;
   a.relu = d->relu;
   a.wide_store = (d->Cout % 4 == 0 && d->ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) ? 1 : 0;
-#ifdef KFN_WINO2_NO_WIDE   // A/B builds only (tools/mb/build_hot.sh): the dword-store epilogue on aligned outputs too
-  a.wide_store = 0;
-#endif
-  a.dbg = KFN_WINO2_DBG;   // build-time timing hooks (-DKFN_WINO2_DBG=1: hot A, 2: hot B); 0 in the product build
   a.x_bytes = (unsigned long long)x_bytes;
   a.y_bytes = (unsigned long long)(((in_pix - 1) * d->ldy + d->Cout) * 4L);
   a.u_bytes = (unsigned)u_bytes;

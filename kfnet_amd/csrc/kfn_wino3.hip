@@ -24,11 +24,9 @@
 #include <type_traits>
 #include <cstdlib>
 
-#ifndef KFN_WINO_DEFAULT_N_FAST
-#define KFN_WINO_DEFAULT_N_FAST 0   // measured (kfn_conv_desc.wino_order M_FAST / N_FAST): 2.9 vs 4.8 GB fetched per launch, conv4b 4.59 vs 4.72 ms
-#endif
-
 namespace {
+
+constexpr int W3_DEFAULT_N_FAST = 0;   // measured (kfn_conv_desc.wino_order M_FAST / N_FAST): 2.9 vs 4.8 GB fetched per launch, conv4b 4.59 vs 4.72 ms
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -54,19 +52,13 @@ template <bool H16> struct VLayout {
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 constexpr int NBR = 16;                 // B ring = one chunk of positions ahead
 constexpr int NVR = 8;                  // V fragment ring (positions ahead inside a super-step)
-// producer schedule inside a super-step of 256 MFMA slots (tools/mb/wino3_prof.hip sweeps these)
-#ifndef KFN_W3_GSTEP
-#define KFN_W3_GSTEP 8      // one raw-patch gather every GSTEP slots, from slot 0
-#define KFN_W3_XSLOT 175    // the transform burst
-#define KFN_W3_SSLOT 192    // first V store
-#define KFN_W3_SSTEP 2      // one V store every SSTEP slots
-#endif
-#ifndef KFN_W3P_GSTEP       // the two-wave form: 128 slots per super-step
-#define KFN_W3P_GSTEP 4
-#define KFN_W3P_XSLOT 96
-#define KFN_W3P_SSLOT 104
-#define KFN_W3P_SSTEP 1
-#endif
+// producer schedule inside a super-step of 256 MFMA slots
+constexpr int W3_GSTEP = 8;      // one raw-patch gather every GSTEP slots, from slot 0
+constexpr int W3_XSLOT = 175;    // the transform burst
+constexpr int W3_SSLOT = 192;    // first V store
+constexpr int W3_SSTEP = 2;      // one V store every SSTEP slots
+// the two-wave form: 128 slots per super-step
+constexpr int W3P_GSTEP = 4, W3P_XSLOT = 96, W3P_SSLOT = 104, W3P_SSTEP = 1;
 
 struct Wino3Args {
   const float* x;
@@ -85,19 +77,7 @@ struct Wino3Args {
   unsigned long long x_bytes;
   unsigned long long y_bytes;
   unsigned u_bytes;
-#ifdef KFN_WINO3_PROF
-  unsigned long long* prof;   // tools/mb/wino3_prof.hip: [block][wave][8] cycle stamps
-#endif
 };
-
-#ifdef KFN_WINO3_PROF
-// Every lane stores the same counter value to the same address: an `if (lane == 0)` here is divergent control flow,
-// after which hipcc no longer trusts the gather descriptors to be uniform and wraps each buffer_load in a
-// waterfall loop (4 v_readfirstlane + compare + branch) -- +12 % on the main loop, in the profiled build only.
-#define KFN_STAMP(i) (p.prof[((size_t)blockIdx.x * NW + wave) * 8 + (i)] = __builtin_readcyclecounter())
-#else
-#define KFN_STAMP(i) do { } while (0)
-#endif
 
 template <int I, int N, class F>
 __device__ __forceinline__ void sfor_impl(F& f) {
@@ -172,11 +152,6 @@ __device__ __forceinline__ void wino3_body(const Wino3Args& p) {
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform: keep it in an SGPR
-  KFN_STAMP(0);
-#ifdef KFN_WINO3_PROF
-  p.prof[((size_t)blockIdx.x * NW + wave) * 8 + 6] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_ID
-  p.prof[((size_t)blockIdx.x * NW + wave) * 8 + 7] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));  // XCC_ID
-#endif
   const int nwg = p.tiles_m * p.tiles_n;
   const int tile = xcd_remap3(blockIdx.x, nwg);
   // Workgroups that run side by side on an XCD share its L2.  n_fast: the Cout/128 channel groups of one tile
@@ -324,7 +299,6 @@ __device__ __forceinline__ void wino3_body(const Wino3Args& p) {
     vq[g % NVR] = *reinterpret_cast<const frag_t*>(smem3 + (ch & (NVBUF - 1)) * VBUF + g * VPOS + v_lane);
   };
 
-  KFN_STAMP(1);
   // ---- prologue: every wave produces its tile row of super-step 0 -------------------------------
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
@@ -337,23 +311,16 @@ __device__ __forceinline__ void wino3_body(const Wino3Args& p) {
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 
-  KFN_STAMP(2);
   // One super-step: the MFMAs of chunks c0 .. c0+3 (slot j = 4 interleaved positions x 4 k-steps), and as a
   // producer: gather chunk c0+4+wave behind the first MFMAs of chunk c0, transform it as ONE burst in the
   // middle of chunk c0+2, store it behind the MFMAs of chunk c0+3; then the barrier.
-#ifdef KFN_W3_TL
-#ifndef KFN_W3_TL_KS
-#define KFN_W3_TL_KS (-1)   // the super-step whose timeline is kept (-1: the last one)
-#endif
-  unsigned long long tl[17];
-#endif
   // MFMA slots per chunk and the producer's schedule inside the 4-chunk super-step.  fp32: gather super-step ks+1
   // early, transform late, store.  fp16: transform + store super-step ks+1 (gathered during ks-1) first, then gather
   // ks+2 into the buffer that just became free.
   constexpr int SPC = H16 ? 16 : 64;
-  constexpr int GSLOT = H16 ? 32 : 0, GSTEP = H16 ? 2 : (NW == 4 ? KFN_W3_GSTEP : KFN_W3P_GSTEP);
-  constexpr int XSLOT = H16 ? 8 : (NW == 4 ? KFN_W3_XSLOT : KFN_W3P_XSLOT);
-  constexpr int SSLOT = H16 ? 12 : (NW == 4 ? KFN_W3_SSLOT : KFN_W3P_SSLOT), SSTEP = H16 ? 1 : (NW == 4 ? KFN_W3_SSTEP : KFN_W3P_SSTEP);
+  constexpr int GSLOT = H16 ? 32 : 0, GSTEP = H16 ? 2 : (NW == 4 ? W3_GSTEP : W3P_GSTEP);
+  constexpr int XSLOT = H16 ? 8 : (NW == 4 ? W3_XSLOT : W3P_XSLOT);
+  constexpr int SSLOT = H16 ? 12 : (NW == 4 ? W3_SSLOT : W3P_SSLOT), SSTEP = H16 ? 1 : (NW == 4 ? W3_SSTEP : W3P_SSTEP);
   static_assert(GSLOT + 16 * GSTEP <= CPS * SPC && SSLOT + 16 * SSTEP <= CPS * SPC && XSLOT < SSLOT, "producer schedule inside the super-step");
   auto super_step = [&](int ks, auto par_) __attribute__((always_inline)) {
     constexpr int par = decltype(par_)::value;        // fp16: ks & 1 = the buffer this super-step gathers into
@@ -373,10 +340,6 @@ __device__ __forceinline__ void wino3_body(const Wino3Args& p) {
         // fp32: 4 interleaved positions x 4 k-steps of 32x32x2; fp16: one 32x32x8 per position
         constexpr int g = H16 ? j : (j >> 4) * 4 + (j & 3), t = H16 ? 3 : (j >> 2) & 3;
         constexpr int sl = (cc * 16 + g) % NB;     // B ring slot of fragment ch*16 + g (c0 is a multiple of 4)
-#ifdef KFN_W3_TL
-        if constexpr (!H16 && (cc * 64 + j) % 16 == 0)
-          if (KFN_W3_TL_KS < 0 || ks == KFN_W3_TL_KS) tl[(cc * 64 + j) / 16] = __builtin_readcyclecounter();
-#endif
         if constexpr (H16)
           acc[g] = __builtin_amdgcn_mfma_f32_32x32x8f16(__builtin_bit_cast(f16x4, vq[g % NVR]), __builtin_bit_cast(f16x4, bq[sl]), acc[g], 0, 0, 0);
         else
@@ -401,9 +364,6 @@ __device__ __forceinline__ void wino3_body(const Wino3Args& p) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-#ifdef KFN_W3_TL
-    if (KFN_W3_TL_KS < 0 || ks == KFN_W3_TL_KS) tl[16] = __builtin_readcyclecounter();
-#endif
   };
   if constexpr (H16) {
     for (int ks = 0; ks < n_super; ks += 2) {   // n_super is even (Cin % 64 == 0): two super-steps per trip, one per buffer
@@ -414,11 +374,6 @@ __device__ __forceinline__ void wino3_body(const Wino3Args& p) {
     for (int ks = 0; ks < n_super; ++ks) super_step(ks, I0{});
   }
 
-#ifdef KFN_W3_TL
-#pragma unroll
-  for (int i = 0; i < 17; ++i) p.prof[((size_t)gridDim.x * NW) * 8 + ((size_t)blockIdx.x * NW + wave) * 17 + i] = tl[i];
-#endif
-  KFN_STAMP(3);
   // ---- epilogue (per wave, as kfn_wino2.hip) -----------------------------------------------------
   const bool relu = p.relu != 0;
   const unsigned long long y_base = (unsigned long long)img0 * p.H * p.W * p.ldy * 4ull;
@@ -458,9 +413,6 @@ __device__ __forceinline__ void wino3_body(const Wino3Args& p) {
     out_transform([&](float v, int trow, int ec, int a, int b) __attribute__((always_inline)) {
       *reinterpret_cast<float*>(stg + st_w + ((2 * trow + a) * 16 + 2 * ec + b) * 128) = v;
     });
-#ifdef KFN_W3_EPI
-    KFN_STAMP(6);
-#endif
     const int oxl = lane >> 3, nq = lane & 7;            // store lane: pixel column oxl (+8), channel quad nq
     const unsigned voff_q = (unsigned)((oxl * p.ldy + n0 + nq * 4) * 4);
     const bool q_ok = n0 + nq * 4 < p.Cout;
@@ -476,7 +428,7 @@ __device__ __forceinline__ void wino3_body(const Wino3Args& p) {
       const int oy = 2 * ty + a;
       const bool row_ok = vr0 + trow < p.vrows && oy < p.H;        // uniform
       const unsigned soff = (unsigned)(((img_rel * p.H + oy) * p.W + ox0 + 8 * hx) * pix_bytes);
-      kfn::buffer_store_b128<KFN_NT_STORE_AUX>(v, rsY, row_ok ? voff_h[hx] : OOBV, soff);
+      kfn::buffer_store_b128<0>(v, rsY, row_ok ? voff_h[hx] : OOBV, soff);
     }
   } else {
     // Cout or the row pitch not a multiple of 4 floats: one dword per store
@@ -491,11 +443,6 @@ __device__ __forceinline__ void wino3_body(const Wino3Args& p) {
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsY, ok ? voff_y : OOBV, soff, 0);
     });
   }
-  KFN_STAMP(4);
-#ifdef KFN_WINO3_PROF
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  KFN_STAMP(5);
-#endif
 }
 
 // the four-wave form (128 output channels per workgroup) and the two-wave form (33 .. 64 output channels in all)
@@ -504,10 +451,6 @@ __global__ __launch_bounds__(256, 1) void wino3_kernel(Wino3Args p) { wino3_body
 __global__ __launch_bounds__(128, 1) void wino3_pair_kernel(Wino3Args p) { wino3_body<false, 2>(p); }
 
 }  // namespace
-
-#ifdef KFN_WINO3_PROF
-unsigned long long* g_wino3_prof = nullptr;
-#endif
 
 namespace kfn {
 
@@ -543,14 +486,11 @@ int launch_wino3(const kfn_conv_desc* d, const float* x, const void* u2_packed, 
   KFN_REQUIRE(tiles_m * a.tiles_n < (1L << 31), "kfn_conv2d_winograd_fused: grid too large");
   a.tiles_m = (int)tiles_m;
   a.relu = d->relu;
-  a.n_fast = d->wino_order == KFN_WINO_ORDER_N_FAST ? 1 : (d->wino_order == KFN_WINO_ORDER_M_FAST ? 0 : KFN_WINO_DEFAULT_N_FAST);
+  a.n_fast = d->wino_order == KFN_WINO_ORDER_N_FAST ? 1 : (d->wino_order == KFN_WINO_ORDER_M_FAST ? 0 : W3_DEFAULT_N_FAST);
   a.wide_store = (d->Cout % 4 == 0 && d->ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) ? 1 : 0;
   a.x_bytes = (unsigned long long)(((in_pix - 1) * d->ldx + d->Cin) * 4L);
   a.y_bytes = (unsigned long long)(((in_pix - 1) * d->ldy + d->Cout) * 4L);
   a.u_bytes = (unsigned)(16L * d->cout_pad * d->Cin * (h16 ? 2L : 4L));
-#ifdef KFN_WINO3_PROF
-  a.prof = g_wino3_prof;
-#endif
   const dim3 grid((unsigned)(a.tiles_m * a.tiles_n));
   if (pair) {
     // per-lane patch offsets carry their out-of-image marks in bits 30 and 31: two images must stay below 1 GiB

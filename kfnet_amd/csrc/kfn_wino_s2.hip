@@ -35,11 +35,9 @@
 #include <type_traits>
 #include <cstdlib>
 
-#ifndef KFN_WINO_DEFAULT_N_FAST
-#define KFN_WINO_DEFAULT_N_FAST 1   // measured (kfn_conv_desc.wino_order M_FAST / N_FAST): 3.8 vs 4.8 GB fetched per launch, same time
-#endif
-
 namespace {
+
+constexpr bool S2_DEFAULT_N_FAST = true;   // measured (kfn_conv_desc.wino_order M_FAST / N_FAST): 3.8 vs 4.8 GB fetched per launch, same time
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -411,7 +409,7 @@ __global__ __launch_bounds__(64 * NWAVE, 1) void wino_s2_kernel(WinoS2Args p) {
       const int oy = 2 * ty + a;
       const bool row_ok = vr0 + trow < p.vrows && oy < p.Ho;        // uniform
       const unsigned soff = (unsigned)(((img_rel * p.Ho + oy) * p.Wo + ox0 + 8 * hx) * pix_bytes);
-      kfn::buffer_store_b128<KFN_NT_STORE_AUX>(v, rsY, row_ok ? voff_h[hx] : OOBV, soff);
+      kfn::buffer_store_b128<0>(v, rsY, row_ok ? voff_h[hx] : OOBV, soff);
     }
   } else {
     // Cout or the row pitch not a multiple of 4 floats: one dword per store
@@ -677,7 +675,7 @@ __global__ __launch_bounds__(512, 1) void wino_s2b_kernel(WinoS2Args p) {
       const int oy = 2 * ty + a;
       const bool row_ok = vr0 + trow < p.vrows && oy < p.Ho;        // uniform
       const unsigned soff = (unsigned)(((img_rel * p.Ho + oy) * p.Wo) * pix_bytes);
-      kfn::buffer_store_b128<KFN_NT_STORE_AUX>(v, rsY, row_ok ? voff_q : OOBV, soff);
+      kfn::buffer_store_b128<0>(v, rsY, row_ok ? voff_q : OOBV, soff);
     }
   } else {
     const int pix_bytes = p.ldy * 4;
@@ -765,11 +763,11 @@ int s2_launch(const kfn_conv_desc* d, const float* x, const void* u2_packed, con
   {
     // AUTO: two channel groups of a tile block adjacent (round 4, profiles/r04_wino4_microbench.log: conv4a 7.19 ms against
     // 7.34 with all eight adjacent and 7.29 with the tile blocks fastest; conv3a / conv2a within 1 % of each other)
-    int ng = a.tiles_n % 2 == 0 ? 2 : (KFN_WINO_DEFAULT_N_FAST ? a.tiles_n : 1);
+    int ng = a.tiles_n % 2 == 0 ? 2 : (S2_DEFAULT_N_FAST ? a.tiles_n : 1);
     if (d->wino_order == KFN_WINO_ORDER_N_FAST) ng = a.tiles_n;
     else if (d->wino_order == KFN_WINO_ORDER_M_FAST) ng = 1;
     else if (d->wino_order >= KFN_WINO_ORDER_GROUPS(1)) ng = d->wino_order - KFN_WINO_ORDER_GROUPS(0);
-    if (ng < 1 || ng > a.tiles_n || a.tiles_n % ng != 0) ng = KFN_WINO_DEFAULT_N_FAST ? a.tiles_n : 1;
+    if (ng < 1 || ng > a.tiles_n || a.tiles_n % ng != 0) ng = S2_DEFAULT_N_FAST ? a.tiles_n : 1;
     a.n_group = ng;
   }
   a.wide_store = (d->Cout % 4 == 0 && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) ? 1 : 0;

@@ -30,32 +30,15 @@
 // LDS.  V of a super-step is 81 slots x [4 k][16 tiles][4 k-steps] floats = 81 KiB: two full buffers exceed the 160 KiB.  The
 // slots are laid out in CONSUMPTION order; the 43 consumed in the first half of a super-step are single-buffered, the other 38
 // double-buffered: a barrier in the middle of the super-step (behind position 43) frees the first 43 slots for the next super-step's
-// values, which the producers store in the second half anyway (gather in the first half, transform, store).  119 KiB.
+// values, which the producers store in the second half anyway.  119 KiB.
 #include "kfn_common.h"
 #include <type_traits>
 
-// Timing-experiment builds (tools/mb/build_s2c.sh; results are WRONG on purpose): bit 0 no mid barrier, 1 no gathers, 2 no
-// transform, 3 no V stores, 4 no weight loads in the loop, 5 no V reads in the loop, 6 no output stores, 7 no epilogue at all
-#ifndef KFN_S2C_EXP
-#define KFN_S2C_EXP 0
-#endif
-// 1: the gathers of super-step s+2 are issued in super-step s right behind the V stores of s+1 (the patch registers are free
-// from there on): more than a super-step between a gather and the transform that consumes it.  0: gathered at the start of s+1.
-#ifndef KFN_S2C_LATE_GATHER
-#define KFN_S2C_LATE_GATHER 1
-#endif
-// 1: launches of at least two workgroups per CU run the persistent form (wino_s2c_pkernel, below); 0: one workgroup per tile block
-#ifndef KFN_S2C_PERSIST
-#define KFN_S2C_PERSIST 1
-#endif
-#ifndef KFN_S2C_PERSIST_MAX_SS
-#define KFN_S2C_PERSIST_MAX_SS 64         // ... of layers with at most this many super-steps
-#endif
-#ifndef KFN_S2C_XSLOT_B
-#define KFN_S2C_XSLOT_B 24
-#endif
-
 namespace {
+
+// Launches of at least two workgroups per CU run the persistent form (wino_s2c_pkernel, below) ...
+constexpr int PERSIST_MAX_SS = 64;   // ... of layers with at most this many super-steps
+constexpr int XSLOT_B = 24;          // first transform slot of waves 4-7 (PART >= 2; waves 0-3: slot 112)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -322,13 +305,14 @@ __global__ __launch_bounds__(512, 1) void wino_s2c_kernel(S2cArgs p) {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     const int s_last = n_super - 1;
-    if constexpr (KFN_S2C_LATE_GATHER) sfor<NPX>([&](auto ic) { p_gather(ic, s_last < 1 ? s_last : 1); });
+    sfor<NPX>([&](auto ic) { p_gather(ic, s_last < 1 ? s_last : 1); });
 
-    // producer timetable inside a super-step (MFMA slots): gathers from slot 0 every GSTEP, transform lines from XSLOT every
-    // XSTEP, [mid barrier at JMID], stores from SSLOT every SSTEP
+    // producer timetable inside a super-step (MFMA slots): transform lines from XSLOT every XSTEP, [mid barrier at JMID], stores
+    // from SSLOT every SSTEP, and two slots behind each store the gather of super-step s+2 into the patch registers it has just
+    // freed: more than a super-step between a gather and the transform that consumes it
     // (the two waves of a SIMD -- w and w + 4: phases A+D, B+C -- run their transform bursts at different times)
-    constexpr int GSTEP = 4, XSLOT = (KFN_S2C_LATE_GATHER && PART >= 2) ? KFN_S2C_XSLOT_B : 112, XSTEP = 4, SSLOT = JMID + 4 + (PART >= 2 ? 2 : 0), SSTEP = 4;
-    static_assert((KFN_S2C_LATE_GATHER || GSTEP * 25 <= XSLOT) && XSLOT + XSTEP * 10 <= JMID && SSLOT + 2 + SSTEP * 25 <= 4 * NPOS, "producer timetable");
+    constexpr int XSLOT = PART >= 2 ? XSLOT_B : 112, XSTEP = 4, SSLOT = JMID + 4 + (PART >= 2 ? 2 : 0), SSTEP = 4;
+    static_assert(XSLOT + XSTEP * 10 <= JMID && SSLOT + 2 + SSTEP * 25 <= 4 * NPOS, "producer timetable");
     for (int ks = 0; ks < n_super; ++ks) {
       const int nxt = ks + 1;
       const int ks1 = nxt < s_last ? nxt : s_last, ks2 = nxt + 1 < s_last ? nxt + 1 : s_last;      // clamped look-ahead super-steps
@@ -342,7 +326,7 @@ __global__ __launch_bounds__(512, 1) void wino_s2c_kernel(S2cArgs p) {
         constexpr int np = G_NPOS[g], j0 = 4 * G_POS0[g];
         constexpr int kst = (j - j0) / np, k = (j - j0) % np;  // k-step, position inside the group
         constexpr int pp = G_POS0[g] + k;
-        if constexpr (j == JMID && !(KFN_S2C_EXP & 1)) {
+        if constexpr (j == JMID) {
           // every wave has read the 43 single-buffered slots: they may take the next super-step's values
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           __builtin_amdgcn_s_barrier();
@@ -350,21 +334,20 @@ __global__ __launch_bounds__(512, 1) void wino_s2c_kernel(S2cArgs p) {
         }
         acc[POS_ACC[pp]] = __builtin_amdgcn_mfma_f32_16x16x4f32(vq[g & 1][k][kst], bq[POS_BREG[pp]][kst], acc[POS_ACC[pp]], 0, 0, 0);
         // V of the NEXT group (the other register set) during this group's k-step 1
-        if constexpr (kst == 1 && g + 1 < NGROUP && !(KFN_S2C_EXP & 32)) {
+        if constexpr (kst == 1 && g + 1 < NGROUP) {
           constexpr int np1 = G_NPOS[g + 1];
           if constexpr (k < np1) v_read(std::integral_constant<int, G_POS0[g + 1] + k>{}, rdD);
           if constexpr (k == np - 1 && np1 > np) v_read(std::integral_constant<int, G_POS0[g + 1] + np>{}, rdD);
         }
         // weights: the register's next fragment once this one has had its last k-step
-        if constexpr (kst == 3 && frag_last_user(pp) && !(KFN_S2C_EXP & 16)) {
+        if constexpr (kst == 3 && frag_last_user(pp)) {
           constexpr int nf = next_frag(pp);
           b_load(std::integral_constant<int, POS_BREG[pp]>{}, (nf >= 64 ? ks1 : ks) * NFRAG + (nf & 63));
         }
-        if constexpr (!KFN_S2C_LATE_GATHER && j < NPX * GSTEP && j % GSTEP == 0 && !(KFN_S2C_EXP & 2)) p_gather(std::integral_constant<int, j / GSTEP>{}, ks1);
-        if constexpr (KFN_S2C_LATE_GATHER && j >= SSLOT + 2 && j < SSLOT + 2 + NPX * SSTEP && (j - SSLOT - 2) % SSTEP == 0 && !(KFN_S2C_EXP & 2))
+        if constexpr (j >= SSLOT + 2 && j < SSLOT + 2 + NPX * SSTEP && (j - SSLOT - 2) % SSTEP == 0)
           p_gather(std::integral_constant<int, (j - SSLOT - 2) / SSTEP>{}, ks2);
-        if constexpr (j >= XSLOT && j < XSLOT + NLINE * XSTEP && (j - XSLOT) % XSTEP == 0 && !(KFN_S2C_EXP & 4)) p_line(std::integral_constant<int, (j - XSLOT) / XSTEP>{});
-        if constexpr (j >= SSLOT && j < SSLOT + NPX * SSTEP && (j - SSLOT) % SSTEP == 0 && !(KFN_S2C_EXP & 8)) p_store(std::integral_constant<int, (j - SSLOT) / SSTEP>{}, stD);
+        if constexpr (j >= XSLOT && j < XSLOT + NLINE * XSTEP && (j - XSLOT) % XSTEP == 0) p_line(std::integral_constant<int, (j - XSLOT) / XSTEP>{});
+        if constexpr (j >= SSLOT && j < SSLOT + NPX * SSTEP && (j - SSLOT) % SSTEP == 0) p_store(std::integral_constant<int, (j - SSLOT) / SSTEP>{}, stD);
         __builtin_amdgcn_sched_barrier(0);
       });
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -424,7 +407,7 @@ __global__ __launch_bounds__(512, 1) void wino_s2c_kernel(S2cArgs p) {
     const int oy = 4 * ty + a;
     const bool row_ok = vr0 + trow < p.vrows && oy < p.Ho;        // uniform
     const unsigned soff = (unsigned)img_rel * p.y_img + (unsigned)(oy * p.Wo) * pix_bytes;
-    if (!(KFN_S2C_EXP & 64)) kfn::buffer_store_b128<KFN_NT_STORE_AUX>(v, rsY, row_ok ? voff_q : OOBV, soff);
+    kfn::buffer_store_b128<0>(v, rsY, row_ok ? voff_q : OOBV, soff);
   }
 }
 
@@ -607,7 +590,7 @@ __global__ __launch_bounds__(512, 1) void wino_s2c_pkernel(S2cArgs p) {
     constexpr int PART = decltype(part_c)::value;
     constexpr int NPX = PART_NPX[PART];
     constexpr int NLINE = NPX / ((PART == 0 || PART == 2) ? 5 : 4) + ((PART == 0 || PART == 2) ? 5 : 4);
-    constexpr int XSLOT = PART >= 2 ? KFN_S2C_XSLOT_B : 112, XSTEP = 4, SSLOT = JMID + 4 + (PART >= 2 ? 2 : 0), SSTEP = 4;
+    constexpr int XSLOT = PART >= 2 ? XSLOT_B : 112, XSTEP = 4, SSLOT = JMID + 4 + (PART >= 2 ? 2 : 0), SSTEP = 4;
     static_assert(XSLOT + XSTEP * 10 <= JMID && SSLOT + 2 + SSTEP * 25 <= 4 * NPOS, "producer timetable");
     for (int ks = 0; ks < n_super; ++ks, ++gs) {
       // look-ahead targets: the weights of the next super-step, the gathers of the one after -- of THIS block, of the NEXT block's
@@ -688,7 +671,7 @@ __global__ __launch_bounds__(512, 1) void wino_s2c_pkernel(S2cArgs p) {
       const bool q_ok = n0 + nq * 4 < p.Cout;
       const unsigned voff_q = q_ok ? (unsigned)((spx >> 2) * p.Wo + (spx & 3)) * p.y_pix + (unsigned)(n0 >> 4) * p.y_cb + (unsigned)(nq * 16) : OOBV;
 #pragma unroll
-      for (int e = 0; e < ((KFN_S2C_EXP & 128) ? 0 : 4); ++e) {
+      for (int e = 0; e < 4; ++e) {
         float t[4][5];
 #pragma unroll
         for (int nu = 0; nu < 5; ++nu)
@@ -711,7 +694,7 @@ __global__ __launch_bounds__(512, 1) void wino_s2c_pkernel(S2cArgs p) {
           const int ty = kk < cur.brk ? cur.ty0 + kk : kk - cur.brk;
           const bool row_ok = col_ok && cur.vr0 + kk < p.vrows;  // (uniform; Ho is a multiple of 4: whole tiles)
           const unsigned soff = (unsigned)img_rel * p.y_img + (unsigned)(4 * ty * p.Wo + 4 * tx) * pix_bytes;
-          if (!(KFN_S2C_EXP & 64)) kfn::buffer_store_b128<KFN_NT_STORE_AUX>(v, rsY, row_ok ? voff_q : OOBV, soff);
+          kfn::buffer_store_b128<0>(v, rsY, row_ok ? voff_q : OOBV, soff);
         }
         __builtin_amdgcn_wave_barrier();
       }
@@ -733,7 +716,7 @@ __global__ __launch_bounds__(512, 1) void wino_s2c_pkernel(S2cArgs p) {
 
 }  // namespace
 
-int kfn::wino_s2c_lds_bytes() { return KFN_S2C_PERSIST ? (LDS_P > LDS_BYTES ? LDS_P : LDS_BYTES) : LDS_BYTES; }
+int kfn::wino_s2c_lds_bytes() { return LDS_P > LDS_BYTES ? LDS_P : LDS_BYTES; }
 
 // pointer-free routing check of the F(4,2) form (kfn_winograd_s2_supported answers it for wino_form = KFN_WINO_FORM_S2_F42)
 int kfn::wino_s2c_supported(const kfn_conv_desc* d) {
@@ -789,7 +772,6 @@ int kfn::launch_wino_s2c(const kfn_conv_desc* d, const float* x, const void* u_p
   a.x_img = (unsigned)img_b; a.x_pix = xb ? 64u : (unsigned)d->ldx * 4u; a.x_cb = xb ? (unsigned)(d->H * d->W) * 64u : 64u;
   a.y_img = (unsigned)out_b; a.y_pix = yb ? 64u : (unsigned)d->ldy * 4u; a.y_cb = yb ? (unsigned)(a.Ho * a.Wo) * 64u : 64u;
   const long nwg = (long)a.tiles_m * a.tiles_n;
-#if KFN_S2C_PERSIST
   // the persistent form: one workgroup per CU walking its share of the tile blocks (needs two super-steps of look-ahead inside a
   // block; launches that do not even fill the chip once keep one workgroup per block)
   static int n_cu = 0;
@@ -802,7 +784,7 @@ int kfn::launch_wino_s2c(const kfn_conv_desc* d, const float* x, const void* u_p
   // 3.81.  What a block still costs beyond its super-steps (15 of conv2a's 54 us) is the issue of its 131 KB of output stores (a
   // timing build without them: -8 % on conv2a in either form) and the consumers' epilogue, which persistence cannot hide.  (The
   // first build spilled 31 block-level VGPRs whose reloads queued behind the prefetches in flight: lane_now().)
-  if (d->Cin / SS_CH >= 2 && d->Cin / SS_CH <= KFN_S2C_PERSIST_MAX_SS && nwg >= 2L * n_cu) {
+  if (d->Cin / SS_CH >= 2 && d->Cin / SS_CH <= PERSIST_MAX_SS && nwg >= 2L * n_cu) {
     static std::atomic<uint64_t> attr_done_p{0};
     int rcp = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino_s2c_pkernel), LDS_P, attr_done_p);
     if (rcp != KFN_OK) return rcp;
@@ -810,7 +792,6 @@ int kfn::launch_wino_s2c(const kfn_conv_desc* d, const float* x, const void* u_p
     KFN_LAUNCH_CHECK("wino_s2c_pkernel");
     return KFN_OK;
   }
-#endif
   static std::atomic<uint64_t> attr_done{0};
   int rc = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino_s2c_kernel), LDS_BYTES, attr_done);
   if (rc != KFN_OK) return rc;

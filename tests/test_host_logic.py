@@ -505,6 +505,21 @@ def test_every_header_function_is_bound_and_exported():
         assert len(_lib.SYMBOLS[name][1]) == n, name
 
 
+def test_kernel_sources_have_no_build_switches():
+    """The library is built one way (kfnet_amd/build.py): no source selects code by a KFN_ macro
+    that a -D could flip, so the sources read as what ships."""
+    csrc = os.path.join(ROOT, 'kfnet_amd', 'csrc')
+    cond = re.compile(r'^\s*#\s*(if|ifdef|ifndef|elif|elifdef|elifndef)\b.*\bKFN_.*$', re.M)
+    found = []
+    for name in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, name)
+        if os.path.isfile(path):
+            text = open(path, errors='replace').read()
+            found += ['%s:%d: %s' % (name, text.count('\n', 0, m.start()) + 1, m.group(0).strip())
+                      for m in cond.finditer(text)]
+    assert not found, '\n'.join(found)
+
+
 def test_loader_generated_cost_volume_route_packs_conv0_for_the_direct_kernel():
     """with Graph.factor_cost_volume = False conv0's kernel variable goes to kfn_cost_volume_conv,
     which reads the [cout_pad][9 Cin] direct-convolution layout -- whatever route Network.conv had picked for the layer

@@ -8,7 +8,7 @@ import ctypes as C, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from kfnet_amd import _lib
-if os.environ.get('MB_LIB'):          # a timing-experiment build (tools/mb/build_hot.sh)
+if os.environ.get('MB_LIB'):          # A/B: a libkfnet_hip.so built from another commit
     _lib.LIB_PATH = os.path.abspath(os.environ['MB_LIB'])
 lib = _lib.load()
 st = torch.cuda.current_stream().cuda_stream
