@@ -45,7 +45,7 @@ extern "C" {
  * 8 (round 6): KFN_WINO_FORM_S2_F42, kfn_apply_transform / kfn_pixel_map / kfn_bilinear_sampler.
  * 9 (round 6): kfn_conv_desc.x_layout / y_layout (KFN_LAYOUT_C16).  10 (round 6): kfn_kalman_arith_probe.
  * 11: camera poses -- kfn_pnp_desc, kfn_pnp_scratch_bytes, kfn_pnp_ransac, kfn_pnp_hypotheses. */
-#define KFN_ABI_VERSION 11
+#define KFN_ABI_VERSION 12
 
 const char* kfn_last_error(void);
 int kfn_abi_version(void);
@@ -225,7 +225,8 @@ int kfn_conv2d_plan(const kfn_conv_desc* desc, int* config, int* bk, int* tiles)
  *     kfn_winograd_workspace_bytes / kfn_winograd_plan: the two-kernel Winograd form), kfn_cost_volume (materialising),
  *     kfn_cost_volume_conv (volume generated in conv0's loader), kfn_cost_volume_gather, kfn_flow_softargmax,
  *     kfn_flow_head, kfn_oflow_tail.  A maintainer wiring the reference to this library needs none of them.
- *   Reference API beside eval.py's path: kfn_kalman_fuse, kfn_kalman_fuse2 (KFNet.BuildKFCoord / GetKFCoord2 alone). */
+ *   Reference API beside eval.py's path: kfn_kalman_fuse, kfn_kalman_fuse2 (KFNet.BuildKFCoord / GetKFCoord2 alone).
+ *   The single-network programs (SCoordNet/eval.py, OFlowNet/eval.py) add kfn_coord_records / kfn_flow_records (ABI 12). */
 
 /* [LEGACY: two-kernel form]  Winograd F(2x2,3x3) variant for 3x3 stride-1 SAME convolutions (same arguments and
  * result as kfn_conv2d_nhwc up to fp32 round-off, 2.25x fewer MFMA FLOPs): 16 GEMMs on the
@@ -513,6 +514,21 @@ int kfn_pixel_map(float* out, int ld_out, int B, int H, int W, int normalize, fl
                   float focal_y, void* stream);
 int kfn_bilinear_sampler(const float* imgs, int ld_img, int B, int Hs, int Ws, int C, const float* coords, int ld_coords,
                          int Ht, int Wt, float* out, int ld_out, void* stream);
+
+/* ---- records of the single-network programs (ABI 12) ------------------------------------------------
+ * SCoordNet/eval.py and OFlowNet/eval.py run one network each; these two element-wise launches turn its device output into
+ * the rows their .npy files hold.  Both return KFN_ERR_ARG on a null pointer, P <= 0 or a misaligned pointer.
+ *   kfn_coord_records  meas [P,ld_meas] = (x, y, z, sigma) (ld_meas >= 4, 4-byte aligned) -> out [P,4] = (T.x, 1/sigma)
+ *                      (16-byte aligned): bit for bit the record kfn_kalman_scan emits on a reset frame.  T.x is
+ *                      ((M0 x + M1 y) + M2 z) + M3 per row, every product and sum rounded on its own; 1/sigma is the scan's
+ *                      quotient (correctly rounded for normal-range sigma; below 2^-96 it may differ from IEEE in the last
+ *                      place, exactly as the scan's does).  transform12 = HOST pointer to the 3x4 row-major matrix (read
+ *                      during the call), or NULL for the identity.
+ *   kfn_flow_records   flow_xy [P,2] = (u, v) in grid cells, sigma_trans [P] -> out [P,3] = (u, v, 1/sigma_trans); all
+ *                      4-byte aligned.  The division is IEEE binary32 1.0f / sigma_trans, correctly rounded (round to nearest
+ *                      even, denormals kept): equal bit for bit to numpy's np.float32(1) / sigma. */
+int kfn_coord_records(const float* meas, int ld_meas, const float* transform12, float* out, long P, void* stream);
+int kfn_flow_records(const float* flow_xy, const float* sigma_trans, float* out, long P, void* stream);
 
 /* ---- Network.concat fallback (cnn_wrapper/network.py:316-318): strided channel copy -- */
 int kfn_copy_channels(const float* src, int ld_src, float* dst, int ld_dst, int P, int C,

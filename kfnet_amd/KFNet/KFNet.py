@@ -78,7 +78,10 @@ class _FeatTower(Network):
 
 class KFNet():
     def __init__(self, images, spec, train_scoordnet=False, train_oflownet=False, dropout_rate=0.5,
-                 seed=None, reuse=True):
+                 seed=None, reuse=True, towers=('scoordnet', 'oflownet')):
+        """`towers`: the image towers built here -- both for KFNet; ('scoordnet',) or ('oflownet',) for the single-network
+        programs (kfnet_amd.engine.SCoordNetEngine / OFlowNetEngine), whose graphs then hold only that network's launches,
+        buffers and variables."""
         if train_scoordnet or train_oflownet:
             raise NotImplementedError('training is out of scope of the MI355X prediction path')
         self.focal_x = spec.focal_x
@@ -104,8 +107,11 @@ class KFNet():
         self.frame_ops = []   # image-only stage (towers)
         self.pair_ops = []    # image-pair stage (cost volume, OFlowNet, flow)
         self.scan_ops = []    # recurrent stage
-        self.scoordnet = self.BuildSCoordNet()
-        self.temp_feat_maps = self.BuildOFlowFeat()
+        unknown = set(towers) - {'scoordnet', 'oflownet'}
+        if unknown or not towers:
+            raise ValueError('towers must name scoordnet and/or oflownet, got %r' % (towers,))
+        self.scoordnet = self.BuildSCoordNet() if 'scoordnet' in towers else None
+        self.temp_feat_maps = self.BuildOFlowFeat() if 'oflownet' in towers else None
         self._kalman = None
 
     ####################### I/O #######################

@@ -5,6 +5,9 @@
 //   kfn_apply_transform   KFNet/util.py:12-40   x' = (T [x;1])[0:3], no perspective divide
 //   kfn_pixel_map         KFNet/util.py:42-63   map[b,y,x] = (x, y)  (optionally ((x-u)/fx, (y-v)/fy))
 //   kfn_bilinear_sampler  tools/util.py:3-94    clamped corners AND weights from the clamped corners, add_n order
+// and the record formats of the single-network programs (SCoordNet/eval.py, OFlowNet/eval.py):
+//   kfn_coord_records     (T.x, 1/sigma) of a measurement, bit for bit what the scan emits on a reset frame
+//   kfn_flow_records      (u, v, 1/sigma_trans) of OFlowNet's flow head
 // Built with -ffp-contract=off (kfnet_amd/build.py): products and sums are rounded one by one like TF's elementwise ops.
 #include "kfn_common.h"
 
@@ -62,7 +65,86 @@ __global__ void bilinear_sampler_kernel(const float* __restrict__ img, int ldi, 
   out[p * ldo + c] = ((w00 * im00 + w01 * im01) + w10 * im10) + w11 * im11;   // tf.add_n order
 }
 
+// The quotient of the scan's LEAN build (kfn_kalman.hip, div_rn_normal): the same instructions, so that a coord record is
+// bit-identical to the scan's record of a reset frame.  Correctly rounded for normal-range operands; see kfn_kalman.hip.
+__device__ __forceinline__ float div_rn_normal(float a, float b) {
+  const float r0 = __builtin_amdgcn_rcpf(b);
+  const float nb = -b;
+  const float f0 = __builtin_fmaf(nb, r0, 1.0f);
+  const float f1 = __builtin_fmaf(f0, r0, r0);
+  const float m = a * f1;
+  const float f2 = __builtin_fmaf(nb, m, a);
+  const float f3 = __builtin_fmaf(f2, f1, m);
+  const float f4 = __builtin_fmaf(nb, f3, a);
+  const float q = __builtin_fmaf(f4, f1, f3);
+  return __builtin_amdgcn_div_fixupf(q, b, a);
+}
+
+struct CoordRecordArgs {
+  const float* meas;
+  float* out;
+  long P;
+  int ld;
+  int has_transform;
+  float M[12];
+};
+
+// fuse_pixel's reset branch (kfn_kalman.hip): outv = z, ApplyTransform in the scan's association order, 1/sigma
+__global__ __launch_bounds__(256) void coord_records_kernel(CoordRecordArgs a) {
+  const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= a.P) return;
+  const float* z = a.meas + p * a.ld;
+  const float zx = z[0], zy = z[1], zz = z[2], zw = z[3];
+  float4 r;
+  if (a.has_transform) {
+    const float* M = a.M;
+    r.x = ((M[0] * zx + M[1] * zy) + M[2] * zz) + M[3];
+    r.y = ((M[4] * zx + M[5] * zy) + M[6] * zz) + M[7];
+    r.z = ((M[8] * zx + M[9] * zy) + M[10] * zz) + M[11];
+  } else {
+    r.x = zx; r.y = zy; r.z = zz;
+  }
+  r.w = div_rn_normal(1.0f, zw);
+  reinterpret_cast<float4*>(a.out)[p] = r;
+}
+
+__global__ __launch_bounds__(256) void flow_records_kernel(const float* __restrict__ flow, const float* __restrict__ sigma,
+                                                           float* __restrict__ out, long P) {
+  const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  out[p * 3 + 0] = flow[p * 2 + 0];
+  out[p * 3 + 1] = flow[p * 2 + 1];
+  out[p * 3 + 2] = 1.0f / sigma[p];          // IEEE division, correctly rounded (hipcc's default for '/')
+}
+
 }  // namespace
+
+extern "C" int kfn_coord_records(const float* meas, int ld_meas, const float* transform12, float* out, long P, void* stream) {
+  KFN_REQUIRE(meas && out, "kfn_coord_records: null pointer");
+  KFN_REQUIRE(P > 0, "kfn_coord_records: P = %ld", P);
+  KFN_REQUIRE(ld_meas >= 4, "kfn_coord_records: ld_meas = %d < 4", ld_meas);
+  KFN_REQUIRE((reinterpret_cast<uintptr_t>(meas) & 3) == 0, "kfn_coord_records: meas is not 4-byte aligned");
+  KFN_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "kfn_coord_records: out is not 16-byte aligned");
+  CoordRecordArgs a;
+  a.meas = meas;
+  a.out = out;
+  a.P = P;
+  a.ld = ld_meas;
+  a.has_transform = transform12 != nullptr;
+  for (int i = 0; i < 12; ++i) a.M[i] = transform12 ? transform12[i] : 0.f;
+  hipLaunchKernelGGL(coord_records_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return kfn::check_hip(hipGetLastError(), "kfn_coord_records launch");
+}
+
+extern "C" int kfn_flow_records(const float* flow_xy, const float* sigma_trans, float* out, long P, void* stream) {
+  KFN_REQUIRE(flow_xy && sigma_trans && out, "kfn_flow_records: null pointer");
+  KFN_REQUIRE(P > 0, "kfn_flow_records: P = %ld", P);
+  KFN_REQUIRE(((reinterpret_cast<uintptr_t>(flow_xy) | reinterpret_cast<uintptr_t>(sigma_trans) |
+                reinterpret_cast<uintptr_t>(out)) & 3) == 0, "kfn_flow_records: pointers must be 4-byte aligned");
+  hipLaunchKernelGGL(flow_records_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, flow_xy,
+                     sigma_trans, out, P);
+  return kfn::check_hip(hipGetLastError(), "kfn_flow_records launch");
+}
 
 extern "C" int kfn_apply_transform(const float* coords, int ld_in, const float* transform, int per_batch, int B, int H, int W,
                                    float* out, int ld_out, void* stream) {

@@ -318,3 +318,242 @@ class KFNetEngine(object):
 
     def flops_per_frame(self):
         return sum(op.flops() for op in self.heavy_ops if hasattr(op, 'flops')) / self.B
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Single-network engines: the reference's "Test SCoordNet" and "Test OFlowNet" programs.  Each builds only its
+# own network on the Graph, so it loads (strict) from a container that holds only that scope and allocates nothing of the
+# other network.  They keep the interface pipeline.StreamedSequence and dist.run_chunk drive (heavy / prime / scan /
+# process / records); `scan` is the element-wise record launch, and there is no state to hand from rank to rank.
+# ----------------------------------------------------------------------------------------------------------------------
+def _single_network(g, images, spec, tower):
+    """The KFNet model object with one tower; for 'oflownet' also the cost volume, OFlowNet and the flow head on the
+    feature ring (pair i = ring slots (i, i+1)).  Returns the model."""
+    net = KFNet(images, spec, towers=(tower,))
+    if tower == 'oflownet':
+        B = spec.batch_size
+        ring = net.temp_feat_maps
+        n_ops = len(g.ops)
+        net.BuildOFlowNet(ring.batch(0, B, name='feat_map1'), ring.batch(1, B, name='feat_map2'), None, None)
+        net.pair_ops = g.ops[n_ops:]
+    return net
+
+
+def network_variables(tower, image_size=(480, 640), batch=1):
+    """TF names of the variables an engine of `tower` ('scoordnet' | 'oflownet') loads, i.e. every key of its scope it
+    needs from a container.  Builds the graph on the host only (no device)."""
+    g = Graph()
+    images = g.placeholder((batch,) + tuple(image_size) + (3,), 'u8', name='images')
+    _single_network(g, images, KFNetDataSpec(batch_size=batch, image_size=image_size), tower)
+    return sorted({p.source for p in g.params.values()})
+
+
+def check_weights(W, names):
+    """KeyError naming the first of `names` that the container W lacks; other keys of W are ignored."""
+    for name in names:
+        if name not in W:
+            raise KeyError('weight %s missing from the container' % name)
+
+
+class _SingleNetEngine(object):
+    record_channels = 4
+
+    def _build(self, tower, image_size, batch, max_chunk, device, graph_options):
+        import torch
+        self.torch = torch
+        self.B = int(batch)
+        self.H, self.W = image_size
+        self.h, self.w = grid_size(image_size)
+        self.hw = self.h * self.w
+        self.max_chunk = int(max_chunk)
+        g = self.graph = Graph()
+        if torch.cuda.is_available():      # the LDS a workgroup may use steers Network.conv's routes (as in KFNetEngine)
+            import ctypes as C
+            lds = C.c_int(0)
+            dev_index = torch.device(device).index
+            _lib.check(_lib.load().kfn_device_info(torch.cuda.current_device() if dev_index is None else dev_index,
+                                                   None, C.byref(lds), None, 0), 'kfn_device_info')
+            if lds.value > 0:
+                g.lds_bytes_per_cu = int(lds.value)
+        for key, val in (graph_options or {}).items():
+            if not hasattr(g, key):
+                raise ValueError('unknown Graph option %r' % key)
+            setattr(g, key, val)
+        self.images = g.placeholder((self.B, self.H, self.W, 3), 'u8', name='images')
+        self.net = _single_network(g, self.images, KFNetDataSpec(batch_size=self.B, image_size=image_size), tower)
+        return g
+
+    def _finish(self, weights, device):
+        g = self.graph
+        self.c_rec = g.tensor((self.max_chunk, self.h, self.w, self.record_channels), name='chunk_records')
+        g.finalize(device)
+        g.load_weights(weights, strict=True)     # this network's scope only: other keys are ignored, a missing one raises
+        self.lib = _lib.load()
+        self.device = g.device
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def _chunk_buffer(self, t, C, name):
+        """[max_chunk + B, h, w, C] buffer the batch output `t` is produced into in place (slid per batch, as in
+        KFNetEngine: a partial batch still addresses B slots)."""
+        if t.base is not None or t.ld != t.C or t.ch_off != 0:
+            raise _lib.KfnError('%r is not a dense root tensor: cannot be produced in place' % t.name)
+        c = self.graph.tensor((self.max_chunk + self.B, self.h, self.w, C), name=name)
+        t.rebind(c.storage, 0, t.C)
+        return c
+
+    def upload_frames(self, frames):
+        """uint8 [T,H,W,3] host array -> device tensor."""
+        frames = np.ascontiguousarray(frames)
+        assert frames.dtype == np.uint8 and frames.shape[1:] == (self.H, self.W, 3)
+        return self.torch.from_numpy(frames).to(self.device)
+
+    def _set_batch_images(self, dev_frames, start, count, stream):
+        fb = self.H * self.W * 3
+        _lib.check(self.lib.kfn_memcpy_d2d(self.images.ptr, dev_frames.data_ptr() + start * fb, count * fb, stream),
+                   'memcpy images')
+
+    def process(self, dev_frames, t0=0):
+        """heavy + records; returns the device records view [T,h,w,C] (valid until the next call)."""
+        T = int(dev_frames.shape[0])
+        if T == 0:
+            return self.records(0)
+        self.heavy(dev_frames, T)
+        self.scan(T, t0)
+        return self.records(T)
+
+    def records(self, T):
+        C = self.record_channels
+        return self.c_rec.root_storage.buf[:T * self.hw * C].view(T, self.h, self.w, C)
+
+    def get_state(self):
+        raise _lib.KfnError('%s has no recurrent state to hand between ranks' % type(self).__name__)
+
+
+class SCoordNetEngine(_SingleNetEngine):
+    """SCoordNet alone: per frame the measurement (x, y, z, sigma) and its record (T.x, 1/sigma) -- bit for bit the record
+    KFNetEngine emits on a reset frame.  Frames are independent: `reset_period` = 1 tells dist.run_chunk that no chunk
+    needs its predecessor (nothing to prime, nothing to hand over)."""
+    reset_period = 1
+    record_channels = 4
+
+    def __init__(self, weights, image_size=(480, 640), batch=4, transform=None, max_chunk=256, device='cuda:0',
+                 emit_metrics=False, graph_options=None):
+        g = self._build('scoordnet', image_size, batch, max_chunk, device, graph_options)
+        self.transform = None if transform is None else np.asarray(transform, dtype=np.float32)
+        self.emit_metrics = bool(emit_metrics)
+        self.meas = self.net.GetMeasureCoord()[0].base                  # [B,h,w,4] (x, y, z, sigma)
+        self.c_meas = self._chunk_buffer(self.meas, 4, 'chunk_meas')
+        # kfnet_amd.KFNet.metrics.DeviceMetrics reads the measurement in the meas / temp / KF roles, and an all-zero NIS
+        self.c_temp = self.c_kf = self.c_meas if emit_metrics else None
+        self.c_nis = g.tensor((self.max_chunk, self.h, self.w, 3), name='chunk_nis') if emit_metrics else None
+        self.heavy_ops = list(self.net.frame_ops)
+        self._finish(weights, device)
+        import ctypes as C
+        self._t12 = None
+        if self.transform is not None:
+            self._t12 = (C.c_float * 12)(*[float(v) for v in self.transform[:3, :4].reshape(-1)])
+
+    def prime(self, dev_prev_frame):
+        """Nothing to do: a measurement depends on its own frame only."""
+
+    def heavy(self, dev_frames, T=None, dst0=0):
+        """SCoordNet for frames [0,T) of `dev_frames` -> measurement slots dst0 + t."""
+        T = int(dev_frames.shape[0]) if T is None else int(T)
+        if dst0 + T > self.max_chunk:
+            raise ValueError('chunk of %d frames (at slot %d) exceeds max_chunk=%d' % (T, dst0, self.max_chunk))
+        stream = self._stream()
+        for s0 in range(0, T, self.B):
+            cnt = min(self.B, T - s0)
+            self._set_batch_images(dev_frames, s0, cnt, stream)
+            self.meas.slide((dst0 + s0) * self.hw * 4)
+            self.graph.run(stream, self.heavy_ops, active=(cnt, self.B))
+
+    def scan(self, T, t0=0):
+        """The records of the T staged measurements (kfn_coord_records)."""
+        if T > 0:
+            _lib.check(self.lib.kfn_coord_records(self.c_meas.ptr, 4, self._t12, self.c_rec.ptr, int(T) * self.hw,
+                                                  self._stream()), 'kfn_coord_records')
+
+    def debug(self, T):
+        return {'meas': self.c_meas.root_storage.buf[:T * self.hw * 4].view(T, self.h, self.w, 4).cpu().numpy()}
+
+    def flops_per_frame(self):
+        return sum(op.flops() for op in self.heavy_ops if hasattr(op, 'flops')) / self.B
+
+
+class OFlowNetEngine(_SingleNetEngine):
+    """The flow-feature tower + cost volume + OFlowNet + flow head alone: per frame t the flow (u, v) in grid cells and
+    sigma_trans of the pair (t-1, t), as records (u, v, 1/sigma_trans).  Cell (r, c) of frame t comes from cell
+    (r + v, c + u) of frame t-1.  The long feature ring and the prime() hand-over are KFNetEngine's: the first pair of a
+    chunk uses the last frame of the previous chunk (or the frame prime() was given); the row of a sequence's first frame
+    has no predecessor and means nothing.  `reset_period` = 0: every chunk but the first needs the frame before it."""
+    reset_period = 0
+    record_channels = 3
+
+    def __init__(self, weights, image_size=(480, 640), batch=4, max_chunk=256, device='cuda:0', graph_options=None):
+        g = self._build('oflownet', image_size, batch, max_chunk, device, graph_options)
+        net = self.net
+        self.flow = net.prob.flow                                          # [B*hw,1,1,2]
+        self.sigma_t = net.oflownet.get_output_by_name('uncertainty')      # [B*hw,1,1,1]
+        self.c_flow = self._chunk_buffer(self.flow, 2, 'chunk_flow')
+        self.c_sigma = self._chunk_buffer(self.sigma_t, 1, 'chunk_sigma_trans')
+        # the long ring of KFNetEngine: [max_chunk + B + 1] maps, batch k's behind batch k-1's
+        from .graph import Storage
+        ring = net.temp_feat_maps
+        self.ring_slots = self.max_chunk + self.B + 1
+        ring_store = Storage(self.ring_slots * self.hw * ring.C, ring.dtype)
+        g.storages.append(ring_store)
+        ring.rebind(ring_store, 0, ring.C)
+        self._ring_pos = 0
+        self.tower_ops = list(net.frame_ops)
+        self.heavy_ops = net.frame_ops + net.pair_ops
+        self._finish(weights, device)
+
+    def prime(self, dev_prev_frame):
+        """Flow features of the frame preceding the next chunk -> ring slot 1 (as KFNetEngine.prime)."""
+        stream = self._stream()
+        fb = self.H * self.W * 3
+        _lib.check(self.lib.kfn_memcpy_d2d(self.images.ptr, dev_prev_frame.data_ptr(), fb, stream), 'prime')
+        self.net.temp_feat_maps.slide(0)
+        self.graph.run(stream, self.tower_ops, active=(1, self.B))
+        self._ring_pos = 1
+
+    def heavy(self, dev_frames, T=None, dst0=0):
+        """Tower + OFlowNet for frames [0,T) of `dev_frames` -> flow / sigma_trans slots dst0 + t."""
+        T = int(dev_frames.shape[0]) if T is None else int(T)
+        if dst0 + T > self.max_chunk:
+            raise ValueError('chunk of %d frames (at slot %d) exceeds max_chunk=%d' % (T, dst0, self.max_chunk))
+        stream = self._stream()
+        ring = self.net.temp_feat_maps
+        hw = self.hw
+        per_map = hw * ring.C
+        if self._ring_pos != 0:
+            # once per chunk: the map of the frame before this chunk -> slot 0
+            ring.slide(0)
+            _lib.check(self.lib.kfn_memcpy_d2d(ring.ptr, ring.ptr + self._ring_pos * per_map * 4, per_map * 4, stream),
+                       'ring hand-over')
+            self._ring_pos = 0
+        for s0 in range(0, T, self.B):
+            cnt = min(self.B, T - s0)
+            d0 = dst0 + s0
+            self._set_batch_images(dev_frames, s0, cnt, stream)
+            self.flow.slide(d0 * hw * 2)
+            self.sigma_t.slide(d0 * hw)
+            ring.slide(self._ring_pos * per_map)
+            self.graph.run(stream, self.heavy_ops, active=(cnt, self.B))
+            self._ring_pos += cnt
+
+    def scan(self, T, t0=0):
+        """The records of the T staged flows (kfn_flow_records)."""
+        if T > 0:
+            _lib.check(self.lib.kfn_flow_records(self.c_flow.ptr, self.c_sigma.ptr, self.c_rec.ptr, int(T) * self.hw,
+                                                 self._stream()), 'kfn_flow_records')
+
+    def debug(self, T):
+        return {'flow': self.c_flow.root_storage.buf[:T * self.hw * 2].view(T, self.h, self.w, 2).cpu().numpy(),
+                'sigma_trans': self.c_sigma.root_storage.buf[:T * self.hw].view(T, self.h, self.w, 1).cpu().numpy()}
+
+    def flops_per_frame(self):
+        return sum(op.flops() for op in self.heavy_ops if hasattr(op, 'flops')) / self.B

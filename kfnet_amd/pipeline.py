@@ -231,10 +231,10 @@ class ChunkLoader(object):
 
 
 class StreamedSequence(object):
-    """Runs host-resident chunks through a `KFNetEngine` with uploads, compute and downloads
-    overlapped.  `run(chunks)` takes an iterable of (first_index, uint8 host tensor
+    """Runs host-resident chunks through a `KFNetEngine` (or a SCoordNetEngine / OFlowNetEngine) with uploads, compute and
+    downloads overlapped.  `run(chunks)` takes an iterable of (first_index, uint8 host tensor
     [n,H,W,3]) -- e.g. a `ChunkLoader` -- and yields (first_index, float32 numpy records
-    [n,h,w,4]); a yielded array is a view of a rotating pinned buffer and is valid until the
+    [n,h,w,C], C = the engine's record_channels); a yielded array is a view of a rotating pinned buffer and is valid until the
     generator is advanced again."""
 
     def __init__(self, eng, chunk=None, depth=3):
@@ -253,8 +253,9 @@ class StreamedSequence(object):
         self.up = torch.cuda.Stream(device=dev)
         self.down = torch.cuda.Stream(device=dev)
         self.dev_frames = [torch.empty((self.chunk, eng.H, eng.W, 3), dtype=torch.uint8, device=dev) for _ in range(n)]
-        self.dev_rec = [torch.empty((self.chunk, eng.h, eng.w, 4), dtype=torch.float32, device=dev) for _ in range(n)]
-        self.host_rec = [_host_buffer((self.chunk, eng.h, eng.w, 4), torch.float32, True) for _ in range(n)]
+        rc = int(getattr(eng, 'record_channels', 4))        # 4 = (T.x, 1/sigma); OFlowNetEngine's flow records: 3
+        self.dev_rec = [torch.empty((self.chunk, eng.h, eng.w, rc), dtype=torch.float32, device=dev) for _ in range(n)]
+        self.host_rec = [_host_buffer((self.chunk, eng.h, eng.w, rc), torch.float32, True) for _ in range(n)]
         self.ev_up = [torch.cuda.Event() for _ in range(n)]
         self.ev_done = [None] * n
         self.ev_down = [None] * n
