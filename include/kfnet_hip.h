@@ -44,7 +44,9 @@ extern "C" {
  * 6 (round 5): split-K Winograd entry points, kfn_winograd_lds_bytes.  7 (round 5): kfn_decode_png_rgb8.
  * 8 (round 6): KFN_WINO_FORM_S2_F42, kfn_apply_transform / kfn_pixel_map / kfn_bilinear_sampler.
  * 9 (round 6): kfn_conv_desc.x_layout / y_layout (KFN_LAYOUT_C16).  10 (round 6): kfn_kalman_arith_probe.
- * 11: camera poses -- kfn_pnp_desc, kfn_pnp_scratch_bytes, kfn_pnp_ransac, kfn_pnp_hypotheses. */
+ * 11: camera poses -- kfn_pnp_desc, kfn_pnp_scratch_bytes, kfn_pnp_ransac, kfn_pnp_hypotheses.
+ * 12: kfn_coord_records, kfn_flow_records; later kfn_crc32c (reading TensorFlow checkpoints), an added export that leaves
+ * every ABI-12 host working, so the number stays. */
 #define KFN_ABI_VERSION 12
 
 const char* kfn_last_error(void);
@@ -65,6 +67,14 @@ int kfn_device_info(int device, int* cu_count, int* lds_bytes_per_cu, char* arch
 #define KFN_PNG_UNSUPPORTED 1
 #define KFN_PNG_ERROR 2
 int kfn_decode_png_rgb8(const char* const* paths, int n, int H, int W, unsigned char* dst, int* status, int threads);
+
+/* ---- host side of restoring a tf.train.Saver V2 checkpoint (ABI 12) -------------------------------------------------
+ * CRC-32C (Castagnoli, reflected polynomial 0x82F63B78, ~0 pre- and post-inversion) of n bytes, extending *crc: *crc == 0
+ * starts a checksum, and calls over consecutive pieces of a buffer give the value of one call over all of it.  The
+ * checkpoint's table blocks and tensors carry it (masked; kfnet_amd/checkpoint.py).  Uses the SSE4.2 crc32 instruction
+ * when the CPU has it, a slicing-by-8 table otherwise (same result).  Host code only -- no device access.  KFN_ERR_ARG on
+ * a null crc, or null data with n > 0. */
+int kfn_crc32c(const void* data, size_t n, uint32_t* crc);
 
 /* ---- plumbing for hosts that do not bring their own allocator/streams (PyTorch does) -- */
 int kfn_malloc(void** dptr, size_t bytes);

@@ -29,8 +29,7 @@ import sys
 
 import numpy as np
 
-from ..tools.io import get_snapshot, read_lines
-from ..weights import load_npz, synthetic_weights
+from ..tools.io import read_lines
 
 SCENES = ('chess', 'fire', 'heads', 'office', 'pumpkin', 'redkitchen', 'stairs')
 # first frames of the test sequences per scene (get_indexes(False), KFNet/train.py:82-141)
@@ -279,14 +278,10 @@ def main(argv=None):
     if a.scene not in SCENES:
         print('Invalid scene:', a.scene)   # KFNet/train.py:142-144
         return 1
-    if a.random_weights:
-        W = synthetic_weights(1234)
-    else:
-        snapshot, step = get_snapshot(a.model_folder)
-        if snapshot is None:
-            print('no kfnet_weights*.npz in', a.model_folder)
-            return 1
-        W = load_npz(snapshot)
+    from .. import modes
+    W = modes.load_weights(a)
+    if W is None:
+        return 1
     import torch
     size = (a.height, a.width)
     rank = int(os.environ.get('RANK', '0'))

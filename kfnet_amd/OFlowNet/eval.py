@@ -7,7 +7,8 @@ I holds image_list.txt.  For every consecutive image pair (i-1, i), i = 1..N-1, 
 frame i-1) and the confidence the reference's vis/vis_optical_flow*.py threshold at 100.  flow_list.txt lists the files in
 order, so `vis/vis_optical_flow_list.py O/flow_list.txt I/image_list.txt out/` pairs line k with images k and k+1.  The
 flow is the same whatever the sequence length: there are no resets.  Only the flow-feature tower, the cost volume and
-OFlowNet run (kfnet_amd.engine.OFlowNetEngine); the model folder's kfnet_weights*.npz may hold just the Temporal/* scope.
+OFlowNet run (kfnet_amd.engine.OFlowNetEngine); the model folder's newest snapshot (a TF checkpoint model.ckpt-<step> or
+a kfnet_weights*.npz) may hold just the Temporal/* scope.
 `--synthetic T` / `--random_weights` replace the images / the checkpoint.
 
 Under `python -m torch.distributed.run --nproc-per-node N -m kfnet_amd.OFlowNet.eval ...` every rank processes a

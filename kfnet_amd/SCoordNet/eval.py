@@ -5,8 +5,9 @@
 I holds image_list.txt (+ optional label_list.txt) and transform.txt; for every image one `coord_<i>.npy` float32 [h,w,4] =
 (T.x, 1/sigma) of SCoordNet's measurement is written to O -- the file contract of kfnet_amd.KFNet.eval, and bit for bit
 the record KFNet writes on a reset frame (kfn_coord_records).  Only SCoordNet runs (kfnet_amd.engine.SCoordNetEngine); the
-model folder's kfnet_weights*.npz may hold just the ScoreNet/* scope.  `--synthetic T` / `--random_weights` replace the
-images / the checkpoint; `--pose` also writes pose_<i>.txt (single process, kfnet_amd.KFNet.eval.write_poses).
+model folder's newest snapshot (a TF checkpoint model.ckpt-<step> or a kfnet_weights*.npz) may hold just the ScoreNet/*
+scope.  `--synthetic T` / `--random_weights` replace the images / the checkpoint; `--pose` also writes pose_<i>.txt
+(single process, kfnet_amd.KFNet.eval.write_poses).
 With label_list.txt every frame's median distance error d_m (cm) is printed, then the median / mean / stddev over d_m.
 
 Under `python -m torch.distributed.run --nproc-per-node N -m kfnet_amd.SCoordNet.eval ...` every rank processes a

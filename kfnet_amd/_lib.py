@@ -132,6 +132,7 @@ SYMBOLS = {
     'kfn_coord_records': (_i, [_vp, _i, _vp, _vp, C.c_long, _vp]),
     'kfn_flow_records': (_i, [_vp, _vp, _vp, C.c_long, _vp]),
     'kfn_decode_png_rgb8': (_i, [C.POINTER(C.c_char_p), _i, _i, _i, _vp, C.POINTER(_i), _i]),
+    'kfn_crc32c': (_i, [_vp, _sz, C.POINTER(C.c_uint32)]),
     'kfn_pnp_scratch_bytes': (_i, [C.POINTER(PnPDesc), C.POINTER(_sz)]),
     'kfn_pnp_ransac': (_i, [C.POINTER(PnPDesc), _vp, _vp, _vp, _vp, _vp]),
     'kfn_pnp_hypotheses': (_i, [C.POINTER(PnPDesc), _vp, _vp, _vp, _vp, _vp]),

@@ -9,6 +9,7 @@ File contracts (float32 .npy, one per frame, [h,w,C] on the label grid h = ceil(
                  images k and k+1 of image_list.txt (vis/vis_optical_flow_list.py's arguments)
 """
 import os
+import sys
 
 import numpy as np
 
@@ -147,14 +148,19 @@ def add_project_flags(ap):
 
 
 def load_weights(a):
-    """--random_weights, or the newest kfnet_weights*.npz of --model_folder (a full KFNet container or one holding only
-    the program's own scope).  None when there is none."""
+    """--random_weights, or the newest snapshot of --model_folder (tools.io.get_snapshot): a kfnet_weights*.npz container
+    or a TF V2 checkpoint model.ckpt-<step>, holding the full KFNet or only the program's own scope.  None, after a
+    message on stderr, when there is none or it cannot be read."""
     from .tools.io import get_snapshot
-    from .weights import load_npz, synthetic_weights
+    from .weights import load_snapshot, synthetic_weights
     if a.random_weights:
         return synthetic_weights(1234)
     snapshot, _ = get_snapshot(a.model_folder)
     if snapshot is None:
-        print('no kfnet_weights*.npz in', a.model_folder)
+        print('no kfnet_weights*.npz or model.ckpt-*.index in', a.model_folder)
         return None
-    return load_npz(snapshot)
+    try:
+        return load_snapshot(snapshot, verbose=os.environ.get('RANK', '0') == '0')
+    except (ValueError, OSError) as e:       # checkpoint.CheckpointError is a ValueError
+        print('cannot restore %s: %s' % (snapshot, e), file=sys.stderr)
+        return None

@@ -2,17 +2,18 @@
 
 The reference restores two TF variable scopes from a tf.train.Saver checkpoint
 (`RestoreFromScope(sess, snapshot, 'ScoreNet' | 'Temporal')`, KFNet/train.py:317-321,
-KFNet/eval.py:66-68).  TF checkpoints cannot be read without TensorFlow, so this
-framework's container is a flat ``{tf_variable_name: float32 ndarray}`` dict stored as
-``.npz`` -- the keys and layouts are exactly the TF ones:
+KFNet/eval.py:66-68).  The weights live in a flat ``{tf_variable_name: float32 ndarray}``
+dict, read either straight from such a V2 checkpoint (kfnet_amd/checkpoint.py, no
+TensorFlow needed) or from this framework's ``.npz`` container of the same dict -- the
+keys and layouts are exactly the TF ones:
 
     ScoreNet/<layer>/kernel [kh,kw,Cin,Cout]   ScoreNet/<layer>/bias [Cout]
     Temporal/feat{1..7}/kernel|bias            Temporal/conv*/kernel|bias
     Temporal/upconv{2,1,0}/kernel [kh,kw,Cout,Cin] (conv2d_transpose layout)
     Temporal/{fc1,fc2,uncertainty}/kernel [in,out]
 
-An offline converter (run where TensorFlow exists) only has to dump
-``{v.name[:-2]: sess.run(v)}`` for these scopes with ``np.savez``.
+`load_snapshot` reads either kind; ``python -m kfnet_amd.checkpoint to-npz`` converts a
+checkpoint into the container.
 `Network.load`'s ``{op_name: {param_name: array}}`` dict (cnn_wrapper/network.py:60-75)
 maps 1:1: ``flat[scope + '/' + op_name + '/' + param_name]``.
 
@@ -97,6 +98,23 @@ def save_npz(path, W):
 def load_npz(path):
     with np.load(path) as z:
         return {k: z[k].astype(np.float32) for k in z.files}
+
+
+def load_snapshot(path, scopes=('ScoreNet', 'Temporal'), verbose=True):
+    """The weights of what tools.io.get_snapshot returned: a `.npz` container (load_npz) or a TF V2 checkpoint prefix
+    (checkpoint.load_checkpoint, only the variables under `scopes`).  Prints one line in the manner of the reference's
+    `Restore from scope ...`: the snapshot, its step, and how many variables were restored and ignored."""
+    from .tools.io import snapshot_step
+    if path.endswith('.npz'):
+        W, ignored = load_npz(path), 0
+    else:
+        from .checkpoint import restore
+        W, ck = restore(path, scopes)
+        ignored = len(ck.names()) - len(W)
+    if verbose:
+        print('Restore from %s (step %d): %d variables restored, %d ignored'
+              % (path, snapshot_step(path), len(W), ignored))
+    return W
 
 
 def from_network_load_dict(data_dict, scope):

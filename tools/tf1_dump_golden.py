@@ -16,6 +16,16 @@ installed where this repository is built, so the repository's ora
   3. commit tests/golden/tf1_kfnet_small.npz (a few hundred KB).  tests/test_golden.py picks every
      tests/golden/tf1_*.npz up automatically and holds the oracle AND the HIP path to it.
 
+A second, independent hook pins the checkpoint reader (kfnet_amd/checkpoint.py), which has only
+ever read files written by this repository's test writer:
+
+         python tools/tf1_dump_golden.py --ckpt tests/golden/tf1_ckpt
+
+writes a small tf.train.Saver V2 checkpoint there (four model variables under ScoreNet/ and
+Temporal/, their Adam slots after one training step, beta1_power / beta2_power, an int64
+global_step) and expected.npz with every variable's value.  Commit the directory (a few KB);
+tests/test_checkpoint_golden.py reads it whenever it exists.
+
 What it does: builds the reference's own graph -- KFNet(images[2,H,W,3], spec, False, False),
 GetMeasureCoord2, GetKFCoordRecursive(last_coord, last_uncertainty), GetNIS, ApplyTransform, the
 exact calls of KF_fusion (KFNet/train.py:241-266) minus the queue-runner input pipeline, which
@@ -113,12 +123,45 @@ def run_sequence(tf, sess, ph, fetch, frames, T4, reset_period, nis_gate):
     return np.stack(records), stages
 
 
+def dump_checkpoint(folder):
+    """A small training-shaped checkpoint written by tf.train.Saver (V2), and expected.npz of its variables."""
+    import tensorflow as tf
+    if not os.path.isdir(folder):
+        os.makedirs(folder)
+    rng = np.random.RandomState(20)
+    shapes = [('ScoreNet/prediction/kernel', (1, 1, 128, 4)), ('ScoreNet/prediction/bias', (4,)),
+              ('Temporal/fc2/kernel', (64, 32)), ('Temporal/fc2/bias', (32,))]
+    with tf.Graph().as_default():
+        vs = []
+        for name, shape in shapes:
+            scope, var = name.rsplit('/', 1)
+            with tf.variable_scope(scope):
+                vs.append(tf.get_variable(var, initializer=rng.uniform(-1, 1, shape).astype(np.float32)))
+        step = tf.train.get_or_create_global_step()
+        loss = tf.add_n([tf.reduce_sum(tf.square(v)) for v in vs])
+        train = tf.train.AdamOptimizer(1e-3).minimize(loss, global_step=step)
+        saver = tf.train.Saver(write_version=tf.train.SaverDef.V2)
+        with tf.Session() as sess:
+            sess.run(tf.global_variables_initializer())
+            sess.run(train)
+            prefix = saver.save(sess, os.path.join(folder, 'model.ckpt'), global_step=step)
+            values = dict((v.op.name, sess.run(v)) for v in tf.global_variables())
+    np.savez(os.path.join(folder, 'expected.npz'), **values)
+    print('wrote', prefix, 'and expected.npz (%d variables, tensorflow %s)' % (len(values), tf.__version__))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('--reference', required=True, help='root of a zlthinker/KFNet checkout')
-    ap.add_argument('--inputs', required=True, help='npz written by tests/golden/make_tf1_inputs.py')
-    ap.add_argument('--out', required=True)
+    ap.add_argument('--reference', help='root of a zlthinker/KFNet checkout')
+    ap.add_argument('--inputs', help='npz written by tests/golden/make_tf1_inputs.py')
+    ap.add_argument('--out')
+    ap.add_argument('--ckpt', help='instead: write a small tf.train.Saver checkpoint into this folder')
     a = ap.parse_args()
+    if a.ckpt:
+        dump_checkpoint(a.ckpt)
+        return
+    if not (a.reference and a.inputs and a.out):
+        ap.error('--reference, --inputs and --out are required (or --ckpt FOLDER)')
     z = np.load(a.inputs)
     frames = z['images']
     T4 = z['transform'].astype(np.float32)
