@@ -82,6 +82,23 @@ def pair_schedule(first, count, total, sequence_length):
     return out
 
 
+def label_rows(first, pairs, total, label_grid):
+    """The label grids the pairs [count,2] (global indices) of frames first.. refer to, for DeviceMetrics.launch:
+    (rows [L,h,w,4] = label_grid(i) for the frames base..top-1 the pairs and the frames themselves span, clipped to the
+    list, pairs as rows of it).  A chunk's pairs reach one frame in front of it and one behind at most, so L <= count + 2."""
+    count = pairs.shape[0]
+    base, top = max(min(int(pairs.min()), first), 0), min(max(int(pairs.max()), first + count - 1) + 1, total)
+    rows = np.stack([label_grid(i) for i in range(base, top)])
+    return rows, np.clip(pairs, base, top - 1) - base
+
+
+def summary_lines(metrics, keys=('d_m', 'd_t', 'd_kf')):
+    """The reference's closing lines (KFNet/eval.py:162-164): median, mean and stddev of each distance error in `keys`
+    over the frames, as print(name, value, ...) writes them."""
+    return [' '.join([name] + [str(fn([m[k] for m in metrics])) for k in keys])
+            for name, fn in (('Median dist error: ', np.median), ('Mean dist error: ', np.mean), ('stddev error: ', np.std))]
+
+
 def dist_median(dmap):
     """np.median over the positive entries of a distance map in cm (KFNet/eval.py:27-29)."""
     pos = dmap[dmap > 0]

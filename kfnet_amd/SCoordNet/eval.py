@@ -7,11 +7,14 @@ I holds image_list.txt (+ optional label_list.txt) and transform.txt; for every 
 the record KFNet writes on a reset frame (kfn_coord_records).  Only SCoordNet runs (kfnet_amd.engine.SCoordNetEngine); the
 model folder's newest snapshot (a TF checkpoint model.ckpt-<step> or a kfnet_weights*.npz) may hold just the ScoreNet/*
 scope.  `--synthetic T` / `--random_weights` replace the images / the checkpoint; `--pose` also writes pose_<i>.txt
-(single process, kfnet_amd.KFNet.eval.write_poses).
+(kfnet_amd.KFNet.eval.write_poses).
 With label_list.txt every frame's median distance error d_m (cm) is printed, then the median / mean / stddev over d_m.
 
 Under `python -m torch.distributed.run --nproc-per-node N -m kfnet_amd.SCoordNet.eval ...` every rank processes a
-contiguous chunk of the frames and writes its own files, bit-identical to a single-process run.
+contiguous chunk of the frames and writes its own files, bit-identical to a single-process run.  With labels or --pose
+each rank also computes its frames' d_m and poses on its GPU (modes.run_shard) and writes their pose_<i>.txt; a process
+group is started only then, and rank 0 gathers the per-frame results and prints the single-process run's d_m lines and
+summary.
 """
 import argparse
 import os
@@ -20,8 +23,7 @@ import sys
 import numpy as np
 
 from .. import modes
-from ..KFNet.eval import SCENES, get_transform, write_poses
-from ..tools.io import read_lines
+from ..KFNet.eval import SCENES, get_transform, read_inputs, refuse_unlaunched, write_poses
 
 FORMAT = '%d, frame %d, d_m = %.3f'
 
@@ -86,20 +88,19 @@ def build_parser():
     ap.add_argument('--model_folder', default='')
     ap.add_argument('--scene', default='')
     modes.add_project_flags(ap)
-    ap.add_argument('--pose', action='store_true', help='also write pose_<i>.txt (RANSAC-PnP on the device; single process)')
+    ap.add_argument('--pose', action='store_true', help='also write pose_<i>.txt (RANSAC-PnP on the device)')
     return ap
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     rank, world, local = modes.sharded_env()
-    if a.pose and world > 1:
-        print('--pose is not supported in the sharded run (WORLD_SIZE=%d): run single-process '
-              '(python -m kfnet_amd.SCoordNet.eval --gpu N ... --pose)' % world, file=sys.stderr)
-        return 2
     if a.scene not in SCENES:
         print('Invalid scene:', a.scene)
         return 1
+    from ..dist import launched
+    if world > 1 and a.pose and not launched():
+        return refuse_unlaunched('--pose', world, 'kfnet_amd.SCoordNet.eval')
     W = modes.load_weights(a)
     if W is None:
         return 1
@@ -111,12 +112,14 @@ def main(argv=None):
         T, paths, label_paths = a.synthetic, None, None
         frames_of = modes.synthetic_frames_of(a.height, a.width)
     else:
-        paths = read_lines(os.path.join(a.input_folder, 'image_list.txt'))
+        try:        # on every rank of a sharded run, before any engine or collective
+            paths, label_paths = read_inputs(a.input_folder)
+        except (OSError, ValueError) as e:
+            print(e, file=sys.stderr)
+            return 1
+        if world > 1 and label_paths is not None and not launched():
+            return refuse_unlaunched('label_list.txt', world, 'kfnet_amd.SCoordNet.eval')
         transform = get_transform(os.path.join(a.input_folder, 'transform.txt'))
-        label_list = os.path.join(a.input_folder, 'label_list.txt')
-        label_paths = read_lines(label_list) if os.path.exists(label_list) else None
-        if label_paths is not None:
-            assert len(paths) == len(label_paths)
         T = len(paths)
         frames_of = modes.image_frames_of(paths, size)
         if rank == 0:
@@ -125,24 +128,47 @@ def main(argv=None):
             print('image number: ', T)
             print('----------------------------------')
     if world > 1:
-        from ..engine import SCoordNetEngine
-        from ..dist import chunk_bounds
-        torch.cuda.set_device(local % max(torch.cuda.device_count(), 1))
-        if label_paths is not None and rank == 0:
-            print('WARNING: label_list.txt found, but the sharded run (WORLD_SIZE=%d) does not evaluate labels' % world,
-                  file=sys.stderr)
-        lo, hi = chunk_bounds(T, world, rank)
-        eng = SCoordNetEngine(W, image_size=size, batch=a.batch, transform=transform, max_chunk=max(hi - lo, 1),
-                              device='cuda:%d' % torch.cuda.current_device())
-        modes.run_shard(eng, frames_of, T, rank, world, a.output_folder, 'coord')
-        torch.cuda.synchronize()
-        return 0
+        return _main_sharded(a, W, size, rank, world, local, T, transform, frames_of, label_paths)
     torch.cuda.set_device(a.gpu)
     device = 'cuda:%d' % a.gpu
     out = eval(paths, transform, W, a.output_folder, image_size=size, batch=a.batch,
                frames=frames_of(0, T) if paths is None else None, label_paths=label_paths, device=device)
     if a.pose:
         write_poses(out[0] if label_paths is not None else out, a.output_folder)
+    return 0
+
+
+def _main_sharded(a, W, size, rank, world, local, T, transform, frames_of, label_paths):
+    """One rank of torch.distributed.run: its contiguous chunk through modes.run_shard.  No rank talks to another unless
+    labels or --pose ask for the per-frame results on rank 0: only then is a process group started (backend as
+    kfnet_amd.KFNet.eval's sharded run)."""
+    import torch
+    from ..engine import SCoordNetEngine
+    from ..dist import chunk_bounds, init_group
+    ndev = torch.cuda.device_count()
+    dev_index = local % max(ndev, 1)
+    torch.cuda.set_device(dev_index)
+    lo, hi = chunk_bounds(T, world, rank)
+    if label_paths is None and not a.pose:
+        eng = SCoordNetEngine(W, image_size=size, batch=a.batch, transform=transform, max_chunk=max(hi - lo, 1),
+                              device='cuda:%d' % torch.cuda.current_device())
+        modes.run_shard(eng, frames_of, T, rank, world, a.output_folder, 'coord')
+        torch.cuda.synchronize()
+        return 0
+    import torch.distributed as dist
+    from ..KFNet.eval import report_sharded
+    init_group(dist, rank, world, dev_index, ndev)
+    try:
+        eng = SCoordNetEngine(W, image_size=size, batch=a.batch, transform=transform, max_chunk=max(hi - lo, 1),
+                              emit_metrics=label_paths is not None, device='cuda:%d' % torch.cuda.current_device())
+        part = modes.run_shard(eng, frames_of, T, rank, world, a.output_folder, 'coord', label_paths=label_paths,
+                               pose=a.pose)
+        report_sharded(dist, [part], T, rank, (lambda m: FORMAT % (m['i'], m['i'], m['d_m']))
+                       if label_paths is not None else None, summary_keys=('d_m',), pose=a.pose)
+        torch.cuda.synchronize()
+        dist.barrier()
+    finally:
+        dist.destroy_process_group()
     return 0
 
 

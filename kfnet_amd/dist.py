@@ -11,16 +11,65 @@ Pairing rule (both sides evaluate it on the same frame index, so no message is e
 unmatched): the chunk that starts at global frame f receives iff `needs_state(f)`; the
 chunk that ends at f (exclusive) sends iff rank+1 exists and `needs_state(f)`.  A chunk that
 starts on a reset boundary (f % reset_period == 0, KFNet/eval.py:94) is independent of its
-predecessor: it posts no receive and its predecessor no send, so it never waits.
+predecessor: it posts no receive and its predecessor no send, so it never waits -- unless the
+engine computes the label metrics, whose numbers on a reset frame depend on the incoming state
+(`handoff_period`).
 
 Transports (`StateLink`): `RcclLink` = the C ABI (kfn_comm_init / kfn_send_state /
 kfn_recv_state: ncclSend/ncclRecv over xGMI, stream-ordered with the scan, device to device);
 `TorchLink` = torch.distributed send/recv (backend 'nccl' is RCCL too; 'gloo' stages the
 message through the host -- CPU tests, or several ranks sharing one GPU).
+
+Per-frame results that the single-process programs print in frame order (label metrics, the
+pose count) are computed by each rank for its own frames and collected once, at the end, onto
+rank 0 (`gather_frames`).
 """
 import ctypes as C
+import os
 
 from . import _lib
+
+
+def backend_for(world, ndev):
+    """Process-group backend of the sharded command lines: KFN_DIST_BACKEND if set, else 'nccl' when every rank has a GPU
+    of its own, else 'gloo' (ranks sharing GPUs)."""
+    return os.environ.get('KFN_DIST_BACKEND', 'nccl' if ndev >= world else 'gloo')
+
+
+def launched():
+    """Is the env:// rendezvous of torch.distributed there: MASTER_PORT, which torch.distributed.run sets for every worker
+    (MASTER_ADDR defaults to this host in init_group)?  Without it no process group can start."""
+    return bool(os.environ.get('MASTER_PORT'))
+
+
+def init_group(dist, rank, world, dev_index, ndev):
+    """Start the torch.distributed process group of a `torch.distributed.run` rank whose device is `dev_index` (already
+    current).  Returns the backend name."""
+    import torch
+    os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
+    backend = backend_for(world, ndev)
+    if backend == 'nccl':
+        dist.init_process_group('nccl', rank=rank, world_size=world, device_id=torch.device('cuda', dev_index))
+    else:
+        dist.init_process_group(backend, rank=rank, world_size=world)
+    return backend
+
+
+def gather_frames(dist, items, dst=0):
+    """Per-frame results of every rank, collected on rank `dst` in global frame order.  `items`: this rank's
+    [(global frame index, result)] -- empty on a rank that owns no frame.  A collective (one gather_object): every rank of
+    the group calls it exactly once per use, whatever it holds.  Results are pickled, so any host object goes (over gloo
+    on the CPU; over nccl through the current device).  Returns the results ordered by frame index on `dst`, None on the
+    other ranks; a frame reported twice raises ValueError on `dst`."""
+    parts = [None] * dist.get_world_size() if dist.get_rank() == dst else None
+    dist.gather_object([(int(i), r) for i, r in items], parts, dst=dst)
+    if parts is None:
+        return None
+    merged = sorted((it for part in parts for it in part), key=lambda it: it[0])
+    for a, b in zip(merged, merged[1:]):
+        if a[0] == b[0]:
+            raise ValueError('gather_frames: frame %d was reported by more than one rank' % a[0])
+    return [r for _, r in merged]
 
 
 def needs_state(first_frame, reset_period):
@@ -28,6 +77,14 @@ def needs_state(first_frame, reset_period):
     if first_frame == 0:
         return False
     return not (reset_period > 0 and first_frame % reset_period == 0)
+
+
+def handoff_period(eng):
+    """The reset period of the pairing rule for `eng`'s chunks: its reset_period, unless the engine says otherwise.  A
+    KFNetEngine built with emit_metrics says 0 (only frame 0 starts clean): the label metrics of a reset frame are computed
+    from the incoming state and the flow from the frame before (kfn_kalman_scan_ex raw_on_reset), so a chunk that starts
+    on a reset frame needs both, like any other chunk."""
+    return getattr(eng, 'handoff_period', eng.reset_period)
 
 
 def chunk_bounds(total_frames, world, rank):
@@ -251,9 +308,10 @@ def iter_cyclic(eng, frames_of, total_frames, block, rank, world, link=None, sta
         # records.  A single process that wants the whole sequence passes world = 1.
         raise ValueError('iter_cyclic: world = %d needs a state link (kfnet_amd.dist.make_link); pass world = 1 to run every block here' % world)
     w = world
+    period = handoff_period(eng)
     for j, lo, hi in cyclic_blocks(total_frames, block, rank, w):
         n = hi - lo
-        need = needs_state(lo, eng.reset_period)
+        need = needs_state(lo, period)
         frames = frames_of(lo - 1 if need else lo, hi)
         if need:
             eng.prime(frames[0])           # flow features of frame lo-1, recomputed locally (5.6 GFLOP instead of a 614 KB message)
@@ -261,7 +319,7 @@ def iter_cyclic(eng, frames_of, total_frames, block, rank, world, link=None, sta
         eng.heavy(frames, n)
         if stamp is not None:
             stamp('heavy_end', j)
-        src, dst = cyclic_handoff_plan(lo, hi, total_frames, rank, w, eng.reset_period)
+        src, dst = cyclic_handoff_plan(lo, hi, total_frames, rank, w, period)
         if src is not None:
             link.recv(eng.get_state(), src, eng)
         if stamp is not None:
@@ -343,9 +401,10 @@ def run_chunk(eng, dev_frames, first_frame, rank, world, link=None, dev_prev_fra
     if link is not None and hasattr(link, 'get_backend'):   # the torch.distributed module itself
         link = TorchLink(link)
     T = int(dev_frames.shape[0])
-    recv, send = handoff_plan(first_frame, T, rank, world if link is not None else 1, eng.reset_period)
+    period = handoff_period(eng)
+    recv, send = handoff_plan(first_frame, T, rank, world if link is not None else 1, period)
     if T > 0:
-        if needs_state(first_frame, eng.reset_period):
+        if needs_state(first_frame, period):
             if dev_prev_frame is None:
                 raise ValueError('chunk starting at frame %d needs the preceding frame' % first_frame)
             eng.prime(dev_prev_frame)      # flow features of frame first_frame-1, recomputed locally

@@ -44,6 +44,9 @@ class KFNetEngine(object):
         emit_debug = bool(emit_debug or emit_metrics)
         self.emit_debug = emit_debug
         self.emit_metrics = bool(emit_metrics)
+        # pairing rule of the sharded runs (dist.handoff_period): with the metrics' debug outputs a reset frame's numbers
+        # depend on the incoming state (raw_on_reset below), so no chunk but frame 0's starts clean
+        self.handoff_period = 0 if self.emit_metrics else self.reset_period
 
         g = self.graph = Graph()
         g.conv_operands = conv_operands

@@ -91,25 +91,40 @@ def run_streamed(eng, source, image_size, output_folder, kind, chunk=256, after_
     return np.zeros((0, eng.h, eng.w, eng.record_channels), np.float32)
 
 
-def run_shard(eng, frames_of, total_frames, rank, world, output_folder, kind, verbose=True):
+def run_shard(eng, frames_of, total_frames, rank, world, output_folder, kind, verbose=True, label_paths=None, pose=False):
     """Frame-sharded run (contiguous chunks, kfnet_amd.dist.chunk_bounds): this rank processes [lo, hi) through
     dist.run_chunk -- which primes an OFlowNetEngine with frame lo - 1 -- and writes its own files.  No rank talks to
     another: neither network carries state from frame to frame.  `frames_of(a, b)` returns uint8 frames [a, b).
-    Returns (lo, records [hi-lo,h,w,C])."""
-    from .dist import chunk_bounds, needs_state, run_chunk
+    Returns (lo, records [hi-lo,h,w,C]).
+    SCoordNet (kind 'coord') only: `label_paths` (the whole sequence's list; the engine built with emit_metrics) and / or
+    `pose` (True, or a PnPSolver) add the chunk's d_m metrics -- label pair (i, i), as SCoordNet.eval -- and poses
+    (kfnet_amd.KFNet.eval.ShardOutputs, right behind the records launch) and return (lo, records, results)."""
+    from .dist import chunk_bounds, handoff_period, needs_state, run_chunk
     lo, hi = chunk_bounds(total_frames, world, rank)
-    need_prev = 1 if (hi > lo and needs_state(lo, eng.reset_period)) else 0
+    outs = None
+    if label_paths is not None or pose:
+        if kind != 'coord':
+            raise ValueError('label metrics and poses need coordinate records, not %r' % kind)
+        from .KFNet.eval import ShardOutputs
+        outs = ShardOutputs(eng, total_frames, output_folder, label_paths,
+                            lambda a, n: np.repeat(np.arange(a, a + n)[:, None], 2, axis=1), pose)
+    res = None
+    need_prev = 1 if (hi > lo and needs_state(lo, handoff_period(eng))) else 0
     if hi > lo:
         dev = eng.upload_frames(frames_of(lo - need_prev, hi))
         rec = run_chunk(eng, dev[need_prev:], lo, rank, world, None, dev[0] if need_prev else None)
+        if outs is not None:
+            res = outs.add(lo, rec)
         rec = rec.cpu().numpy().copy()
     else:
         rec = np.zeros((0, eng.h, eng.w, eng.record_channels), np.float32)
+        if outs is not None:
+            res = outs.add(lo, rec)
     if output_folder and os.path.isdir(output_folder):
         save_records(output_folder, kind, lo, rec)
     if verbose:
         print('rank %d/%d: frames %d~%d done' % (rank, world, lo, hi - 1))
-    return lo, rec
+    return (lo, rec) if outs is None else (lo, rec, res)
 
 
 def sharded_env():
