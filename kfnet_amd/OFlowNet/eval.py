@@ -34,13 +34,8 @@ def eval(image_paths, weights, output_folder, image_size=(480, 640), batch=4, fr
     T = len(image_paths) if frames is None else frames.shape[0]
     eng = engine if engine is not None else OFlowNetEngine(weights, image_size=image_size, batch=batch,
                                                            max_chunk=max(1, min(chunk, T)), device=device)
-
-    def on_chunk(k, lo, rec):
-        if verbose:
-            print('frames %d~%d done' % (lo, lo + rec.shape[0] - 1))
-
-    records = modes.run_streamed(eng, frames if frames is not None else image_paths, image_size, output_folder, 'flow',
-                                 chunk=chunk, on_chunk=on_chunk, decode_workers=decode_workers)
+    records, _ = modes.run_streamed(eng, frames if frames is not None else image_paths, image_size, output_folder, 'flow',
+                                    chunk=chunk, verbose=verbose, decode_workers=decode_workers)
     if output_folder and os.path.isdir(output_folder):
         modes.write_flow_list(output_folder, T)
     return records
@@ -71,13 +66,11 @@ def main(argv=None):
         T = len(paths)
         frames_of = modes.image_frames_of(paths, size)
         if rank == 0:
-            print('----------------------------------')
-            print('image number: ', T)
-            print('----------------------------------')
+            modes.print_banner(T)
     if world > 1:
         from ..engine import OFlowNetEngine
         from ..dist import chunk_bounds
-        torch.cuda.set_device(local % max(torch.cuda.device_count(), 1))
+        modes.rank_device(local)
         lo, hi = chunk_bounds(T, world, rank)
         eng = OFlowNetEngine(W, image_size=size, batch=a.batch, max_chunk=max(hi - lo, 1),
                              device='cuda:%d' % torch.cuda.current_device())

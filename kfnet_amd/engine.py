@@ -28,29 +28,24 @@ def grid_size(image_hw):
     return h, w
 
 
-class KFNetEngine(object):
-    def __init__(self, weights, image_size=(480, 640), batch=4, transform=None, reset_period=500,
-                 nis_gate=0.0, max_chunk=256, device='cuda:0', emit_debug=False, autotune=False,
-                 conv_operands='f32', use_graph=False, emit_metrics=False, graph_options=None):
+class _Engine(object):
+    """What the three engines share: the sizes, the Graph and its options, the batch input, the chunk buffers a batch's
+    outputs are produced into in place, the long flow-feature ring, and the heavy + scan driver that
+    pipeline.StreamedSequence and dist.run_chunk call.  A subclass builds its network between `_build` and `_finish` and
+    provides `heavy`, `scan` and `debug`."""
+    record_channels = 4
+    c_rec = None
+
+    def _build(self, image_size, batch, max_chunk, device, graph_options):
         import torch
         self.torch = torch
         self.B = int(batch)
         self.H, self.W = image_size
         self.h, self.w = grid_size(image_size)
-        self.reset_period = int(reset_period)
-        self.nis_gate = float(nis_gate)
-        self.transform = None if transform is None else np.asarray(transform, dtype=np.float32)
+        self.hw = self.h * self.w
         self.max_chunk = int(max_chunk)
-        emit_debug = bool(emit_debug or emit_metrics)
-        self.emit_debug = emit_debug
-        self.emit_metrics = bool(emit_metrics)
-        # pairing rule of the sharded runs (dist.handoff_period): with the metrics' debug outputs a reset frame's numbers
-        # depend on the incoming state (raw_on_reset below), so no chunk but frame 0's starts clean
-        self.handoff_period = 0 if self.emit_metrics else self.reset_period
-
         g = self.graph = Graph()
-        g.conv_operands = conv_operands
-        if torch.cuda.is_available():
+        if torch.cuda.is_available():      # the LDS a workgroup may use steers Network.conv's routes
             import ctypes as C
             lds = C.c_int(0)
             dev_index = torch.device(device).index
@@ -62,8 +57,129 @@ class KFNetEngine(object):
             if not hasattr(g, key):
                 raise ValueError('unknown Graph option %r' % key)
             setattr(g, key, val)
-        spec = KFNetDataSpec(batch_size=self.B, image_size=image_size)
         self.images = g.placeholder((self.B, self.H, self.W, 3), 'u8', name='images')
+        return g
+
+    def _chunk_tensor(self, C, name, slack=0):
+        return self.graph.tensor((self.max_chunk + slack, self.h, self.w, C), name=name)
+
+    def _chunk_buffer(self, t, name):
+        """The [max_chunk + B, h, w, C] buffer the batch output `t` is WRITTEN IN PLACE into: the launches that produce a
+        batch's `t` write straight into frame slots [d0, d0 + B) of it (Tensor.slide before every batch), so nothing is copied
+        between the heavy phase and the scan.  B frames of slack behind slot max_chunk: a partial batch still addresses B
+        slots, and the hipGraph-replay mode (pointers fixed at capture) parks its batch there."""
+        if t.base is not None or t.ld != t.C or t.ch_off != 0:
+            raise _lib.KfnError('%r is not a dense root tensor: cannot be produced in place' % t.name)
+        c = self._chunk_tensor(t.C, name, slack=self.B)
+        t.rebind(c.storage, 0, t.C)
+        return c
+
+    def _long_ring(self):
+        """The flow-feature ring is LONG: [max_chunk + B + 1] maps instead of [B + 1].  Batch k's maps are written behind
+        batch k-1's, so "the previous frame's map" is simply the slot before -- the hand-over copy of the last map to slot 0
+        happens once per chunk (_ring_handover, at the start of heavy()), not once per batch."""
+        from .graph import Storage
+        ring = self.net.temp_feat_maps
+        store = Storage((self.max_chunk + self.B + 1) * self.hw * ring.C, ring.dtype)
+        self.graph.storages.append(store)
+        ring.rebind(store, 0, ring.C)
+        self._ring_pos = 0          # ring slot that holds the map of the frame before the next batch
+
+    def _finish(self, weights, device):
+        g = self.graph
+        if self.c_rec is None:
+            self.c_rec = self._chunk_tensor(self.record_channels, 'chunk_records')
+        g.finalize(device)
+        g.load_weights(weights, strict=True)     # the graph's scopes only: other keys are ignored, a missing one raises
+        self.lib = _lib.load()
+        self.device = g.device
+
+    # ------------------------------------------------------------------------------
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def upload_frames(self, frames):
+        """uint8 [T,H,W,3] host array -> device tensor (H2D once; the timed region of
+        bench.py starts with frames resident in HBM)."""
+        frames = np.ascontiguousarray(frames)
+        assert frames.dtype == np.uint8 and frames.shape[1:] == (self.H, self.W, 3)
+        return self.torch.from_numpy(frames).to(self.device)
+
+    def _set_batch_images(self, dev_frames, start, count, stream):
+        """Copy `count` frames starting at `start` into the batch input."""
+        fb = self.H * self.W * 3
+        _lib.check(self.lib.kfn_memcpy_d2d(self.images.ptr, dev_frames.data_ptr() + start * fb, count * fb, stream),
+                   'memcpy images')
+
+    def _chunk_frames(self, dev_frames, T, dst0):
+        """The number of frames heavy() stages at slots dst0.. of the chunk buffers."""
+        T = int(dev_frames.shape[0]) if T is None else int(T)
+        if dst0 + T > self.max_chunk:
+            raise ValueError('chunk of %d frames (at slot %d) exceeds max_chunk=%d' % (T, dst0, self.max_chunk))
+        return T
+
+    def prime(self, dev_prev_frame):
+        """Compute the flow features of the frame preceding this chunk and park them in
+        ring slot 1 (multi-GPU: rank r recomputes them from the image -- 5.6 GFLOP --
+        instead of receiving 614 KB from rank r-1)."""
+        stream = self._stream()
+        fb = self.H * self.W * 3
+        _lib.check(self.lib.kfn_memcpy_d2d(self.images.ptr, dev_prev_frame.data_ptr(), fb, stream), 'prime')
+        self.net.temp_feat_maps.slide(0)
+        self.graph.run(stream, self.tower_ops, active=(1, self.B))   # one frame only -> ring slot 1
+        self._ring_pos = 1
+
+    def _ring_handover(self, stream):
+        """Once per chunk: the map of the frame before this chunk (the last slot written, or prime()'s) -> ring slot 0."""
+        if self._ring_pos != 0:
+            ring = self.net.temp_feat_maps
+            nbytes = self.hw * ring.C * 4
+            ring.slide(0)
+            _lib.check(self.lib.kfn_memcpy_d2d(ring.ptr, ring.ptr + self._ring_pos * nbytes, nbytes, stream), 'ring hand-over')
+            self._ring_pos = 0
+
+    def process(self, dev_frames, t0=0):
+        """heavy + scan; returns the device records tensor view [T,h,w,C] (torch; valid until the next call)."""
+        T = int(dev_frames.shape[0])
+        if T == 0:   # empty chunk: nothing to do, state untouched
+            return self.records(0)
+        self.heavy(dev_frames, T)
+        self.scan(T, t0)
+        return self.records(T)
+
+    def _view(self, c, T):
+        """Frames [0,T) of chunk buffer `c` as a torch view [T,h,w,C]."""
+        return c.root_storage.buf[:T * self.hw * c.C].view(T, self.h, self.w, c.C)
+
+    def records(self, T):
+        return self._view(self.c_rec, T)
+
+    def _host_views(self, T, **buffers):
+        return {key: self._view(c, T).cpu().numpy() for key, c in buffers.items()}
+
+    def get_state(self):
+        raise _lib.KfnError('%s has no recurrent state to hand between ranks' % type(self).__name__)
+
+    def flops_per_frame(self):
+        return sum(op.flops() for op in self.heavy_ops if hasattr(op, 'flops')) / self.B
+
+
+class KFNetEngine(_Engine):
+    def __init__(self, weights, image_size=(480, 640), batch=4, transform=None, reset_period=500,
+                 nis_gate=0.0, max_chunk=256, device='cuda:0', emit_debug=False, autotune=False,
+                 conv_operands='f32', use_graph=False, emit_metrics=False, graph_options=None):
+        g = self._build(image_size, batch, max_chunk, device, dict({'conv_operands': conv_operands}, **(graph_options or {})))
+        torch = self.torch
+        self.reset_period = int(reset_period)
+        self.nis_gate = float(nis_gate)
+        self.transform = None if transform is None else np.asarray(transform, dtype=np.float32)
+        emit_debug = bool(emit_debug or emit_metrics)
+        self.emit_debug = emit_debug
+        self.emit_metrics = bool(emit_metrics)
+        # pairing rule of the sharded runs (dist.handoff_period): with the metrics' debug outputs a reset frame's numbers
+        # depend on the incoming state (raw_on_reset below), so no chunk but frame 0's starts clean
+        self.handoff_period = 0 if self.emit_metrics else self.reset_period
+        spec = KFNetDataSpec(batch_size=self.B, image_size=image_size)
         self.state = g.placeholder((1, self.h, self.w, 4), name='last_state')
         last_coord = self.state.channels(0, 3, name='last_coord')
         last_unc = self.state.channels(3, 1, name='last_uncertainty')
@@ -74,49 +190,24 @@ class KFNetEngine(object):
         self.meas = self.net.GetMeasureCoord()[0].base          # [B,h,w,4]
         self.flow = self.net.prob.flow                           # [B*hw,1,1,2]
         self.sigma_t = self.net.oflownet.get_output_by_name('uncertainty')  # [B*hw,1,1,1]
-        # chunk-level scan buffers
-        hw = self.h * self.w
-        T = self.max_chunk
-        # The three per-frame scan inputs are WRITTEN IN PLACE: the launches that produce a batch's measurement / flow /
-        # sigma_trans write straight into frame slots [d0, d0 + B) of the chunk buffers (Tensor.slide before every batch),
-        # so nothing is copied between the heavy phase and the scan.  B frames of slack behind slot T: a partial batch
-        # still addresses B slots, and the hipGraph-replay mode (pointers fixed at capture) parks its batch there.
-        Ts = T + self.B
-        self.c_flow = g.tensor((Ts, self.h, self.w, 2), name='chunk_flow')
-        self.c_sigma = g.tensor((Ts, self.h, self.w, 1), name='chunk_sigma_trans')
-        self.c_meas = g.tensor((Ts, self.h, self.w, 4), name='chunk_meas')
-        for t, c in ((self.meas, self.c_meas), (self.flow, self.c_flow), (self.sigma_t, self.c_sigma)):
-            if t.base is not None or t.ld != t.C or t.ch_off != 0:
-                raise _lib.KfnError('scan input %r is not a dense root tensor: cannot be produced in place' % t.name)
-            t.rebind(c.storage, 0, t.C)
-        # ... and the flow-feature ring is LONG: [T + B + 1] maps instead of [B + 1].  Batch k's maps are written behind
-        # batch k-1's, so "the previous frame's map" is simply the slot before -- the per-batch hand-over copy of the last
-        # map to slot 0 happens once per chunk (at the start of heavy()), not once per batch.
-        ring = self.net.temp_feat_maps
-        self.ring_slots = T + self.B + 1
-        from .graph import Storage
-        ring_store = Storage(self.ring_slots * self.h * self.w * ring.C, ring.dtype)
-        g.storages.append(ring_store)
-        ring.rebind(ring_store, 0, ring.C)
-        self._ring_pos = 0          # ring slot that holds the map of the frame before the next batch
-        self.c_rec = g.tensor((T, self.h, self.w, 4), name='chunk_records')
-        self.c_temp = g.tensor((T, self.h, self.w, 4), name='chunk_temp') if emit_debug else None
-        self.c_nis = g.tensor((T, self.h, self.w, 3), name='chunk_nis') if emit_debug else None
+        # chunk-level scan buffers: the three per-frame scan inputs are written in place
+        self.c_flow = self._chunk_buffer(self.flow, 'chunk_flow')
+        self.c_sigma = self._chunk_buffer(self.sigma_t, 'chunk_sigma_trans')
+        self.c_meas = self._chunk_buffer(self.meas, 'chunk_meas')
+        self._long_ring()
+        self.tower_ops = [op for op in self.net.frame_ops if op in self.net.feat_tower.ops]
+        self.c_rec = self._chunk_tensor(4, 'chunk_records')
+        self.c_temp = self._chunk_tensor(4, 'chunk_temp') if emit_debug else None
+        self.c_nis = self._chunk_tensor(3, 'chunk_nis') if emit_debug else None
         # eval.py's log line needs the raw KF estimate and the graph's (not the host's) view of reset steps
-        self.c_kf = g.tensor((T, self.h, self.w, 4), name='chunk_kf_raw') if emit_metrics else None
+        self.c_kf = self._chunk_tensor(4, 'chunk_kf_raw') if emit_metrics else None
         self.chunk_scan = KalmanScanOp(self.c_flow, self.c_sigma, self.c_meas, self.state, self.c_rec,
                                        self.c_temp, self.c_nis, S=1, T=1, H=self.h, W=self.w,
                                        reset_period=self.reset_period, min_uncertainty=self.net.min_uncertainty,
                                        nis_gate=self.nis_gate, transform=self.transform, kf_raw=self.c_kf,
                                        raw_on_reset=emit_metrics)
-        g.finalize(device)
-        g.load_weights(weights)
-        self.lib = _lib.load()
-        self.device = g.device
-        self.hw = hw
+        self._finish(weights, device)
         self.heavy_ops = self.net.frame_ops + self.net.pair_ops
-        self.handover = self.net.scan_ops[1]
-        self._staging = None
         # Two-stream schedule of the heavy phase: the measurement tower (SCoordNet, MFMA-dense
         # big tiles) on the main stream, the flow-feature tower + OFlowNet (many small
         # launches that cannot fill the chip alone) on a side stream; they only share the
@@ -142,53 +233,16 @@ class KFNetEngine(object):
             self.tuned = g.autotune(self.heavy_ops)
             g.active = (1, 1)
 
-    # ------------------------------------------------------------------------------
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
-
-    def upload_frames(self, frames):
-        """uint8 [T,H,W,3] host array -> device tensor (H2D once; the timed region of
-        bench.py starts with frames resident in HBM)."""
-        frames = np.ascontiguousarray(frames)
-        assert frames.dtype == np.uint8 and frames.shape[1:] == (self.H, self.W, 3)
-        return self.torch.from_numpy(frames).to(self.device)
-
-    def _set_batch_images(self, dev_frames, start, count, stream):
-        """Copy `count` frames starting at `start` into the batch input (pad with the last)."""
-        fb = self.H * self.W * 3
-        dst = self.images.ptr
-        src = dev_frames.data_ptr() + start * fb
-        _lib.check(self.lib.kfn_memcpy_d2d(dst, src, count * fb, stream), 'memcpy images')
-
-    def prime(self, dev_prev_frame):
-        """Compute the flow features of the frame preceding this chunk and park them in
-        ring slot 0 (multi-GPU: rank r recomputes them from the image -- 5.6 GFLOP --
-        instead of receiving 614 KB from rank r-1)."""
-        stream = self._stream()
-        fb = self.H * self.W * 3
-        _lib.check(self.lib.kfn_memcpy_d2d(self.images.ptr, dev_prev_frame.data_ptr(), fb, stream), 'prime')
-        tower_ops = [op for op in self.net.frame_ops if op in self.net.feat_tower.ops]
-        ring = self.net.temp_feat_maps
-        ring.slide(0)
-        self.graph.run(stream, tower_ops, active=(1, self.B))   # one frame only -> ring slot 1
-        self._ring_pos = 1
-
     def heavy(self, dev_frames, T=None, dst0=0):
         """State-independent phase for frames [0,T) of `dev_frames` -> chunk scan buffers
         (frame t lands in slot dst0 + t)."""
-        T = dev_frames.shape[0] if T is None else T
-        if dst0 + T > self.max_chunk:
-            raise ValueError('chunk of %d frames (at slot %d) exceeds max_chunk=%d' % (T, dst0, self.max_chunk))
+        T = self._chunk_frames(dev_frames, T, dst0)
         stream = self._stream()
         lib = self.lib
         ring = self.net.temp_feat_maps
         hw = self.hw
         per_map = hw * ring.C
-        if self._ring_pos != 0:
-            # once per chunk: the map of the frame before this chunk (the last slot written, or prime()'s) -> slot 0
-            ring.slide(0)
-            _lib.check(lib.kfn_memcpy_d2d(ring.ptr, ring.ptr + self._ring_pos * per_map * 4, per_map * 4, stream), 'ring hand-over')
-            self._ring_pos = 0
+        self._ring_handover(stream)
         for s0 in range(0, T, self.B):
             cnt = min(self.B, T - s0)
             d0 = dst0 + s0
@@ -252,15 +306,6 @@ class KFNetEngine(object):
         self.chunk_scan.t0 = int(t0)
         self.chunk_scan.launch(self.lib, self._stream())
 
-    def process(self, dev_frames, t0=0):
-        """heavy + scan; returns the device records tensor view [T,h,w,4] (torch)."""
-        T = dev_frames.shape[0]
-        if T == 0:   # empty chunk: nothing to do, state untouched
-            return self.records(0)
-        self.heavy(dev_frames, T)
-        self.scan(T, t0)
-        return self.records(T)
-
     def process_sequences(self, dev_seqs):
         """Batch-of-sequences (BASELINE config 5): `dev_seqs` is a uint8 device tensor
         [S,T,H,W,3] of S independent sequences.  The heavy phase runs sequence after
@@ -302,25 +347,13 @@ class KFNetEngine(object):
                                        scratch.data_ptr() if scratch is not None else None, stream), 'kfn_kalman_scan')
         return rec.view(S, T, self.h, self.w, 4)
 
-    def records(self, T):
-        buf = self.c_rec.root_storage.buf
-        return buf[:T * self.hw * 4].view(T, self.h, self.w, 4)
-
     def debug(self, T):
-        out = {}
-        if self.c_temp is not None:
-            out['temp'] = self.c_temp.root_storage.buf[:T * self.hw * 4].view(T, self.h, self.w, 4).cpu().numpy()
-            out['nis'] = self.c_nis.root_storage.buf[:T * self.hw * 3].view(T, self.h, self.w, 3).cpu().numpy()
-        out['flow'] = self.c_flow.root_storage.buf[:T * self.hw * 2].view(T, self.h, self.w, 2).cpu().numpy()
-        out['sigma_trans'] = self.c_sigma.root_storage.buf[:T * self.hw].view(T, self.h, self.w, 1).cpu().numpy()
-        out['meas'] = self.c_meas.root_storage.buf[:T * self.hw * 4].view(T, self.h, self.w, 4).cpu().numpy()
+        out = self._host_views(T, temp=self.c_temp, nis=self.c_nis) if self.c_temp is not None else {}
+        out.update(self._host_views(T, flow=self.c_flow, sigma_trans=self.c_sigma, meas=self.c_meas))
         return out
 
     def get_state(self):
         return self.state.root_storage.buf  # torch [hw*4] (x,y,z,sigma), the message rank->rank
-
-    def flops_per_frame(self):
-        return sum(op.flops() for op in self.heavy_ops if hasattr(op, 'flops')) / self.B
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -358,99 +391,23 @@ def check_weights(W, names):
             raise KeyError('weight %s missing from the container' % name)
 
 
-class _SingleNetEngine(object):
-    record_channels = 4
-
-    def _build(self, tower, image_size, batch, max_chunk, device, graph_options):
-        import torch
-        self.torch = torch
-        self.B = int(batch)
-        self.H, self.W = image_size
-        self.h, self.w = grid_size(image_size)
-        self.hw = self.h * self.w
-        self.max_chunk = int(max_chunk)
-        g = self.graph = Graph()
-        if torch.cuda.is_available():      # the LDS a workgroup may use steers Network.conv's routes (as in KFNetEngine)
-            import ctypes as C
-            lds = C.c_int(0)
-            dev_index = torch.device(device).index
-            _lib.check(_lib.load().kfn_device_info(torch.cuda.current_device() if dev_index is None else dev_index,
-                                                   None, C.byref(lds), None, 0), 'kfn_device_info')
-            if lds.value > 0:
-                g.lds_bytes_per_cu = int(lds.value)
-        for key, val in (graph_options or {}).items():
-            if not hasattr(g, key):
-                raise ValueError('unknown Graph option %r' % key)
-            setattr(g, key, val)
-        self.images = g.placeholder((self.B, self.H, self.W, 3), 'u8', name='images')
-        self.net = _single_network(g, self.images, KFNetDataSpec(batch_size=self.B, image_size=image_size), tower)
-        return g
-
-    def _finish(self, weights, device):
-        g = self.graph
-        self.c_rec = g.tensor((self.max_chunk, self.h, self.w, self.record_channels), name='chunk_records')
-        g.finalize(device)
-        g.load_weights(weights, strict=True)     # this network's scope only: other keys are ignored, a missing one raises
-        self.lib = _lib.load()
-        self.device = g.device
-
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
-
-    def _chunk_buffer(self, t, C, name):
-        """[max_chunk + B, h, w, C] buffer the batch output `t` is produced into in place (slid per batch, as in
-        KFNetEngine: a partial batch still addresses B slots)."""
-        if t.base is not None or t.ld != t.C or t.ch_off != 0:
-            raise _lib.KfnError('%r is not a dense root tensor: cannot be produced in place' % t.name)
-        c = self.graph.tensor((self.max_chunk + self.B, self.h, self.w, C), name=name)
-        t.rebind(c.storage, 0, t.C)
-        return c
-
-    def upload_frames(self, frames):
-        """uint8 [T,H,W,3] host array -> device tensor."""
-        frames = np.ascontiguousarray(frames)
-        assert frames.dtype == np.uint8 and frames.shape[1:] == (self.H, self.W, 3)
-        return self.torch.from_numpy(frames).to(self.device)
-
-    def _set_batch_images(self, dev_frames, start, count, stream):
-        fb = self.H * self.W * 3
-        _lib.check(self.lib.kfn_memcpy_d2d(self.images.ptr, dev_frames.data_ptr() + start * fb, count * fb, stream),
-                   'memcpy images')
-
-    def process(self, dev_frames, t0=0):
-        """heavy + records; returns the device records view [T,h,w,C] (valid until the next call)."""
-        T = int(dev_frames.shape[0])
-        if T == 0:
-            return self.records(0)
-        self.heavy(dev_frames, T)
-        self.scan(T, t0)
-        return self.records(T)
-
-    def records(self, T):
-        C = self.record_channels
-        return self.c_rec.root_storage.buf[:T * self.hw * C].view(T, self.h, self.w, C)
-
-    def get_state(self):
-        raise _lib.KfnError('%s has no recurrent state to hand between ranks' % type(self).__name__)
-
-
-class SCoordNetEngine(_SingleNetEngine):
+class SCoordNetEngine(_Engine):
     """SCoordNet alone: per frame the measurement (x, y, z, sigma) and its record (T.x, 1/sigma) -- bit for bit the record
     KFNetEngine emits on a reset frame.  Frames are independent: `reset_period` = 1 tells dist.run_chunk that no chunk
     needs its predecessor (nothing to prime, nothing to hand over)."""
     reset_period = 1
-    record_channels = 4
 
     def __init__(self, weights, image_size=(480, 640), batch=4, transform=None, max_chunk=256, device='cuda:0',
                  emit_metrics=False, graph_options=None):
-        g = self._build('scoordnet', image_size, batch, max_chunk, device, graph_options)
+        g = self._build(image_size, batch, max_chunk, device, graph_options)
+        self.net = _single_network(g, self.images, KFNetDataSpec(batch_size=self.B, image_size=image_size), 'scoordnet')
         self.transform = None if transform is None else np.asarray(transform, dtype=np.float32)
         self.emit_metrics = bool(emit_metrics)
         self.meas = self.net.GetMeasureCoord()[0].base                  # [B,h,w,4] (x, y, z, sigma)
-        self.c_meas = self._chunk_buffer(self.meas, 4, 'chunk_meas')
+        self.c_meas = self._chunk_buffer(self.meas, 'chunk_meas')
         # kfnet_amd.KFNet.metrics.DeviceMetrics reads the measurement in the meas / temp / KF roles, and an all-zero NIS
         self.c_temp = self.c_kf = self.c_meas if emit_metrics else None
-        self.c_nis = g.tensor((self.max_chunk, self.h, self.w, 3), name='chunk_nis') if emit_metrics else None
+        self.c_nis = self._chunk_tensor(3, 'chunk_nis') if emit_metrics else None
         self.heavy_ops = list(self.net.frame_ops)
         self._finish(weights, device)
         import ctypes as C
@@ -463,9 +420,7 @@ class SCoordNetEngine(_SingleNetEngine):
 
     def heavy(self, dev_frames, T=None, dst0=0):
         """SCoordNet for frames [0,T) of `dev_frames` -> measurement slots dst0 + t."""
-        T = int(dev_frames.shape[0]) if T is None else int(T)
-        if dst0 + T > self.max_chunk:
-            raise ValueError('chunk of %d frames (at slot %d) exceeds max_chunk=%d' % (T, dst0, self.max_chunk))
+        T = self._chunk_frames(dev_frames, T, dst0)
         stream = self._stream()
         for s0 in range(0, T, self.B):
             cnt = min(self.B, T - s0)
@@ -480,64 +435,38 @@ class SCoordNetEngine(_SingleNetEngine):
                                                   self._stream()), 'kfn_coord_records')
 
     def debug(self, T):
-        return {'meas': self.c_meas.root_storage.buf[:T * self.hw * 4].view(T, self.h, self.w, 4).cpu().numpy()}
-
-    def flops_per_frame(self):
-        return sum(op.flops() for op in self.heavy_ops if hasattr(op, 'flops')) / self.B
+        return self._host_views(T, meas=self.c_meas)
 
 
-class OFlowNetEngine(_SingleNetEngine):
+class OFlowNetEngine(_Engine):
     """The flow-feature tower + cost volume + OFlowNet + flow head alone: per frame t the flow (u, v) in grid cells and
     sigma_trans of the pair (t-1, t), as records (u, v, 1/sigma_trans).  Cell (r, c) of frame t comes from cell
-    (r + v, c + u) of frame t-1.  The long feature ring and the prime() hand-over are KFNetEngine's: the first pair of a
-    chunk uses the last frame of the previous chunk (or the frame prime() was given); the row of a sequence's first frame
-    has no predecessor and means nothing.  `reset_period` = 0: every chunk but the first needs the frame before it."""
+    (r + v, c + u) of frame t-1.  The first pair of a chunk uses the last frame of the previous chunk (or the frame prime()
+    was given); the row of a sequence's first frame has no predecessor and means nothing.  `reset_period` = 0: every chunk
+    but the first needs the frame before it."""
     reset_period = 0
     record_channels = 3
 
     def __init__(self, weights, image_size=(480, 640), batch=4, max_chunk=256, device='cuda:0', graph_options=None):
-        g = self._build('oflownet', image_size, batch, max_chunk, device, graph_options)
-        net = self.net
+        g = self._build(image_size, batch, max_chunk, device, graph_options)
+        net = self.net = _single_network(g, self.images, KFNetDataSpec(batch_size=self.B, image_size=image_size), 'oflownet')
         self.flow = net.prob.flow                                          # [B*hw,1,1,2]
         self.sigma_t = net.oflownet.get_output_by_name('uncertainty')      # [B*hw,1,1,1]
-        self.c_flow = self._chunk_buffer(self.flow, 2, 'chunk_flow')
-        self.c_sigma = self._chunk_buffer(self.sigma_t, 1, 'chunk_sigma_trans')
-        # the long ring of KFNetEngine: [max_chunk + B + 1] maps, batch k's behind batch k-1's
-        from .graph import Storage
-        ring = net.temp_feat_maps
-        self.ring_slots = self.max_chunk + self.B + 1
-        ring_store = Storage(self.ring_slots * self.hw * ring.C, ring.dtype)
-        g.storages.append(ring_store)
-        ring.rebind(ring_store, 0, ring.C)
-        self._ring_pos = 0
+        self.c_flow = self._chunk_buffer(self.flow, 'chunk_flow')
+        self.c_sigma = self._chunk_buffer(self.sigma_t, 'chunk_sigma_trans')
+        self._long_ring()
         self.tower_ops = list(net.frame_ops)
         self.heavy_ops = net.frame_ops + net.pair_ops
         self._finish(weights, device)
 
-    def prime(self, dev_prev_frame):
-        """Flow features of the frame preceding the next chunk -> ring slot 1 (as KFNetEngine.prime)."""
-        stream = self._stream()
-        fb = self.H * self.W * 3
-        _lib.check(self.lib.kfn_memcpy_d2d(self.images.ptr, dev_prev_frame.data_ptr(), fb, stream), 'prime')
-        self.net.temp_feat_maps.slide(0)
-        self.graph.run(stream, self.tower_ops, active=(1, self.B))
-        self._ring_pos = 1
-
     def heavy(self, dev_frames, T=None, dst0=0):
         """Tower + OFlowNet for frames [0,T) of `dev_frames` -> flow / sigma_trans slots dst0 + t."""
-        T = int(dev_frames.shape[0]) if T is None else int(T)
-        if dst0 + T > self.max_chunk:
-            raise ValueError('chunk of %d frames (at slot %d) exceeds max_chunk=%d' % (T, dst0, self.max_chunk))
+        T = self._chunk_frames(dev_frames, T, dst0)
         stream = self._stream()
         ring = self.net.temp_feat_maps
         hw = self.hw
         per_map = hw * ring.C
-        if self._ring_pos != 0:
-            # once per chunk: the map of the frame before this chunk -> slot 0
-            ring.slide(0)
-            _lib.check(self.lib.kfn_memcpy_d2d(ring.ptr, ring.ptr + self._ring_pos * per_map * 4, per_map * 4, stream),
-                       'ring hand-over')
-            self._ring_pos = 0
+        self._ring_handover(stream)
         for s0 in range(0, T, self.B):
             cnt = min(self.B, T - s0)
             d0 = dst0 + s0
@@ -555,8 +484,4 @@ class OFlowNetEngine(_SingleNetEngine):
                                                  self._stream()), 'kfn_flow_records')
 
     def debug(self, T):
-        return {'flow': self.c_flow.root_storage.buf[:T * self.hw * 2].view(T, self.h, self.w, 2).cpu().numpy(),
-                'sigma_trans': self.c_sigma.root_storage.buf[:T * self.hw].view(T, self.h, self.w, 1).cpu().numpy()}
-
-    def flops_per_frame(self):
-        return sum(op.flops() for op in self.heavy_ops if hasattr(op, 'flops')) / self.B
+        return self._host_views(T, flow=self.c_flow, sigma_trans=self.c_sigma)

@@ -1,5 +1,5 @@
 """-m gpu: the frame-sharded eval runs print and write what a single process does -- label metrics and camera poses
-included (kfnet_amd.KFNet.eval.ShardOutputs / report_sharded, kfnet_amd.modes.run_shard, dist.gather_frames).
+included (kfnet_amd.modes.ChunkOutputs / report_sharded / run_shard / run_shard_cyclic, dist.gather_frames).
 
 Every case runs the command line twice, one after the other: first as one process (the reference), then under
 torch.distributed.run with its ranks sharing this GPU over gloo.  Both poses and metrics are per frame and deterministic,
