@@ -618,6 +618,88 @@ int kfn_comm_rank(const kfn_comm* comm, int* rank, int* nranks);
 int kfn_send_state(kfn_comm* comm, int peer, const float* state /* [H,W,4] */, int H, int W, void* stream);
 int kfn_recv_state(kfn_comm* comm, int peer, float* state /* [H,W,4] */, int H, int W, void* stream);
 
+/* ---- training SCoordNet (added exports; the ABI number stays 12) ---------------------------------------------------
+ * Stage 1 of the reference's procedure, "Train SCoordNet": tf.train.AdamOptimizer(lr).minimize(loss + reg_loss)
+ * (KFNet/train.py:300-315) over the ScoreNet variables.  TensorFlow derives the backward graph; here it is the entry points
+ * below plus the EXISTING forward kernels: the input gradient of a stride-1 convolution is kfn_conv2d_nhwc on the kernel
+ * rotated by 180 degrees with its channel axes swapped, that of a stride-2 convolution of an even-sized image is the
+ * transposed convolution (kfn_conv_desc.transposed = 1) with the kernel as it is.  fp32 only.  DESIGN.md "Training".
+ *
+ * kfn_conv2d_grad_weights -- the gradient of tf.layers.conv2d (cnn_wrapper/network.py:116-135) with respect to its kernel
+ * and bias.  `desc` is the FORWARD convolution's descriptor (N, H, W, Cin, ldx of its input x; Cout; kh = kw = 3 or 1;
+ * stride 1 or 2; transposed = 0; fp32); desc.ldy is the pixel stride of dz, the gradient with respect to the convolution's
+ * output BEFORE its ReLU, [N,Ho,Wo,Cout].  Cin % 16 == 0, any Cout >= 1.
+ *   dw[kh][kw][ci][co] = sum_{n,y,x} x[n, y*s + kh - pad_t, x*s + kw - pad_l, ci] * dz[n, y, x, co]   (TF HWIO, dense)
+ *   db[co]             = sum_{n,y,x} dz[n, y, x, co]                                                   (db may be NULL)
+ * An implicit GEMM on v_mfma_f32_32x32x2_f32 whose reduction runs over the pixels, cut into runs of pixels whose partial
+ * results go to planes of `workspace` (kfn_conv2d_grad_weights_workspace_bytes) and are added in a fixed order by a second
+ * launch: no atomics, bit-identical from launch to launch, and the split depends on the shapes only. */
+int kfn_conv2d_grad_weights_workspace_bytes(const kfn_conv_desc* desc, size_t* bytes);
+int kfn_conv2d_grad_weights(const kfn_conv_desc* desc, const float* x, const float* dz, float* dw, float* db,
+                            float* workspace, void* stream);
+/* The same for SCoordNet.preprocess + conv1a (cnn_wrapper/SCoordNet.py:20-21,34-37) as kfn_first_conv_u8 evaluates them:
+ * img [N,H,W,3] uint8, dz [N,H,W,C1] dense, dw [27][C1] (HWIO flattened), db [C1] or NULL.  C1 = 16, 32, 48 or 64.  The
+ * layer has no input gradient. */
+int kfn_first_conv_u8_grad_weights_workspace_bytes(int N, int H, int W, int C1, size_t* bytes);
+int kfn_first_conv_u8_grad_weights(const uint8_t* img, int N, int H, int W, const float* dz, int C1, float* dw, float* db,
+                                   float* workspace, void* stream);
+/* Gradient of tf.nn.relu (cnn_wrapper/network.py:133), in place: dz[p][c] = y[p][c] > 0 ? dz[p][c] : 0 for P pixels of C
+ * channels with pixel strides ldy / ldz. */
+int kfn_relu_grad(const float* y, int ldy, float* dz, int ldz, long P, int C, void* stream);
+/* The weight matrices of a layer's launches from its TF HWIO master copy [kh][kw][Cin][Cout], on the device (what
+ * kfnet_amd.graph.pack_conv_kernel does on the host once; in training the weights change every step):
+ *   KFN_PACK_FORWARD        [cout_pad][kh*kw*Cin]            w_packed of kfn_conv2d_nhwc for the layer itself
+ *   KFN_PACK_INPUT_GRAD_S1  [cin_pad][kh*kw*cout16]          ... for its input gradient as a stride-1 convolution of dz
+ *                                                            [.., cout16] -> [.., Cin]: row ci, column (a, b, co) =
+ *                                                            w[kh-1-a][kw-1-b][ci][co]
+ *   KFN_PACK_INPUT_GRAD_S2  [cin_pad][kh*kw*cout16]          ... as the transposed convolution: w[a][b][ci][co]
+ * cout_pad / cin_pad = the count rounded up to a multiple of 32 (zero rows), cout16 = Cout rounded up to a multiple of
+ * 16 (zero columns: 'prediction' has 4 output channels, its dz lives in a 16-channel buffer whose other channels are 0).
+ * conv1a's forward matrix [27][C1] is the master copy itself.  kfn_pack_conv_weights_floats: the size of `out`. */
+#define KFN_PACK_FORWARD 0
+#define KFN_PACK_INPUT_GRAD_S1 1
+#define KFN_PACK_INPUT_GRAD_S2 2
+int kfn_pack_conv_weights_floats(int kh, int kw, int Cin, int Cout, int kind, size_t* floats);
+int kfn_pack_conv_weights(const float* w_hwio, int kh, int kw, int Cin, int Cout, int kind, float* out, void* stream);
+
+/* kfn_coord_loss_grad -- KFNet.MeasureCoordLoss restricted to the measurement term (KFNet/KFNet.py:234-254): the NLL of
+ * CoordLossWithUncertainty (:192-232) plus smooth_weight * SmoothLoss (:430-467), on the labels as KFNet/train.py:274-280
+ * prepares them, and the gradient with respect to the network's raw output.
+ *   pred    [B,h,w,ld_pred]  'prediction' before GetOutput's exp: (x, y, z, log sigma)
+ *   labels  [B,h*label_stride,w*label_stride,4] = (gt xyz, mask); cell (r, c) reads pixel (label_stride*r, label_stride*c)
+ *           (tf.image.resize_nearest_neighbor); mask = (mask == 1); gt = transform [gt; 1] when has_transform
+ *   img     [B,h*img_stride,w*img_stride,3] uint8, read the same way (the smoothness weights); NULL iff smooth_weight == 0
+ *   sigma = exp(ch3), u = max(sigma, min_uncertainty), d = sum_c (x_c - gt_c)^2, l = 3 log u + d / (2 u^2),
+ *   l = min(l, loss_clip) when has_loss_clip (KFNet.py:217 clips at -2.0), valid = sum(mask) + 1
+ *   stats[8] = (L_nll = sum(mask l) / valid, L_smooth, accuracy = (valid - #{mask d > dist_threshold^2}) / valid, valid,
+ *               L = L_nll + smooth_weight L_smooth, 0, 0, 0)
+ *   dpred   [B,h,w,ld_dpred]: channels 0..3 = dL/dpred (through exp and the max gate; 0 where the clip is active); the
+ *           other channels of a wider buffer are not written.
+ * One workgroup; per-pixel terms in unfused fp32, their sums in fp64 over a fixed tree. */
+typedef struct kfn_coord_loss_desc {
+  int32_t struct_size;      /* = sizeof(kfn_coord_loss_desc) */
+  int32_t B, h, w;
+  int32_t ld_pred, ld_dpred;
+  int32_t label_stride, img_stride;
+  int32_t has_transform;
+  float transform[12];      /* first 3 rows of transform.txt, row-major */
+  int32_t has_loss_clip;
+  float loss_clip;
+  float smooth_weight;      /* 50 */
+  float dist_threshold;     /* 0.05 */
+  float min_uncertainty;    /* 1e-5 */
+} kfn_coord_loss_desc;
+int kfn_coord_loss_grad(const kfn_coord_loss_desc* desc, const float* pred, const float* labels, const uint8_t* img,
+                        float* dpred, float* stats, void* stream);
+
+/* kfn_adam_step -- tf.train.AdamOptimizer's update of one variable (or one flat buffer) of n floats, the caller passing
+ * lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), t counting from 1:
+ *   g' = g + weight_decay * w  (the gradient of l2_regularizer(weight_decay), KFNet/train.py:301-303)
+ *   m <- beta1 m + (1 - beta1) g',  v <- beta2 v + (1 - beta2) g'^2,  w <- w - lr_t m / (sqrt(v) + epsilon)
+ * evaluated in fp64 from the fp32 variables, each stored value rounded once. */
+int kfn_adam_step(float* w, float* m, float* v, const float* g, long n, double lr_t, double beta1, double beta2,
+                  double epsilon, double weight_decay, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

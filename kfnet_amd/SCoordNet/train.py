@@ -1,0 +1,146 @@
+"""Stage 1 of the reference README's "Training": train SCoordNet on one scene.
+
+    python -m kfnet_amd.SCoordNet.train --input_folder I --model_folder M --scene S
+
+I holds image_list.txt, label_list.txt (one [H,W,4] float32 label per image: scene coordinates and mask) and transform.txt.
+Snapshots go to M as kfnet_weights-<step>.npz (the ScoreNet/* variables: `python -m kfnet_amd.SCoordNet.eval --model_folder
+M` reads it as it is) and kfnet_train_state-<step>.npz (Adam slots and counters).  A run resumes from the newest snapshot
+in M -- a TF checkpoint or an .npz, with or without a state file -- and starts from an untrained graph's values otherwise.
+
+The flags --base_lr --max_steps --display --stepvalue --snapshot --gamma --weight_decay --shuffle --reset_step --gpu are the
+reference's (KFNet/train.py:14-47); stepvalue and max_steps = 5 * stepvalue follow the scene (set_stepvalue) unless given.
+--loss_clip is off by default: the snapshot's clip at -2.0 (KFNet/KFNet.py:217) zeroes every gradient of an untrained
+network; `--loss_clip -2` reproduces it.  `--synthetic N` trains on N seeded synthetic frames and labels.
+"""
+import argparse
+import os
+import sys
+import time
+from datetime import datetime
+
+import numpy as np
+
+from .. import modes
+
+STEPVALUE = {'chess': 100000, 'fire': 30000, 'heads': 60000, 'office': 100000, 'pumpkin': 100000, 'redkitchen': 100000,
+             'stairs': 100000}          # KFNet/train.py:330-344
+FORMAT = ('[%s] epoch %d, step %d/%d, loss=%.3f, l_measure=%.3f, l_smooth=%.3f, a_measure=%.3f, #pixels=%d, lr = %.6f '
+          '(%.3f sec/step)')
+
+
+def format_line(now, epoch, step, max_steps, s, duration):
+    """KFNet/train.py:427-432 reduced to the measurement fields."""
+    return FORMAT % (now, epoch, step, max_steps, s['loss'], s['l_measure'], s['l_smooth'], s['a_measure'], s['pixels'],
+                     s['lr'], duration)
+
+
+def schedule(scene, stepvalue=None, max_steps=None):
+    """(stepvalue, max_steps): set_stepvalue's per-scene values, explicit flags winning."""
+    sv = STEPVALUE[scene] if stepvalue is None else stepvalue
+    return sv, (5 * sv if max_steps is None else max_steps)
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--input_folder', default='')
+    ap.add_argument('--model_folder', default='')
+    ap.add_argument('--scene', default='')
+    ap.add_argument('--base_lr', type=float, default=1e-4)
+    ap.add_argument('--max_steps', type=int, default=None)
+    ap.add_argument('--display', type=int, default=10)
+    ap.add_argument('--stepvalue', type=int, default=None)
+    ap.add_argument('--snapshot', type=int, default=5000)
+    ap.add_argument('--gamma', type=float, default=0.5)
+    ap.add_argument('--weight_decay', type=float, default=1e-4)
+    ap.add_argument('--shuffle', action='store_true')
+    ap.add_argument('--reset_step', type=int, default=-1)
+    ap.add_argument('--gpu', type=int, default=0)
+    ap.add_argument('--batch', type=int, default=4)
+    ap.add_argument('--height', type=int, default=480)
+    ap.add_argument('--width', type=int, default=640)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--loss_clip', type=float, default=None)
+    ap.add_argument('--smooth_weight', type=float, default=50.0)
+    ap.add_argument('--synthetic', type=int, default=0, help='train on this many seeded synthetic frames and labels')
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    if a.scene not in modes.SCENES:
+        print('Invalid scene:', a.scene)
+        return 1
+    if not a.model_folder:
+        print('--model_folder is required: the snapshots go there', file=sys.stderr)
+        return 1
+    if a.height % 8 or a.width % 8 or a.height <= 0 or a.width <= 0:
+        print('--height and --width must be multiples of 8', file=sys.stderr)
+        return 1
+    if a.display < 1 or a.snapshot < 1 or a.batch < 1:
+        print('--display, --snapshot and --batch must be >= 1', file=sys.stderr)
+        return 1
+    size, grid = (a.height, a.width), (a.height // 8, a.width // 8)
+    stepvalue, max_steps = schedule(a.scene, a.stepvalue, a.max_steps)
+    from ..train import SCoordNetTrainer, batch_indices, restore, synthetic_labels
+    if a.synthetic > 0:
+        from ..synth import synthetic_sequence, synthetic_transform
+        count = a.synthetic
+        all_frames = synthetic_sequence(count, a.height, a.width)
+        all_labels = synthetic_labels(count, grid)
+        transform = synthetic_transform()
+
+        def batch_of(idx):
+            return all_frames[idx], all_labels[idx]
+    else:
+        try:
+            paths, label_paths = modes.read_inputs(a.input_folder)
+            if label_paths is None:
+                raise ValueError('%s has no label_list.txt: training needs labels' % a.input_folder)
+            transform = np.loadtxt(os.path.join(a.input_folder, 'transform.txt'), dtype=np.float32)
+        except (OSError, ValueError) as e:
+            print(e, file=sys.stderr)
+            return 1
+        count = len(paths)
+        from ..KFNet.metrics import read_label_grid
+
+        def batch_of(idx):
+            frames = modes.load_images([paths[i] for i in idx], size)
+            return frames, np.stack([read_label_grid(label_paths[i], size, grid) for i in idx])
+
+    W, state, step = restore(a.model_folder)
+    if W is None:
+        from ..weights import initial_weights
+        W = initial_weights(a.seed)
+        print('no snapshot in %s: starting from untrained weights (seed %d)' % (a.model_folder, a.seed))
+    import torch
+    torch.cuda.set_device(a.gpu)
+    tr = SCoordNetTrainer(W, image_size=size, batch=a.batch, transform=transform, base_lr=a.base_lr, gamma=a.gamma,
+                          stepvalue=stepvalue, weight_decay=a.weight_decay, loss_clip=a.loss_clip,
+                          smooth_weight=a.smooth_weight, device='cuda:%d' % a.gpu)
+    if state is not None:
+        tr.load_state(state)
+    tr.global_step = step if a.reset_step < 0 else a.reset_step
+    print('----------------------------------')
+    print('scene: ', a.scene)
+    print('training image number: ', count)
+    print('batch size: ', a.batch)
+    print('step value: ', stepvalue)
+    print('max steps: ', max_steps)
+    print('current step: ', tr.global_step)
+    print('----------------------------------')
+    while tr.global_step < max_steps:
+        t0 = time.time()
+        frames, labels = batch_of(batch_indices(tr.global_step, a.batch, count, a.shuffle, a.seed))
+        stats = tr.step(frames, labels)
+        s = tr.global_step
+        if s % a.display == 0 or s == max_steps:
+            line = dict(stats)           # the read-back waits for the step
+            print(format_line(datetime.now(), (s * a.batch) // count, s, max_steps, line, time.time() - t0), flush=True)
+        if s % a.snapshot == 0 or s == max_steps:
+            print('snapshot: %s, %s' % tr.save(a.model_folder, s), flush=True)
+    torch.cuda.synchronize()
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

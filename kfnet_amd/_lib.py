@@ -25,6 +25,7 @@ WINO_FORM_S2_EIGHT_WAVE = 4                                # ... for kfn_conv2d_
 WINO_FORM_S2_F42 = 5                                       # ... its polyphase + F(4,2) form (wino_s2c_kernel)
 PNP_OK, PNP_TOO_FEW_POINTS, PNP_NO_HYPOTHESIS = 0, 1, 2      # kfn_pnp_ransac info[:, 0] (KFN_PNP_*)
 PNP_MAX_HYPOTHESES = 1024
+PACK_FORWARD, PACK_INPUT_GRAD_S1, PACK_INPUT_GRAD_S2 = 0, 1, 2     # kfn_pack_conv_weights kind (KFN_PACK_*)
 CFG_AUTO, CFG_160x128, CFG_128x128, CFG_128x64, CFG_128x32, CFG_64x64, CFG_256x32, CFG_192x64 = 0, 1, 2, 3, 4, 5, 6, 7
 
 
@@ -65,6 +66,20 @@ class PnPDesc(C.Structure):
         super(PnPDesc, self).__init__(*args, **kw)
         if not self.struct_size:
             self.struct_size = C.sizeof(PnPDesc)
+
+
+class CoordLossDesc(C.Structure):
+    """kfn_coord_loss_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
+    _fields_ = [('struct_size', C.c_int32), ('B', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('ld_pred', C.c_int32),
+                ('ld_dpred', C.c_int32), ('label_stride', C.c_int32), ('img_stride', C.c_int32),
+                ('has_transform', C.c_int32), ('transform', C.c_float * 12), ('has_loss_clip', C.c_int32),
+                ('loss_clip', C.c_float), ('smooth_weight', C.c_float), ('dist_threshold', C.c_float),
+                ('min_uncertainty', C.c_float)]
+
+    def __init__(self, *args, **kw):
+        super(CoordLossDesc, self).__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(CoordLossDesc)
 
 
 # name -> (restype, argtypes); every symbol declared in include/kfnet_hip.h
@@ -143,6 +158,16 @@ SYMBOLS = {
     'kfn_comm_rank': (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     'kfn_send_state': (_i, [_vp, _i, _vp, _i, _i, _vp]),
     'kfn_recv_state': (_i, [_vp, _i, _vp, _i, _i, _vp]),
+    # training SCoordNet (added exports, ABI 12)
+    'kfn_conv2d_grad_weights_workspace_bytes': (_i, [C.POINTER(ConvDesc), C.POINTER(_sz)]),
+    'kfn_conv2d_grad_weights': (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
+    'kfn_first_conv_u8_grad_weights_workspace_bytes': (_i, [_i, _i, _i, _i, C.POINTER(_sz)]),
+    'kfn_first_conv_u8_grad_weights': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    'kfn_relu_grad': (_i, [_vp, _i, _vp, _i, C.c_long, _i, _vp]),
+    'kfn_pack_conv_weights_floats': (_i, [_i, _i, _i, _i, _i, C.POINTER(_sz)]),
+    'kfn_pack_conv_weights': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'kfn_coord_loss_grad': (_i, [C.POINTER(CoordLossDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
+    'kfn_adam_step': (_i, [_vp, _vp, _vp, _vp, C.c_long, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
 }
 
 _lib = None

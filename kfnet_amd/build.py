@@ -29,6 +29,8 @@ EXTRA = {
     'kfn_metrics.hip': ['-ffp-contract=off'],
     # ApplyTransform / bilinear_sampler as stand-alone launches: the same unfused arithmetic as inside the scan
     'kfn_util_ops.hip': ['-ffp-contract=off'],
+    # the training loss clips, thresholds and counts per-pixel terms, like the metrics kernel
+    'kfn_train_loss.hip': ['-ffp-contract=off'],
 }
 
 

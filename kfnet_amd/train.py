@@ -1,0 +1,399 @@
+"""Training SCoordNet on the device: stage 1 of the reference's procedure ("Train SCoordNet").
+
+The reference builds the TF-1 graph of KFNet/train.py:268-315 and lets tf.gradients / AdamOptimizer derive the rest.  Here
+one step is a fixed list of launches of libkfnet_hip.so (DESIGN.md "Training"):
+
+    forward      kfn_first_conv_u8, then kfn_conv2d_nhwc per layer (the direct route, fp32, every output kept)
+    loss         kfn_coord_loss_grad: NLL + smoothness on the prepared labels, and d(loss)/d(prediction)
+    backward     per layer, last to first: kfn_conv2d_grad_weights; the input gradient on the FORWARD kernel
+                 (stride 1: kfn_conv2d_nhwc with the rotated, channel-swapped pack; stride 2: its transposed form);
+                 kfn_relu_grad.  conv1a: kfn_first_conv_u8_grad_weights.
+    update       kfn_adam_step on the flat parameter buffer (TensorFlow's Adam, L2 regulariser folded in)
+    packs        kfn_pack_conv_weights: the forward and input-gradient matrices of the new weights
+
+Nothing travels through the host inside a step, and nothing is read back unless the caller asks (StepStats).  There is no
+fallback: a missing entry point or an unsupported shape raises.
+
+Definitions that are this module's own (the reference's SCoordNet training branch is not in the snapshot):
+`global_step` counts applied updates, the learning rate of update number global_step + 1 is base_lr * gamma ** (global_step /
+stepvalue), and Adam's t is the number of updates applied since the slots were zero, + 1.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib
+
+# cnn_wrapper/SCoordNet.py:21-32: (name, kernel, Cin, Cout, stride, relu)
+LAYERS = [('conv1a', 3, 3, 64, 1, True), ('conv1b', 3, 64, 64, 1, True), ('conv2a', 3, 64, 256, 2, True),
+          ('conv2b', 3, 256, 256, 1, True), ('conv3a', 3, 256, 512, 2, True), ('conv3b', 3, 512, 512, 1, True),
+          ('conv4a', 3, 512, 1024, 2, True), ('conv4b', 3, 1024, 1024, 1, True), ('conv5', 3, 1024, 512, 1, True),
+          ('conv6', 3, 512, 256, 1, True), ('conv7', 1, 256, 128, 1, True), ('prediction', 1, 128, 4, 1, False)]
+SCOPE = 'ScoreNet'
+BETA1, BETA2, EPSILON = 0.9, 0.999, 1e-8          # tf.train.AdamOptimizer defaults (KFNet/train.py:313)
+WEIGHTS_NAME = 'kfnet_weights-%d.npz'             # tools.io.get_snapshot's kind: SCoordNet.eval --model_folder reads it
+STATE_NAME = 'kfnet_train_state-%d.npz'           # NOT matched by get_snapshot's kfnet_weights*.npz
+
+
+def learning_rate(base_lr, gamma, stepvalue, global_step):
+    """tf.train.exponential_decay without staircase (KFNet/train.py:306-310): a real-valued exponent."""
+    return float(base_lr) * float(gamma) ** (float(global_step) / float(stepvalue))
+
+
+def adam_lr_t(lr, t):
+    """lr_t of TensorFlow's Adam for update number t (from 1)."""
+    return lr * np.sqrt(1.0 - BETA2 ** t) / (1.0 - BETA1 ** t)
+
+
+def batch_indices(step, batch, count, shuffle=False, seed=0):
+    """The frames of update number `step` (from 0): consecutive indices that wrap round; with `shuffle` position q of the
+    stream is entry q % count of a permutation drawn per epoch q // count from (seed, epoch).  A function of its arguments
+    alone, so a resumed run continues the same stream."""
+    out = []
+    perms = {}
+    for j in range(batch):
+        q = step * batch + j
+        if not shuffle:
+            out.append(q % count)
+            continue
+        e = q // count
+        if e not in perms:
+            perms[e] = np.random.default_rng([int(seed), int(e)]).permutation(count)
+        out.append(int(perms[e][q % count]))
+    return out
+
+
+def synthetic_labels(count, grid_hw, seed=3, start=0):
+    """Grid-sized label maps [count,h,w,4] of a seeded synthetic scene, for runs without data: a gently curved surface seen
+    from a camera that drifts with the frame index; the mask leaves out a border column and a moving block."""
+    h, w = grid_hw
+    rng = np.random.default_rng(seed)
+    a = rng.uniform(0.5, 1.5, size=6)
+    r, c = np.meshgrid(np.arange(h, dtype=np.float64) / h, np.arange(w, dtype=np.float64) / w, indexing='ij')
+    out = np.zeros((count, h, w, 4), dtype=np.float32)
+    for i in range(count):
+        t = 0.05 * (start + i)
+        out[i, ..., 0] = a[0] * c + t
+        out[i, ..., 1] = a[1] * r - 0.5 * t
+        out[i, ..., 2] = 1.5 + a[2] * np.sin(a[3] * c + t) * np.cos(a[4] * r)
+        m = np.ones((h, w), dtype=np.float32)
+        m[:, 0] = 0.0
+        b = (start + i) % max(w - 2, 1)
+        m[h // 2:h // 2 + 2, b:b + 2] = 0.0
+        out[i, ..., 3] = m
+    return out
+
+
+def snapshot_paths(folder, step):
+    return os.path.join(folder, WEIGHTS_NAME % step), os.path.join(folder, STATE_NAME % step)
+
+
+class StepStats(object):
+    """What a step reports, read from the device on first access (so that steps queue): loss, l_measure, l_smooth,
+    a_measure, pixels, lr.  dict(stats) gives plain floats."""
+    KEYS = ('loss', 'l_measure', 'l_smooth', 'a_measure', 'pixels', 'lr')
+
+    def __init__(self, stats_dev, lr):
+        self._dev, self._lr, self._host = stats_dev, lr, None
+
+    def keys(self):
+        return list(self.KEYS)
+
+    def __getitem__(self, k):
+        if self._host is None:
+            s = self._dev.cpu().numpy()
+            # kfn_coord_loss_grad's stats; valid = sum(mask) + 1, the reference logs np.sum(masks)
+            self._host = dict(loss=float(s[4]), l_measure=float(s[0]), l_smooth=float(s[1]), a_measure=float(s[2]),
+                              pixels=float(s[3]) - 1.0, lr=self._lr)
+        return self._host[k]
+
+
+class SCoordNetTrainer(object):
+    def __init__(self, weights, image_size=(480, 640), batch=4, transform=None, base_lr=1e-4, gamma=0.5, stepvalue=80000,
+                 weight_decay=1e-4, loss_clip=None, smooth_weight=50.0, device='cuda:0'):
+        """weights: {TF name: array} holding at least ScoreNet/*.  transform: the 4x4 of transform.txt ITSELF (labels are
+        mapped by it, KFNet/train.py:279-280), None = identity.  loss_clip: None (no clip) or the reference's -2.0."""
+        import torch
+        H, Wd = image_size
+        if H % 8 or Wd % 8 or H <= 0 or Wd <= 0:
+            raise ValueError('training needs an image size whose height and width are multiples of 8, got %dx%d' % (H, Wd))
+        if batch < 1:
+            raise ValueError('batch must be >= 1')
+        self.lib = _lib.load()
+        self.torch = torch
+        self.device = torch.device(device)
+        self.image_size, self.batch = (H, Wd), batch
+        self.grid = (H // 8, Wd // 8)
+        self.base_lr, self.gamma, self.stepvalue = float(base_lr), float(gamma), float(stepvalue)
+        self.weight_decay = float(weight_decay)
+        self.loss_clip = None if loss_clip is None else float(loss_clip)
+        self.smooth_weight = float(smooth_weight)
+        self.transform = None if transform is None else np.asarray(transform, dtype=np.float32).reshape(4, 4)
+        self.global_step = 0
+        self.adam_t = 0
+
+        # flat parameter buffer: kernel then bias per layer, TF HWIO order (every offset a multiple of 4 floats)
+        self.slots = {}
+        off = 0
+        for name, k, ci, co, _, _ in LAYERS:
+            for kind, shape in (('kernel', (k, k, ci, co)), ('bias', (co,))):
+                n = int(np.prod(shape))
+                self.slots['%s/%s/%s' % (SCOPE, name, kind)] = (off, n, shape)
+                off += -(-n // 4) * 4
+        self.num_floats = off
+        with torch.cuda.device(self.device):
+            f32 = dict(dtype=torch.float32, device=self.device)
+            self.params = torch.zeros(off, **f32)
+            self.grads = torch.zeros(off, **f32)
+            self.m = torch.zeros(off, **f32)
+            self.v = torch.zeros(off, **f32)
+            self.set_weights(weights)
+
+            # activations (each layer's output after its ReLU) and the gradients with respect to them
+            self.frames = torch.zeros((batch, H, Wd, 3), dtype=torch.uint8, device=self.device)
+            self.labels = None
+            self.shapes, self.act, self.dact, self.packs = [], [], [], []
+            h, w = H, Wd
+            ws_bytes = self._first_ws_bytes(batch, H, Wd, LAYERS[0][3])
+            for li, (name, k, ci, co, s, relu) in enumerate(LAYERS):
+                hin, win = h, w
+                h, w = -(-h // s), -(-w // s)
+                self.shapes.append((hin, win, h, w))
+                self.act.append(torch.zeros((batch, h, w, co), **f32))
+                self.dact.append(torch.zeros((batch, h, w, -(-co // 16) * 16), **f32))   # 'prediction': 4 of 16 channels
+                if li == 0:
+                    self.packs.append(None)
+                    continue
+                fwd = torch.zeros(self._pack_floats(k, ci, co, _lib.PACK_FORWARD), **f32)
+                kind = _lib.PACK_INPUT_GRAD_S2 if s == 2 else _lib.PACK_INPUT_GRAD_S1
+                back = torch.zeros(self._pack_floats(k, ci, co, kind), **f32)
+                self.packs.append((fwd, back, kind))
+                d = self._fwd_desc(li)
+                nbytes = C.c_size_t()
+                _lib.check(self.lib.kfn_conv2d_grad_weights_workspace_bytes(C.byref(d), C.byref(nbytes)),
+                           'kfn_conv2d_grad_weights_workspace_bytes[%s]' % name)
+                ws_bytes = max(ws_bytes, nbytes.value)
+            self.workspace = torch.zeros(-(-ws_bytes // 4), **f32)
+            self.stats = torch.zeros(8, **f32)
+            self._packs_stale = True
+
+    # ---- sizes and descriptors ------------------------------------------------------------------------------------
+    def _first_ws_bytes(self, n, h, w, c1):
+        nbytes = C.c_size_t()
+        _lib.check(self.lib.kfn_first_conv_u8_grad_weights_workspace_bytes(n, h, w, c1, C.byref(nbytes)),
+                   'kfn_first_conv_u8_grad_weights_workspace_bytes')
+        return nbytes.value
+
+    def _pack_floats(self, k, ci, co, kind):
+        n = C.c_size_t()
+        _lib.check(self.lib.kfn_pack_conv_weights_floats(k, k, ci, co, kind, C.byref(n)), 'kfn_pack_conv_weights_floats')
+        return n.value
+
+    def _fwd_desc(self, li):
+        """The forward convolution of layer li; as the weight gradient's descriptor its ldy is dZ's pixel stride."""
+        name, k, ci, co, s, relu = LAYERS[li]
+        hin, win, _, _ = self.shapes[li]
+        return _lib.ConvDesc(N=self.batch, H=hin, W=win, Cin=ci, ldx=ci, Cout=co, cout_pad=-(-co // 32) * 32, ldy=co,
+                             kh=k, kw=k, stride=s, transposed=0, relu=int(relu))
+
+    def _view(self, buf, name):
+        off, n, shape = self.slots[name]
+        return buf[off:off + n]
+
+    def _ptr(self, buf, name):
+        return buf.data_ptr() + 4 * self.slots[name][0]
+
+    # ---- weights and optimiser state ---------------------------------------------------------------------------------
+    def set_weights(self, weights):
+        torch = self.torch
+        for name, (off, n, shape) in self.slots.items():
+            if name not in weights:
+                raise KeyError('weights lack %s' % name)
+            a = np.ascontiguousarray(np.asarray(weights[name], dtype=np.float32))
+            if a.shape != tuple(shape):
+                raise ValueError('%s has shape %s, expected %s' % (name, a.shape, tuple(shape)))
+            self.params[off:off + n].copy_(torch.from_numpy(a.reshape(-1)))
+        self._packs_stale = True
+
+    def _named(self, buf, prefix=''):
+        host = buf.cpu().numpy()
+        return {prefix + name: host[off:off + n].reshape(shape).copy() for name, (off, n, shape) in self.slots.items()}
+
+    def weights(self):
+        """{TF variable name: float32 array}: what kfnet_amd.weights.save_npz stores and the engines load."""
+        return self._named(self.params)
+
+    def gradients(self):
+        """Debug view of the last step's gradients of the loss (without the regulariser, which kfn_adam_step adds), in TF
+        layout under the variables' names."""
+        return self._named(self.grads)
+
+    def state(self):
+        """The Adam slots and the counters, as numpy arrays (an .npz's content)."""
+        st = dict(global_step=np.int64(self.global_step), adam_t=np.int64(self.adam_t))
+        st.update(self._named(self.m, 'adam_m/'))
+        st.update(self._named(self.v, 'adam_v/'))
+        return st
+
+    def load_state(self, st):
+        torch = self.torch
+        for buf, prefix in ((self.m, 'adam_m/'), (self.v, 'adam_v/')):
+            for name, (off, n, shape) in self.slots.items():
+                a = np.ascontiguousarray(np.asarray(st[prefix + name], dtype=np.float32))
+                if a.shape != tuple(shape):
+                    raise ValueError('%s%s has shape %s, expected %s' % (prefix, name, a.shape, tuple(shape)))
+                buf[off:off + n].copy_(torch.from_numpy(a.reshape(-1)))
+        self.global_step = int(st['global_step'])
+        self.adam_t = int(st['adam_t'])
+
+    def save(self, folder, step=None):
+        """Writes kfnet_weights-<step>.npz (ScoreNet/* only) and kfnet_train_state-<step>.npz; returns the two paths."""
+        from .weights import save_npz
+        step = self.global_step if step is None else step
+        os.makedirs(folder, exist_ok=True)
+        wp, sp = snapshot_paths(folder, step)
+        save_npz(wp, self.weights())
+        np.savez(sp, **self.state())
+        return wp, sp
+
+    # ---- one step ----------------------------------------------------------------------------------------------------
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def _repack(self, stream):
+        for li, (name, k, ci, co, s, relu) in enumerate(LAYERS):
+            if li == 0:
+                continue          # conv1a's forward matrix [27][C] is the master copy
+            fwd, back, kind = self.packs[li]
+            w = self._ptr(self.params, '%s/%s/kernel' % (SCOPE, name))
+            _lib.check(self.lib.kfn_pack_conv_weights(w, k, k, ci, co, _lib.PACK_FORWARD, fwd.data_ptr(), stream),
+                       'kfn_pack_conv_weights[%s]' % name)
+            _lib.check(self.lib.kfn_pack_conv_weights(w, k, k, ci, co, kind, back.data_ptr(), stream),
+                       'kfn_pack_conv_weights[%s, input gradient]' % name)
+        self._packs_stale = False
+
+    def _upload(self, frames_u8, labels):
+        torch = self.torch
+        B, (H, Wd), (h, w) = self.batch, self.image_size, self.grid
+        fr = frames_u8 if torch.is_tensor(frames_u8) else torch.from_numpy(np.ascontiguousarray(frames_u8))
+        if tuple(fr.shape) != (B, H, Wd, 3) or fr.dtype != torch.uint8:
+            raise ValueError('frames must be uint8 [%d,%d,%d,3], got %s %s' % (B, H, Wd, fr.dtype, tuple(fr.shape)))
+        self.frames.copy_(fr, non_blocking=True)
+        lb = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.float32))
+        if tuple(lb.shape) == (B, H, Wd, 4):
+            stride = 8
+        elif tuple(lb.shape) == (B, h, w, 4):
+            stride = 1
+        else:
+            raise ValueError('labels must be float32 [%d,%d,%d,4] or grid-sized [%d,%d,%d,4], got %s'
+                             % (B, H, Wd, B, h, w, tuple(lb.shape)))
+        if self.labels is None or self.labels.shape != lb.shape:
+            self.labels = torch.zeros(tuple(lb.shape), dtype=torch.float32, device=self.device)
+        self.labels.copy_(lb.to(torch.float32), non_blocking=True)
+        return stride
+
+    def forward(self, stream=None):
+        """The forward pass on the uploaded frames; every layer's output stays in self.act."""
+        lib = self.lib
+        stream = self._stream() if stream is None else stream
+        if self._packs_stale:
+            self._repack(stream)
+        H, Wd = self.image_size
+        n0 = LAYERS[0][0]
+        _lib.check(lib.kfn_first_conv_u8(self.frames.data_ptr(), self.batch, H, Wd,
+                                         self._ptr(self.params, '%s/%s/kernel' % (SCOPE, n0)),
+                                         self._ptr(self.params, '%s/%s/bias' % (SCOPE, n0)), self.act[0].data_ptr(),
+                                         LAYERS[0][3], None, None, None, 0, stream), 'kfn_first_conv_u8')
+        for li in range(1, len(LAYERS)):
+            d = self._fwd_desc(li)
+            _lib.check(lib.kfn_conv2d_nhwc(C.byref(d), self.act[li - 1].data_ptr(), self.packs[li][0].data_ptr(),
+                                           self._ptr(self.params, '%s/%s/bias' % (SCOPE, LAYERS[li][0])),
+                                           self.act[li].data_ptr(), stream), 'kfn_conv2d_nhwc[%s]' % LAYERS[li][0])
+
+    def loss_and_gradients(self, label_stride, stream=None):
+        """Loss on self.act[-1], then the backward pass into self.grads."""
+        lib = self.lib
+        stream = self._stream() if stream is None else stream
+        B, (h, w) = self.batch, self.grid
+        last = len(LAYERS) - 1
+        d = _lib.CoordLossDesc(B=B, h=h, w=w, ld_pred=LAYERS[last][3], ld_dpred=self.dact[last].shape[3],
+                               label_stride=label_stride, img_stride=8, has_transform=int(self.transform is not None),
+                               has_loss_clip=int(self.loss_clip is not None), loss_clip=self.loss_clip or 0.0,
+                               smooth_weight=self.smooth_weight, dist_threshold=0.05, min_uncertainty=1e-5)
+        if self.transform is not None:
+            d.transform = (C.c_float * 12)(*[float(x) for x in self.transform[:3].reshape(-1)])
+        _lib.check(lib.kfn_coord_loss_grad(C.byref(d), self.act[last].data_ptr(), self.labels.data_ptr(),
+                                           self.frames.data_ptr(), self.dact[last].data_ptr(), self.stats.data_ptr(), stream),
+                   'kfn_coord_loss_grad')
+        for li in range(last, 0, -1):
+            name, k, ci, co, s, relu = LAYERS[li]
+            hin, win, ho, wo = self.shapes[li]
+            dz, ldz = self.dact[li], self.dact[li].shape[3]
+            gd = self._fwd_desc(li)
+            gd.ldy = ldz
+            _lib.check(lib.kfn_conv2d_grad_weights(C.byref(gd), self.act[li - 1].data_ptr(), dz.data_ptr(),
+                                                   self._ptr(self.grads, '%s/%s/kernel' % (SCOPE, name)),
+                                                   self._ptr(self.grads, '%s/%s/bias' % (SCOPE, name)),
+                                                   self.workspace.data_ptr(), stream), 'kfn_conv2d_grad_weights[%s]' % name)
+            # d/d(input): the forward kernel on dZ with the pack kfn_pack_conv_weights made for it
+            bd = _lib.ConvDesc(N=B, H=ho, W=wo, Cin=ldz, ldx=ldz, Cout=ci, cout_pad=-(-ci // 32) * 32, ldy=ci, kh=k, kw=k,
+                               stride=s, transposed=int(s == 2), relu=0)
+            _lib.check(lib.kfn_conv2d_nhwc(C.byref(bd), dz.data_ptr(), self.packs[li][1].data_ptr(), None,
+                                           self.dact[li - 1].data_ptr(), stream), 'kfn_conv2d_nhwc[%s, input gradient]' % name)
+            _lib.check(lib.kfn_relu_grad(self.act[li - 1].data_ptr(), ci, self.dact[li - 1].data_ptr(), ci,
+                                         B * hin * win, ci, stream), 'kfn_relu_grad[%s]' % LAYERS[li - 1][0])
+        n0, c1 = LAYERS[0][0], LAYERS[0][3]
+        H, Wd = self.image_size
+        _lib.check(lib.kfn_first_conv_u8_grad_weights(self.frames.data_ptr(), B, H, Wd, self.dact[0].data_ptr(), c1,
+                                                      self._ptr(self.grads, '%s/%s/kernel' % (SCOPE, n0)),
+                                                      self._ptr(self.grads, '%s/%s/bias' % (SCOPE, n0)),
+                                                      self.workspace.data_ptr(), stream), 'kfn_first_conv_u8_grad_weights')
+
+    def apply_gradients(self, stream=None):
+        """TensorFlow's Adam on the flat buffer, with the regulariser's weight_decay * w folded into the gradient."""
+        stream = self._stream() if stream is None else stream
+        lr = learning_rate(self.base_lr, self.gamma, self.stepvalue, self.global_step)
+        t = self.adam_t + 1
+        _lib.check(self.lib.kfn_adam_step(self.params.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.grads.data_ptr(),
+                                          self.num_floats, adam_lr_t(lr, t), BETA1, BETA2, EPSILON, self.weight_decay, stream),
+                   'kfn_adam_step')
+        self.adam_t = t
+        self.global_step += 1
+        self._packs_stale = True
+        return lr
+
+    def step(self, frames_u8, labels):
+        """One update on a batch: frames uint8 [B,H,W,3], labels float32 [B,H,W,4] or grid-sized [B,H/8,W/8,4] =
+        (gt xyz, mask).  Returns StepStats (loss, l_measure, l_smooth, a_measure, pixels, lr of THIS step's loss, before
+        the update), read back only when accessed."""
+        with self.torch.cuda.device(self.device):
+            stream = self._stream()
+            stride = self._upload(frames_u8, labels)
+            self.forward(stream)
+            self.loss_and_gradients(stride, stream)
+            stats = self.stats.clone()
+            lr = self.apply_gradients(stream)
+            self._repack(stream)
+        return StepStats(stats, lr)
+
+
+def restore(model_folder, verbose=True):
+    """The newest snapshot of a model folder for resuming: (weights or None, state or None, step).  The snapshot may be a TF
+    checkpoint or a kfnet_weights*.npz, with or without a kfnet_train_state-<step>.npz beside it."""
+    from .tools.io import get_snapshot
+    from .weights import load_snapshot
+    snapshot, step = get_snapshot(model_folder) if model_folder and os.path.isdir(model_folder) else (None, 0)
+    if snapshot is None:
+        return None, None, 0
+    W = load_snapshot(snapshot, scopes=(SCOPE,), verbose=verbose)
+    W = {k: v for k, v in W.items() if k.startswith(SCOPE + '/')}
+    sp = snapshot_paths(model_folder, step)[1]
+    state = None
+    if os.path.exists(sp):
+        with np.load(sp) as z:
+            state = {k: z[k] for k in z.files}
+    if verbose:
+        print('Adam slots restored from %s' % sp if state is not None else
+              'no %s: the Adam slots start at zero' % os.path.basename(sp))
+    return W, state, step

@@ -91,6 +91,23 @@ def synthetic_weights(seed=1234, init='he', bias_scale=0.05, flow_gain=8.0):
     return W
 
 
+def initial_weights(seed=0, scopes=('ScoreNet',)):
+    """What an untrained `tf.layers` graph holds for the variables under `scopes`: Glorot-uniform kernels (limit
+    sqrt(6 / (fan_in + fan_out)), fans from the variable shape), zero biases, no head scaling -- the starting point of
+    kfnet_amd.train.  Seeded; a variable's values depend on (seed, its position in variable_specs()) alone."""
+    W = {}
+    for i, (name, kind, shape) in enumerate(variable_specs()):
+        if name.split('/')[0] not in scopes:
+            continue
+        fan_in, fan_out = _fans(kind, shape)
+        lim = np.sqrt(6.0 / (fan_in + fan_out))
+        rng = np.random.default_rng([int(seed), i])
+        W[name + '/kernel'] = rng.uniform(-lim, lim, size=shape).astype(np.float32)
+        nb = shape[2] if kind == 'deconv' else shape[-1]
+        W[name + '/bias'] = np.zeros((nb,), dtype=np.float32)
+    return W
+
+
 def save_npz(path, W):
     np.savez(path, **W)
 

@@ -1,0 +1,97 @@
+"""Microbenchmark of the training step (DESIGN.md "Training"): ms per step of kfnet_amd.train.SCoordNetTrainer on synthetic
+frames and labels, the split of a step over its phases, and per layer the weight-gradient launch beside the forward direct
+launch as fractions of the fp32 MFMA peak.
+
+    python tools/mb_train.py [--height 480 --width 640 --batch 4 --steps 10 --warmup 3] [--layers]
+
+Under `rocprofv3 --kernel-trace --stats -- python tools/mb_train.py --steps 5` the kernel table gives the same split per
+kernel name (wgrad_mfma_kernel, conv_mfma_kernel, ...)."""
+import argparse
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+PEAK_FP32_MFMA = 157.3e12      # MI355X, v_mfma_f32_32x32x2_f32
+
+
+def timed(torch, fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fn()
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--height', type=int, default=480)
+    ap.add_argument('--width', type=int, default=640)
+    ap.add_argument('--batch', type=int, default=4)
+    ap.add_argument('--steps', type=int, default=10)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--layers', action='store_true', help='also time every layer\'s weight-gradient and forward launch')
+    a = ap.parse_args(argv)
+    import torch
+    from kfnet_amd import _lib
+    from kfnet_amd.synth import synthetic_sequence, synthetic_transform
+    from kfnet_amd.train import LAYERS, SCOPE, SCoordNetTrainer, synthetic_labels
+    from kfnet_amd.weights import initial_weights
+    size = (a.height, a.width)
+    tr = SCoordNetTrainer(initial_weights(0), image_size=size, batch=a.batch, transform=synthetic_transform())
+    frames = torch.from_numpy(synthetic_sequence(a.batch, a.height, a.width)).cuda()
+    labels = torch.from_numpy(synthetic_labels(a.batch, tr.grid)).cuda()
+    for _ in range(a.warmup):
+        tr.step(frames, labels)
+    ms = timed(torch, lambda: tr.step(frames, labels), a.steps)
+    print('%dx%d batch %d: %.2f ms per step (%.1f frames/s), %.1f M parameters' %
+          (a.height, a.width, a.batch, ms, 1e3 * a.batch / ms, tr.num_floats / 1e6))
+    stride = tr._upload(frames, labels)
+    fwd = timed(torch, tr.forward, a.steps)
+    bwd = timed(torch, lambda: tr.loss_and_gradients(stride), a.steps)
+    lib = tr.lib
+    stream = tr._stream()
+    adam = timed(torch, lambda: _lib.check(lib.kfn_adam_step(tr.params.data_ptr(), tr.m.data_ptr(), tr.v.data_ptr(),
+                                                             tr.grads.data_ptr(), tr.num_floats, 0.0, 0.9, 0.999, 1e-8, 0.0,
+                                                             stream), 'adam'), a.steps)
+    pack = timed(torch, lambda: tr._repack(stream), a.steps)
+    print('forward %.2f ms, loss + backward %.2f ms, adam %.2f ms, packs %.2f ms' % (fwd, bwd, adam, pack))
+    if not a.layers:
+        return 0
+    print('%-11s %10s %9s %7s | %10s %9s %7s' % ('layer', 'wgrad ms', 'TFLOP/s', 'peak', 'forward ms', 'TFLOP/s', 'peak'))
+    tot_w = tot_f = 0.0
+    for li in range(1, len(LAYERS)):
+        name, k, ci, co, s, relu = LAYERS[li]
+        hin, win, ho, wo = tr.shapes[li]
+        d = tr._fwd_desc(li)
+        gd = tr._fwd_desc(li)
+        gd.ldy = tr.dact[li].shape[3]
+        P = a.batch * ho * wo
+        # FLOPs the weight-gradient MFMAs execute: whole 128 x (64 | 128) tiles, the bias row included
+        bn = 64 if co <= 64 else 128
+        executed = 2.0 * P * (-(-(k * k * ci + 1) // 128) * 128) * (-(-co // bn) * bn)
+        nominal = 2.0 * P * k * k * ci * co
+        tw = timed(torch, lambda: _lib.check(lib.kfn_conv2d_grad_weights(
+            C.byref(gd), tr.act[li - 1].data_ptr(), tr.dact[li].data_ptr(), tr._ptr(tr.grads, '%s/%s/kernel' % (SCOPE, name)),
+            tr._ptr(tr.grads, '%s/%s/bias' % (SCOPE, name)), tr.workspace.data_ptr(), stream), 'wgrad'), a.steps)
+        tf = timed(torch, lambda: _lib.check(lib.kfn_conv2d_nhwc(
+            C.byref(d), tr.act[li - 1].data_ptr(), tr.packs[li][0].data_ptr(), tr._ptr(tr.params, '%s/%s/bias' % (SCOPE, name)),
+            tr.act[li].data_ptr(), stream), 'forward'), a.steps)
+        tot_w += tw
+        tot_f += tf
+        print('%-11s %10.3f %9.1f %6.1f%% | %10.3f %9.1f %6.1f%%' %
+              (name, tw, executed / tw / 1e9, 100 * executed / (tw * 1e-3) / PEAK_FP32_MFMA,
+               tf, nominal / tf / 1e9, 100 * nominal / (tf * 1e-3) / PEAK_FP32_MFMA))
+    print('weight gradients %.2f ms, forward convolutions %.2f ms (conv1a apart)' % (tot_w, tot_f))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
