@@ -46,8 +46,11 @@ extern "C" {
  * 9 (round 6): kfn_conv_desc.x_layout / y_layout (KFN_LAYOUT_C16).  10 (round 6): kfn_kalman_arith_probe.
  * 11: camera poses -- kfn_pnp_desc, kfn_pnp_scratch_bytes, kfn_pnp_ransac, kfn_pnp_hypotheses.
  * 12: kfn_coord_records, kfn_flow_records; later kfn_crc32c (reading TensorFlow checkpoints), an added export that leaves
- * every ABI-12 host working, so the number stays. */
-#define KFN_ABI_VERSION 12
+ * every ABI-12 host working, so the number stays.
+ * 13: the constants the reference squares in Python cross the boundary as doubles -- kfn_kalman_desc.min_uncertainty,
+ * kfn_coord_loss_desc.dist_threshold / min_uncertainty and the two thresholds of kfn_eval_metrics (layout and signature
+ * change: an ABI-12 host must be rebuilt). */
+#define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
 int kfn_abi_version(void);
@@ -446,7 +449,8 @@ typedef struct kfn_kalman_desc {
   int32_t S, T, H, W;
   int32_t t0;            /* global index of frame 0 of this call (reset phase) */
   int32_t reset_period;  /* eval.py: spec.sequence_length (500); <=0 = never reset */
-  float min_uncertainty; /* KFNet.min_uncertainty = 1e-5 */
+  double min_uncertainty; /* KFNet.min_uncertainty = 1e-5, as the Python double: the variance floor is the double product
+                            rounded once, float(1e-5 * 1e-5) = 0x2EDBE6FF (KFNet/KFNet.py:394,398), not 1e-5f * 1e-5f */
   float nis_gate;        /* 0 = off; eval.py --NIS uses 7.815 */
   int32_t has_transform; /* 0 = identity */
   float transform[12];   /* first 3 rows of inv(transform.txt), row-major */
@@ -485,11 +489,14 @@ int kfn_kalman_scan_ex(const kfn_kalman_desc* desc, const float* flow_xy, const 
  * stats [T,16]: [0..2] masked loss sums (measure, temporal, KF), [3..5] "inaccurate" pixel counts,
  * [6] valid_pixel = sum(mask_a) + sum(mask_b) + 1, [7] NIS values > 0, [8] of those inside (0.0157, 2.706);
  * loss = stats[k]/stats[6], accuracy = (stats[6] - stats[3+k])/stats[6].  dist_maps [T,3,H*W] in cm
- * (0 where masked); the host takes the medians of the positive entries. */
+ * (0 where masked); the host takes the medians of the positive entries.
+ * dist_threshold is the Python double 0.05: it is squared in double and the product rounded once to fp32, as TensorFlow
+ * does with `dist_threshold * dist_threshold` (KFNet.py:227) -- 0x3B23D70A; a caller that rounds 0.05 to float first gets
+ * 0x3B23D70B and a pixel exactly 0.05f away counted accurate.  min_uncertainty is compared as float(min_uncertainty). */
 int kfn_eval_metrics(const float* meas, const float* temp, const float* kf_raw, const float* records,
                      const float* nis, const float* labels, const int32_t* label_pair,
                      const uint8_t* reset_flags, const float* transform12 /* 3x4 row-major or NULL */,
-                     int T, int HW, float dist_threshold /* 0.05 */, float min_uncertainty /* 1e-5 */,
+                     int T, int HW, double dist_threshold /* 0.05 */, double min_uncertainty /* 1e-5 */,
                      float* stats, float* dist_maps, void* stream);
 
 /* KFNet.BuildKFCoord on its own (KFNet/KFNet.py:148-162) + optional KFNet.GetNIS
@@ -686,8 +693,8 @@ typedef struct kfn_coord_loss_desc {
   int32_t has_loss_clip;
   float loss_clip;
   float smooth_weight;      /* 50 */
-  float dist_threshold;     /* 0.05 */
-  float min_uncertainty;    /* 1e-5 */
+  double dist_threshold;    /* 0.05, the Python double: compared as float(dist_threshold * dist_threshold), one rounding */
+  double min_uncertainty;   /* 1e-5: u = max(sigma, float(min_uncertainty)) */
 } kfn_coord_loss_desc;
 int kfn_coord_loss_grad(const kfn_coord_loss_desc* desc, const float* pred, const float* labels, const uint8_t* img,
                         float* dpred, float* stats, void* stream);

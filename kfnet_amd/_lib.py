@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libkfnet_hip.so')
 
 KFN_OK = 0
-ABI_VERSION = 12
+ABI_VERSION = 13
 COMM_ID_BYTES = 128
 EPI_NONE, EPI_L2NORM, EPI_EXP_CH3, EPI_EXP_1E2 = 0, 1, 2, 3
 OPERAND_F32, OPERAND_F16, OPERAND_F16X3 = 0, 1, 2
@@ -51,7 +51,7 @@ class ConvDesc(C.Structure):
 class KalmanDesc(C.Structure):
     _fields_ = [('S', C.c_int32), ('T', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
                 ('t0', C.c_int32), ('reset_period', C.c_int32),
-                ('min_uncertainty', C.c_float), ('nis_gate', C.c_float),
+                ('min_uncertainty', C.c_double), ('nis_gate', C.c_float),
                 ('has_transform', C.c_int32), ('transform', C.c_float * 12)]
 
 
@@ -73,8 +73,8 @@ class CoordLossDesc(C.Structure):
     _fields_ = [('struct_size', C.c_int32), ('B', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('ld_pred', C.c_int32),
                 ('ld_dpred', C.c_int32), ('label_stride', C.c_int32), ('img_stride', C.c_int32),
                 ('has_transform', C.c_int32), ('transform', C.c_float * 12), ('has_loss_clip', C.c_int32),
-                ('loss_clip', C.c_float), ('smooth_weight', C.c_float), ('dist_threshold', C.c_float),
-                ('min_uncertainty', C.c_float)]
+                ('loss_clip', C.c_float), ('smooth_weight', C.c_float), ('dist_threshold', C.c_double),
+                ('min_uncertainty', C.c_double)]
 
     def __init__(self, *args, **kw):
         super(CoordLossDesc, self).__init__(*args, **kw)
@@ -136,7 +136,7 @@ SYMBOLS = {
     'kfn_kalman_scan_scratch_bytes': (_i, [C.POINTER(KalmanDesc), C.POINTER(_sz)]),
     'kfn_kalman_scan': (_i, [C.POINTER(KalmanDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'kfn_kalman_scan_ex': (_i, [C.POINTER(KalmanDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    'kfn_eval_metrics': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp]),
+    'kfn_eval_metrics': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
     'kfn_kalman_fuse': (_i, [_vp, _vp, _vp, _vp, C.c_long, _vp]),
     'kfn_kalman_arith_probe': (_i, [_vp, _vp, _vp, C.c_long, _vp]),
     'kfn_kalman_fuse2': (_i, [_vp, _vp, _vp, C.c_long, _vp]),

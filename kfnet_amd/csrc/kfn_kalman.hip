@@ -41,6 +41,7 @@ struct KalmanArgs {
   float* opt_nis;
   f32x4* opt_kf;      // raw (untransformed, ungated) KF estimate per frame, or null
   int raw_on_reset;   // debug outputs of a reset frame = what the reference GRAPH computes there
+  float eps2;         // the variance floor, float(min_uncertainty^2) formed in double by the launcher (floor_variance)
   kfn_kalman_desc d;
 };
 
@@ -237,7 +238,7 @@ __global__ __launch_bounds__(KT) void kalman_scan_kernel(KalmanArgs a) {
   const int tid = threadIdx.x;
   const int s = blockIdx.x;
   const int H = a.d.H, W = a.d.W, HW = H * W, T = a.d.T;
-  const float eps2 = a.d.min_uncertainty * a.d.min_uncertainty;
+  const float eps2 = a.eps2;
   const float xmax = (float)(W - 1), ymax = (float)(H - 1);
   const bool want_nis = (DBG && a.opt_nis != nullptr) || (a.d.nis_gate > 0.f);
 
@@ -366,7 +367,7 @@ __global__ __launch_bounds__(256) void kalman_step_kernel(KalmanArgs a, const f3
   in.z = a.meas[off + p];
   const int gi = a.d.t0 + t;
   const bool reset = a.d.reset_period > 0 && (gi % a.d.reset_period) == 0;
-  const float eps2 = a.d.min_uncertainty * a.d.min_uncertainty;
+  const float eps2 = a.eps2;
   const bool want_nis = (a.opt_nis != nullptr) || (a.d.nis_gate > 0.f);
   const int py = p / W, px = p - py * W;
   next[(size_t)s * HW + p] = fuse_pixel(a, prev + (size_t)s * HW, in, p, px, py, off, reset, W, (float)(W - 1),
@@ -463,6 +464,10 @@ constexpr bool SCAN_NT = true;      // non-temporal record stores and input load
 constexpr int FUSE_BLOCK = 256, FUSE_U = 4;
 constexpr bool FUSE_NT = true;
 
+// tf.maximum(variance, self.min_uncertainty * self.min_uncertainty) (KFNet/KFNet.py:394,398): the reference squares the Python
+// double and TensorFlow rounds the PRODUCT once to fp32 -- float(1e-5 * 1e-5) = 0x2EDBE6FF, one ulp above 1e-5f * 1e-5f.
+inline float floor_variance(double min_uncertainty) { return (float)(min_uncertainty * min_uncertainty); }
+
 template <int KT, int PPT, bool DBL, int D, bool NT, bool DBG, bool PTR = false, bool LEAN = true>
 int launch_scan_dbg(const KalmanArgs& a, hipStream_t stream) {
   const size_t smem = (size_t)a.d.H * a.d.W * sizeof(f32x4) * (DBL ? 2 : 1);
@@ -533,6 +538,7 @@ extern "C" int kfn_kalman_scan_ex(const kfn_kalman_desc* d, const float* flow_xy
   a.opt_nis = opt_nis;
   a.opt_kf = reinterpret_cast<f32x4*>(opt_kf);
   a.raw_on_reset = raw_on_reset;
+  a.eps2 = floor_variance(d->min_uncertainty);
   a.d = *d;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if ((size_t)HW * 16 > 160 * 1024) {

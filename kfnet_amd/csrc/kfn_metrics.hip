@@ -133,11 +133,12 @@ __global__ __launch_bounds__(MT) void eval_metrics_kernel(MetricArgs a) {
 extern "C" int kfn_eval_metrics(const float* meas, const float* temp, const float* kf_raw, const float* records,
                                 const float* nis, const float* labels, const int32_t* label_pair,
                                 const uint8_t* reset_flags, const float* transform12, int T, int HW,
-                                float dist_threshold, float min_uncertainty, float* stats, float* dist_maps,
+                                double dist_threshold, double min_uncertainty, float* stats, float* dist_maps,
                                 void* stream) {
   KFN_REQUIRE(meas && temp && kf_raw && records && nis && labels && label_pair && reset_flags && stats && dist_maps,
               "kfn_eval_metrics: null argument");
   KFN_REQUIRE(T > 0 && HW > 0, "kfn_eval_metrics: bad shape T=%d HW=%d", T, HW);
+  KFN_REQUIRE(dist_threshold >= 0.0 && min_uncertainty > 0.0, "kfn_eval_metrics: bad thresholds");
   KFN_REQUIRE(((reinterpret_cast<uintptr_t>(meas) | reinterpret_cast<uintptr_t>(temp) | reinterpret_cast<uintptr_t>(kf_raw) |
                 reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(labels)) & 15) == 0,
               "kfn_eval_metrics: misaligned buffer");
@@ -153,8 +154,11 @@ extern "C" int kfn_eval_metrics(const float* meas, const float* temp, const floa
   a.stats = stats;
   a.dist = dist_maps;
   a.T = T; a.HW = HW;
-  a.thr2 = (float)((double)dist_threshold * (double)dist_threshold);   // the reference squares in Python (double)
-  a.min_unc = min_uncertainty;
+  // `diff - dist_threshold * dist_threshold` (KFNet/KFNet.py:227): the reference squares the Python double 0.05 and TensorFlow
+  // rounds the product once to fp32 (0x3B23D70A); the threshold therefore arrives as a double -- squaring 0.05f, in float or in
+  // double, gives 0x3B23D70B
+  a.thr2 = (float)(dist_threshold * dist_threshold);
+  a.min_unc = (float)min_uncertainty;
   a.has_transform = transform12 != nullptr;
   for (int i = 0; i < 12; ++i) a.M[i] = transform12 ? transform12[i] : 0.f;
   hipLaunchKernelGGL(eval_metrics_kernel, dim3((unsigned)T), dim3(MT), 0, (hipStream_t)stream, a);

@@ -169,7 +169,7 @@ extern "C" int kfn_coord_loss_grad(const kfn_coord_loss_desc* d, const float* pr
   KFN_REQUIRE(d->label_stride >= 1 && d->img_stride >= 1, "kfn_coord_loss_grad: bad label_stride %d / img_stride %d",
               d->label_stride, d->img_stride);
   KFN_REQUIRE(d->smooth_weight == 0.0f || img, "kfn_coord_loss_grad: the smoothness term needs the frames");
-  KFN_REQUIRE(d->min_uncertainty > 0.0f && d->dist_threshold >= 0.0f, "kfn_coord_loss_grad: bad thresholds");
+  KFN_REQUIRE(d->min_uncertainty > 0.0 && d->dist_threshold >= 0.0, "kfn_coord_loss_grad: bad thresholds");
   LossArgs a;
   a.pred = pred; a.labels = labels; a.img = img; a.dpred = dpred; a.stats = stats;
   a.B = d->B; a.h = d->h; a.w = d->w; a.ld_pred = d->ld_pred; a.ld_dpred = d->ld_dpred;
@@ -177,7 +177,8 @@ extern "C" int kfn_coord_loss_grad(const kfn_coord_loss_desc* d, const float* pr
   a.has_M = d->has_transform; a.has_clip = d->has_loss_clip;
   for (int i = 0; i < 12; ++i) a.M[i] = d->transform[i];
   a.clip = d->loss_clip; a.smooth_weight = d->smooth_weight;
-  a.thr2 = d->dist_threshold * d->dist_threshold; a.min_unc = d->min_uncertainty;
+  // the reference squares the Python double and TensorFlow rounds the product once (KFNet/KFNet.py:227): 0x3B23D70A for 0.05
+  a.thr2 = (float)(d->dist_threshold * d->dist_threshold); a.min_unc = (float)d->min_uncertainty;
   hipLaunchKernelGGL(coord_loss_grad_kernel, dim3(1), dim3(LT), 0, reinterpret_cast<hipStream_t>(stream), a);
   KFN_LAUNCH_CHECK("coord_loss_grad_kernel");
   return KFN_OK;

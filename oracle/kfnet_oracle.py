@@ -280,7 +280,9 @@ def process_model(prob, sigma_trans, offsets, last_coord, last_unc):
     pixel_map = get_pixel_map(h, w, dt) + flow
     temp_coord = bilinear_sampler(last_coord, pixel_map)
     last_u = bilinear_sampler(last_unc, pixel_map)
-    eps2 = dt.type(MIN_UNCERTAINTY) * dt.type(MIN_UNCERTAINTY)
+    # tf.maximum(var, self.min_uncertainty * self.min_uncertainty): the product of two Python doubles, rounded ONCE to the graph's
+    # dtype (KFNet/KFNet.py:394,398) -- float32(1e-5 * 1e-5) = 0x2EDBE6FF, one ulp above float32(1e-5) * float32(1e-5)
+    eps2 = dt.type(MIN_UNCERTAINTY * MIN_UNCERTAINTY)
     last_var = np.maximum(last_u * last_u, eps2)
     st = sigma_trans.astype(dt).reshape(1, h, w, 1)
     trans_var = np.maximum(st * st, eps2)

@@ -192,7 +192,7 @@ def process_model(prob, sigma_trans, offsets, last_coord, last_unc):
     pm = np.stack([xs, ys], -1)[None] + flow
     tx = bilinear_sampler(last_coord, pm)
     lu = bilinear_sampler(last_unc, pm)
-    eps2 = np.float32(MIN_UNCERTAINTY) * np.float32(MIN_UNCERTAINTY)
+    eps2 = np.float32(MIN_UNCERTAINTY * MIN_UNCERTAINTY)      # the double product rounded once, as TensorFlow folds it
     lv = np.maximum(lu * lu, eps2)
     st = sigma_trans.reshape(1, h, w, 1).astype(np.float32)
     tv = np.maximum(st * st, eps2)

@@ -218,7 +218,7 @@ def _scan_ref(flow, sig, meas, state0, T4, t0, reset_period, nis_gate):
                 pm = O.get_pixel_map(H, W, np.float32) + flow[s, t][None]
                 tx = O.bilinear_sampler(sx, pm)
                 lu = O.bilinear_sampler(ss, pm)
-                eps2 = np.float32(1e-5) * np.float32(1e-5)
+                eps2 = np.float32(1e-5 * 1e-5)          # the reference's Python-double product, rounded once (0x2EDBE6FF)
                 ts = np.sqrt(np.maximum(sig[s, t][None] ** 2, eps2) + np.maximum(lu * lu, eps2))
                 kx, ks = O.build_kf_coord(tx, ts, z, sz)
                 nn = O.get_nis(z, sz, tx, ts)
@@ -287,6 +287,50 @@ def test_kalman_scan_vs_oracle(cfg):
     assert np.allclose(g_rec[..., 3], r_rec[..., 3], rtol=1e-5)
     if gate == 0.0:
         assert np.allclose(nis.cpu().numpy().reshape(r_nis.shape), r_nis, rtol=1e-4, atol=1e-6)
+
+
+@pytest.mark.parametrize('grid', [(17, 23), (101, 121)], ids=['scan-17x23', 'step-101x121'])
+def test_kalman_scan_variance_floor_is_the_double_product_rounded_once(grid):
+    """tf.maximum(var, self.min_uncertainty * self.min_uncertainty) (KFNet/KFNet.py:394,398): the floor is the product of two
+    Python doubles rounded once, float32(1e-5 * 1e-5) = 0x2EDBE6FF, not 1e-5f * 1e-5f = 0x2EDBE6FE.  A block of pixels with state
+    sigma 0, transition sigma 0 and flow that stays inside the block: both variances are the floor, the predicted sigma in the
+    `temp` output is sqrt(floor + floor) with bits 929907715 (929907714 with the fp32 product), and the block's records equal
+    the fp32 oracle's bit for bit.  Both kernels that form the floor: the LDS scan and the per-frame step of a large grid."""
+    from tests.gpu_util import dev, stream, sync
+    from kfnet_amd import _lib
+    import torch
+    lib = _lib.load()
+    H, W = grid
+    S, T = 1, 2
+    rng = np.random.default_rng(H)
+    flow = (rng.normal(size=(S, T, H, W, 2)) * 2.0).astype(np.float32)
+    sig = np.abs(rng.normal(size=(S, T, H, W, 1)) * 0.05).astype(np.float32)
+    meas = rng.normal(size=(S, T, H, W, 4)).astype(np.float32)
+    meas[..., 3] = np.abs(meas[..., 3]) * 0.3 + 0.05
+    state0 = rng.normal(size=(S, H, W, 4)).astype(np.float32)
+    state0[..., 3] = np.abs(state0[..., 3]) * 0.3 + 0.05
+    rows, cols = slice(4, 12), slice(5, 16)                            # the zero block: state rows 4..12, columns 5..16
+    state0[:, 4:13, 5:17, 3] = 0.0
+    sig[:, 0, rows, cols] = 0.0
+    flow[:, 0, rows, cols] = rng.uniform(0.0, 0.9, size=(S, 8, 11, 2)).astype(np.float32)   # all four taps inside the block
+    d = _lib.KalmanDesc(S=S, T=T, H=H, W=W, t0=1, reset_period=500, min_uncertainty=1e-5, nis_gate=0.0, has_transform=0)
+    dfl, dsg, dme, dst = dev(flow), dev(sig), dev(meas), dev(state0)
+    rec = torch.zeros(S * T * H * W * 4, device='cuda')
+    tmp = torch.zeros(S * T * H * W * 4, device='cuda')
+    need = C.c_size_t(0)
+    _lib.check(lib.kfn_kalman_scan_scratch_bytes(C.byref(d), C.byref(need)), 'scratch bytes')
+    assert (need.value > 0) == (H * W > 10240)
+    scratch = torch.empty(max(need.value // 4, 1), device='cuda')
+    _lib.check(lib.kfn_kalman_scan(C.byref(d), dfl.data_ptr(), dsg.data_ptr(), dme.data_ptr(), dst.data_ptr(), rec.data_ptr(),
+                                   tmp.data_ptr(), None, scratch.data_ptr(), stream()), 'scan')
+    sync()
+    r_rec, r_tmp, _, _ = _scan_ref(flow, sig, meas, state0, None, 1, 500, 0.0)
+    g_tmp = tmp.cpu().numpy().reshape(r_tmp.shape)
+    g_rec = rec.cpu().numpy().reshape(r_rec.shape)
+    assert np.all(r_tmp[0, 0, rows, cols, 3].view(np.uint32) == 929907715), 'the fp32 oracle itself'
+    assert np.all(g_tmp[0, 0, rows, cols, 3].view(np.uint32) == 929907715)
+    assert np.array_equal(g_rec[0, 0, rows, cols].view(np.uint32), r_rec[0, 0, rows, cols].view(np.uint32))
+    assert np.allclose(g_tmp, r_tmp, rtol=2e-6, atol=2e-6) and np.allclose(g_rec, r_rec, rtol=1e-5, atol=1e-5)
 
 
 @pytest.mark.parametrize('grid', [(60, 80), (68, 120)])

@@ -249,6 +249,24 @@ def _loss_inputs(seed, B=2, h=8, w=12, full_res=False):
     return pred, labels, frames, M
 
 
+THR2 = float(np.float32(0.05 * 0.05))       # what the kernel subtracts: the reference's double product, rounded once to fp32
+THR_MARGIN = 1e-6
+
+
+def _assert_clear_of_the_threshold(pred, labels, M):
+    """The condition on the inputs that lets the fp64 reference alone decide the accuracy count: no masked pixel whose squared
+    distance lies within 1e-6 of the squared threshold (the fp32 d of the kernel is off by ~1e-9 there)."""
+    B, h, w, _ = pred.shape
+    lab = R.grid_labels(labels, (h, w)).astype(np.float64)
+    gt = lab[..., :3]
+    if M is not None:
+        M64 = np.asarray(M, np.float64)
+        gt = gt @ M64[:3, :3].T + M64[:3, 3]
+    d = ((pred[..., :3].astype(np.float64) - gt) ** 2).sum(-1)
+    assert not np.any((lab[..., 3] == 1.0) & (np.abs(d - THR2) < THR_MARGIN))
+    return d
+
+
 def _check_loss(pred, labels, frames, M, clip, sw, what):
     import torch
     st, g = run_loss(pred, labels, frames, M, clip, sw)
@@ -279,25 +297,60 @@ def test_coord_loss_and_gradient_against_fp64_autograd():
     _check_loss(pred8, labels8, frames8, M8, None, 50.0, 'full-resolution labels')
 
 
-def test_coord_loss_clip_with_both_branches():
-    pred, labels, frames, M = _loss_inputs(3)
-    rng = np.random.default_rng(4)
+def _vertical_weights(frames):
+    """exp(-0.625 mean_c |img(r, c) - img(r + 1, c)|) on the frames' grid [B,h-1,w] (fp64); _horizontal_weights alike."""
+    img = frames[:, ::8, ::8].astype(np.float64)
+    return np.exp(-0.625 * np.abs(img[:, :-1] - img[:, 1:]).mean(-1))
+
+
+def _horizontal_weights(frames):
+    img = frames[:, ::8, ::8].astype(np.float64)
+    return np.exp(-0.625 * np.abs(img[:, :, :-1] - img[:, :, 1:]).mean(-1))
+
+
+def _flatten_upper_half(frames):
+    """_loss_inputs' frames are flat along the rows only (columns 40..), so every VERTICAL edge weight is exp(-0.625 * ~85) = 0
+    and the r + 1 / r - 1 reads of the kernel would go unchecked.  The upper half of each frame becomes flat down the columns:
+    vertical weights 1 there, and 1 in both directions where the two flat regions meet.  Asserted: at least 10 % of the vertical
+    and of the horizontal edges carry a weight above 0.1 (where the grid has such edges at all)."""
+    H = frames.shape[1]
+    frames[:, :(H + 1) // 2] = frames[:, :1]
+    for wts in (_vertical_weights(frames), _horizontal_weights(frames)):
+        assert wts.size == 0 or (wts > 0.1).mean() >= 0.1
+    return frames
+
+
+def _clip_inputs(seed, flat=False, **grid):
+    """Inputs on both sides of loss_clip = -2 and of the 5 cm threshold; also returns the fp64 loss map l."""
+    pred, labels, frames, M = _loss_inputs(seed, **grid)
+    if flat:
+        _flatten_upper_half(frames)
+    rng = np.random.default_rng(seed + 1)
     pred[..., 3] = rng.uniform(-2.5, -0.5, size=pred.shape[:3])
     # labels a few centimetres from the prediction in the transformed frame: 3 log u in [-7.5, -1.5] decides the branch
     target = pred[..., :3].astype(np.float64) + 0.03 * rng.normal(size=pred.shape[:3] + (3,))
     M64 = M.astype(np.float64)
     labels[..., :3] = ((target - M64[:3, 3]) @ np.linalg.inv(M64[:3, :3]).T).astype(np.float32)
     gt = labels[..., :3].astype(np.float64) @ M64[:3, :3].T + M64[:3, 3]
-    for _ in range(20):                                  # no pixel within 1e-3 of the clip
+    for _ in range(20):                                  # no pixel within 1e-3 of the clip, none within 1e-6 of (5 cm)^2
         sig = np.exp(pred[..., 3].astype(np.float64))
-        l = 3 * np.log(sig) + ((pred[..., :3].astype(np.float64) - gt) ** 2).sum(-1) / (2 * sig * sig)
+        d = ((pred[..., :3].astype(np.float64) - gt) ** 2).sum(-1)
+        l = 3 * np.log(sig) + d / (2 * sig * sig)
         near = np.abs(l + 2.0) < 1e-3
-        if not near.any():
+        edge = np.abs(d - THR2) < THR_MARGIN
+        if not near.any() and not edge.any():
             break
         pred[..., 3][near] += np.float32(0.05)
-    assert not near.any()
+        pred[..., 0][edge] += np.float32(0.01)
+    assert not near.any() and not edge.any()
     m = labels[..., 3] == 1.0
     assert (l[m] > -2.0).sum() > 10 and (l[m] < -2.0).sum() > 10
+    assert (d[m] > THR2).sum() > 10 and (d[m] < THR2).sum() > 10
+    return pred, labels, frames, M, l, m
+
+
+def test_coord_loss_clip_with_both_branches():
+    pred, labels, frames, M, l, m = _clip_inputs(3)
     g64 = _check_loss(pred, labels, frames, M, -2.0, 0.0, 'loss_clip -2')
     assert np.all(g64[(l > -2.0)] == 0.0) and np.any(g64[(l < -2.0) & m] != 0.0)
     _check_loss(pred, labels, frames, M, -2.0, 50.0, 'loss_clip -2 with smoothness')
@@ -315,6 +368,104 @@ def test_coord_loss_below_the_uncertainty_floor_and_with_an_empty_mask():
     _check_loss(pred, empty, frames, M, None, 50.0, 'all-zero mask')
     st, g = run_loss(pred, empty, frames, M, None, 50.0)
     assert st[3] == 1.0 and st[0] == 0.0 and st[1] == 0.0 and st[2] == 1.0 and not g.any()
+
+
+# the loss beyond one pass of its 1024-thread loop `for (i = t; i < P; i += 1024)`; the tests above stop at 192 pixels
+LOSS_GRIDS = [(1, 1, 1024), (1, 1, 1025),      # one row: no vertical neighbours; the second pass holds one pixel
+              (1, 1025, 1),                    # one column
+              (3, 17, 23),                     # 1173 pixels, odd, frame boundaries inside a pass
+              (4, 60, 80), (2, 68, 120)]       # the production batch (19 passes) and the second product grid
+
+
+def _grid_inputs(grid, full_res=False):
+    B, h, w = grid
+    pred, labels, frames, M = _loss_inputs(100 + LOSS_GRIDS.index(grid) + 10 * int(full_res), B=B, h=h, w=w, full_res=full_res)
+    _flatten_upper_half(frames)
+    _assert_clear_of_the_threshold(pred, labels, M)
+    _assert_clear_of_the_threshold(pred, labels, None)
+    return pred, labels, frames, M
+
+
+def _seam_inputs():
+    """B = 3 frames of 17x23 = 391 pixels, so frame boundaries fall inside a pass of the 1024-thread loop.  The last row of
+    frame b and the first row of frame b + 1 lie 100 apart in every coordinate, all seam pixels are masked in, and the image
+    rows under grid rows 0, 1, h-2 and h-1 are one and the same row in every frame: the vertical edge weight is 1 between rows
+    0-1 and (h-2)-(h-1) inside a frame, and would be 1 between row h-1 of frame b and row 0 of frame b + 1.
+    Returns the inputs and `tol`, _check_loss's tolerance 1e-5 max|g64|.  Asserted here, on the host: the within-frame weights
+    at the seam rows are 1, and the term a neighbour from across the seam would add to the gradient,
+    smooth_weight (2/3) / valid * weight * |x(b, h-1) - x(b+1, 0)|, exceeds 100 tol at EVERY seam pixel and coordinate."""
+    import torch
+    pred, labels, frames, M = _loss_inputs(200, B=3, h=17, w=23)
+    B, h, w, _ = pred.shape
+    pred[:, -1, :, :3] += 50.0
+    pred[:, 0, :, :3] -= 50.0
+    labels[:, (0, 1, -2, -1), :, 3] = 1.0
+    for r in (0, 1, h - 2, h - 1):
+        frames[:, 8 * r] = frames[0, 0]
+    _assert_clear_of_the_threshold(pred, labels, M)
+    wv = _vertical_weights(frames)
+    assert np.all(wv[:, 0] == 1.0) and np.all(wv[:, -1] == 1.0)
+    img = frames[:, ::8, ::8].astype(np.float64)
+    w_cross = np.exp(-0.625 * np.abs(img[:-1, -1] - img[1:, 0]).mean(-1))                   # [B-1,w]
+    assert np.all(w_cross == 1.0)
+    p = torch.from_numpy(pred.astype(np.float64)).requires_grad_(True)
+    L, _, _, _, valid = R.coord_loss(p, labels, img, M, None, 50.0)
+    g64, = torch.autograd.grad(L, [p])
+    tol = 1e-5 * float(g64.abs().max())
+    cross = 50.0 * (2.0 / 3.0) / valid.item() * w_cross[..., None] * np.abs(pred[:-1, -1, :, :3].astype(np.float64) - pred[1:, 0, :, :3])
+    assert cross.min() > 100.0 * tol, (cross.min(), tol)
+    return pred, labels, frames, M, tol
+
+
+@pytest.mark.parametrize('grid', LOSS_GRIDS, ids=['%dx%dx%d' % g for g in LOSS_GRIDS])
+def test_coord_loss_beyond_one_pass_against_fp64_autograd(grid):
+    pred, labels, frames, M = _grid_inputs(grid)
+    for m in (M, None):
+        for sw in (50.0, 0.0):
+            _check_loss(pred, labels, frames, m, None, sw, '%dx%dx%d%s, smooth_weight %g' % (grid + (' transform' if m is not None else '', sw)))
+
+
+def test_coord_loss_on_the_production_batch_with_full_resolution_labels_and_with_the_clip():
+    grid = (4, 60, 80)
+    pred, labels, frames, M = _grid_inputs(grid, full_res=True)
+    assert labels.shape == (4, 480, 640, 4)
+    _check_loss(pred, labels, frames, M, None, 50.0, '4x60x80, labels at stride 8')
+    pred, labels, frames, M, l, m = _clip_inputs(7, flat=True, B=4, h=60, w=80)
+    g64 = _check_loss(pred, labels, frames, M, -2.0, 50.0, '4x60x80, loss_clip -2 with smoothness')
+    g64 = _check_loss(pred, labels, frames, M, -2.0, 0.0, '4x60x80, loss_clip -2')
+    assert np.all(g64[(l > -2.0)] == 0.0) and np.any(g64[(l < -2.0) & m] != 0.0)
+
+
+def test_coord_loss_smoothness_does_not_reach_across_a_frame_seam():
+    """_seam_inputs: edge weights of 1 on both sides of every frame seam and across it, the rows there 100 apart.  A vertical
+    neighbour taken from the next (or previous) frame would move the gradient of those rows by more than 100 times the tolerance
+    of _check_loss (asserted on the host by _seam_inputs); the legitimate neighbours, 50 away with weight 1, are checked by
+    the same comparison."""
+    pred, labels, frames, M, tol = _seam_inputs()
+    g64 = _check_loss(pred, labels, frames, M, None, 50.0, 'frame seam')
+    assert 1e-5 * float(np.abs(g64).max()) == pytest.approx(tol, rel=1e-9)
+
+
+def test_coord_loss_counts_a_pixel_exactly_five_centimetres_off_as_inaccurate():
+    """No transform, labels at the origin with mask 1, predictions (0.05f, 0, 0) on k pixels and the float below 0.05f on the
+    others, 1173 pixels (the k pixels lie in both passes).  d = 0.05f^2 = 0x3B23D70B exceeds the reference's float32(0.05 * 0.05) =
+    0x3B23D70A: accuracy = (valid - k) / valid.  With the threshold squared in fp32 it was 1."""
+    B, h, w = 3, 17, 23
+    P = B * h * w
+    rng = np.random.default_rng(12)
+    at = rng.permutation(P)[:P // 3]
+    assert (at < 1024).any() and (at >= 1024).any()
+    pred = np.zeros((P, 4), np.float32)
+    pred[:, 0] = np.nextafter(np.float32(0.05), np.float32(0))
+    pred[at, 0] = np.float32(0.05)
+    pred[:, 3] = -1.0
+    labels = np.zeros((B, h, w, 4), np.float32)
+    labels[..., 3] = 1.0
+    frames = np.zeros((B, h * 8, w * 8, 3), np.uint8)
+    st, _ = run_loss(pred.reshape(B, h, w, 4), labels, frames, None, None, 0.0)
+    valid = P + 1.0
+    assert st[3] == valid
+    assert st[2] == np.float32((valid - at.size) / valid), (st[2], at.size)
 
 
 # -- 4. Adam ---------------------------------------------------------------------------------------------------------------

@@ -156,8 +156,8 @@ def test_helpers_reproduce_the_scan_kernels_process_model():
     sync()
     t = temp.cpu().numpy().reshape(H, W, 4)
     assert np.array_equal(t[..., :3], warped_x.numpy()[0])
-    lv = np.maximum(warped_s.numpy()[0, ..., 0] ** 2, np.float32(1e-10))
-    tv = np.maximum(sig[0, ..., 0] ** 2, np.float32(1e-10))
+    lv = np.maximum(warped_s.numpy()[0, ..., 0] ** 2, np.float32(1e-5 * 1e-5))
+    tv = np.maximum(sig[0, ..., 0] ** 2, np.float32(1e-5 * 1e-5))
     assert np.allclose(t[..., 3], np.sqrt(tv + lv), rtol=2e-7, atol=0)
 
 
@@ -171,3 +171,62 @@ def test_c_abi_argument_checks():
     assert lib.kfn_pixel_map(buf.data_ptr(), 2, 1, 2, 2, 1, 0.0, 0.0, 0.0, 1.0, s) == -1
     assert lib.kfn_bilinear_sampler(buf.data_ptr(), 1, 1, 2, 2, 2, buf.data_ptr(), 2, 2, 2, buf.data_ptr(), 2, s) == -1
     assert b'kfn_bilinear_sampler' in lib.kfn_last_error()
+
+
+def test_eval_metrics_argument_checks():
+    """kfn_eval_metrics: a null pointer, T = 0, HW = 0, a base that is not 16-byte aligned and bad thresholds return -1 with a
+    message; nothing is launched."""
+    import torch
+    from kfnet_amd import _lib
+    lib = _lib.load()
+    buf, out = torch.zeros(256, device='cuda'), torch.zeros(64, device='cuda')
+    p, s = buf.data_ptr(), torch.cuda.current_stream().cuda_stream
+    good = [p, p, p, p, p, p, p, p, None, 1, 4, 0.05, 1e-5, out.data_ptr(), out.data_ptr() + 64, s]
+    assert lib.kfn_eval_metrics(*good) == 0
+    torch.cuda.synchronize()
+    assert out[6].item() == 1.0                                      # an all-zero mask: valid_pixel = 0 + 0 + 1
+    for i in (0, 1, 2, 3, 4, 5, 6, 7, 13, 14):
+        bad = list(good)
+        bad[i] = None
+        assert lib.kfn_eval_metrics(*bad) == -1 and b'kfn_eval_metrics: null' in lib.kfn_last_error(), i
+    for i, v in ((9, 0), (10, 0), (9, -1)):
+        bad = list(good)
+        bad[i] = v
+        assert lib.kfn_eval_metrics(*bad) == -1 and b'bad shape' in lib.kfn_last_error(), (i, v)
+    for i in (0, 1, 2, 3, 5):
+        bad = list(good)
+        bad[i] = p + 4
+        assert lib.kfn_eval_metrics(*bad) == -1 and b'misaligned' in lib.kfn_last_error(), i
+    for i, v in ((11, -0.05), (12, 0.0)):
+        bad = list(good)
+        bad[i] = v
+        assert lib.kfn_eval_metrics(*bad) == -1 and b'thresholds' in lib.kfn_last_error(), (i, v)
+
+
+@pytest.mark.parametrize('shape', [(1, 1), (1000, 3), (4800, 48), (70000, 32)], ids=lambda s: '%dx%d' % s)
+def test_copy_channels_between_wider_buffers_is_exact(shape):
+    """kfn_copy_channels (Network.concat's fallback) had no direct test.  Source rows C + 8 wide, destination rows C + 4 wide,
+    both filled with sentinels: the C channels arrive bit for bit, nothing else moves.  70000 x 32 = 2.24 M elements exceed
+    the launch's 8192 x 256 threads, so its grid-stride loop runs a second time."""
+    import torch
+    from kfnet_amd import _lib
+    from tests.gpu_util import dev, stream, sync
+    lib = _lib.load()
+    P, Cc = shape
+    rng = np.random.default_rng(P)
+    src = rng.integers(0, 2 ** 32, size=(P, Cc + 8), dtype=np.uint32)          # every bit pattern, NaNs included
+    G = 64
+    dst = np.full((P + G, Cc + 4), 0xC0A00000, np.uint32)                      # -5.0f
+    sd, dd = dev(src.view(np.float32)), dev(dst.view(np.float32))
+    _lib.check(lib.kfn_copy_channels(sd.data_ptr(), Cc + 8, dd.data_ptr(), Cc + 4, P, Cc, stream()), 'kfn_copy_channels')
+    sync()
+    got = dd.cpu().numpy().view(np.uint32)
+    want = dst.copy()
+    want[:P, :Cc] = src[:, :Cc]
+    assert np.array_equal(got, want)
+    assert np.array_equal(sd.cpu().numpy().view(np.uint32), src)
+    if P == 1:
+        for bad in ((None, 9, dd.data_ptr(), 5, 1, 1), (sd.data_ptr(), 9, None, 5, 1, 1), (sd.data_ptr(), 9, dd.data_ptr(), 5, 0, 1),
+                    (sd.data_ptr(), 9, dd.data_ptr(), 5, 1, 0), (sd.data_ptr(), 2, dd.data_ptr(), 5, 1, 3),
+                    (sd.data_ptr(), 9, dd.data_ptr(), 2, 1, 3)):
+            assert lib.kfn_copy_channels(*bad, stream()) == -1 and b'kfn_copy_channels' in lib.kfn_last_error(), bad

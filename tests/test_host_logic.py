@@ -485,7 +485,9 @@ def test_conv_desc_matches_header_and_integration_doc():
     # the scan descriptor too
     kf = _header_struct_fields(hdr, 'kfn_kalman_desc')
     assert [f[0] for f in kf] == [f[0] for f in _lib.KalmanDesc._fields_]
-    assert sum(f[2] for f in kf) * 4 == C.sizeof(_lib.KalmanDesc)
+    width = {'int32_t': 4, 'float': 4, 'double': 8}       # min_uncertainty is a double (ABI 13), 8-byte aligned at offset 24
+    assert sum(width[f[1]] * f[2] for f in kf) == C.sizeof(_lib.KalmanDesc)           # no padding: 88 bytes
+    assert _lib.KalmanDesc.min_uncertainty.offset == 24 and _lib.KalmanDesc.min_uncertainty.size == 8
 
 
 def test_every_header_function_is_bound_and_exported():

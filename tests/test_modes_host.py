@@ -156,12 +156,12 @@ def test_record_formats_in_numpy():
 
 
 def test_abi12_exports_the_record_entry_points_and_checks_arguments():
-    assert _lib.ABI_VERSION == 12
+    assert _lib.ABI_VERSION == 13
     hdr = open(os.path.join(ROOT, 'include', 'kfnet_hip.h')).read()
-    assert '#define KFN_ABI_VERSION 12' in hdr
-    assert 'kfn_abi_version() == 12' in open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+    assert '#define KFN_ABI_VERSION 13' in hdr
+    assert 'kfn_abi_version() == 13' in open(os.path.join(ROOT, 'INTEGRATION.md')).read()
     lib = _lib.load()
-    assert lib.kfn_abi_version() == 12
+    assert lib.kfn_abi_version() == 13
     for name in ('kfn_coord_records', 'kfn_flow_records'):
         assert name in _lib.SYMBOLS and hasattr(lib, name)
     d16, d4 = C.c_void_p(64), C.c_void_p(68)        # never dereferenced: every call below fails its checks first

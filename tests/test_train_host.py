@@ -100,7 +100,7 @@ def test_initial_weights_are_glorot_uniform_with_zero_biases():
 
 def test_new_entry_points_are_exported_and_check_their_arguments_without_a_device():
     lib = _lib.load()
-    assert lib.kfn_abi_version() == 12
+    assert lib.kfn_abi_version() == 13
     for name in NEW:
         assert name in _lib.SYMBOLS and hasattr(lib, name)
     ARG = -1
@@ -238,3 +238,21 @@ def test_reference_adam_is_the_tensorflow_formula():
     np.testing.assert_allclose(w - w1, 1e-3 * np.sign(g), rtol=1e-4)          # the first Adam step is lr * sign(g)
     w2, _, _ = R.adam_step(w, m, v, g * 0, 1e-3, 1, weight_decay=0.5)
     np.testing.assert_allclose(w - w2, 1e-3 * np.sign(w), rtol=1e-4, atol=1e-12)   # the regulariser's gradient is wd * w
+
+
+def test_inputs_of_the_gpu_loss_tests_keep_clear_of_the_squared_threshold():
+    """With numpy alone: every grid tests/test_gpu_train.py runs the loss on beyond one pass satisfies its input condition -- no
+    masked pixel whose squared distance lies within 1e-6 of float32(0.05 * 0.05) -- and the clip construction fills both
+    branches at the production batch.  The frames carry smoothness weights in both directions (_flatten_upper_half), and the
+    seam case has weights of 1 across every frame seam (_seam_inputs asserts what a cross-seam read would add)."""
+    import numpy as np
+    import test_gpu_train as G
+    assert np.float32(G.THR2).view(np.uint32) == 0x3B23D70A
+    for grid in G.LOSS_GRIDS:
+        pred, labels, frames, M = G._grid_inputs(grid)
+        assert pred.shape == grid + (4,) and frames.shape[1:3] == (8 * grid[1], 8 * grid[2])
+    assert max(g[0] * g[1] * g[2] for g in G.LOSS_GRIDS) == 19200 and min(g[0] * g[1] * g[2] for g in G.LOSS_GRIDS) == 1024
+    G._grid_inputs((4, 60, 80), full_res=True)
+    assert G._seam_inputs()[4] > 0
+    G._clip_inputs(3)
+    G._clip_inputs(7, flat=True, B=4, h=60, w=80)

@@ -25,7 +25,7 @@ __global__ __launch_bounds__(KT) void kalman_scan_kernel_r4(KalmanArgs a) {
   const int tid = threadIdx.x;
   const int s = blockIdx.x;
   const int H = a.d.H, W = a.d.W, HW = H * W, T = a.d.T;
-  const float eps2 = a.d.min_uncertainty * a.d.min_uncertainty;
+  const float eps2 = a.eps2;
   const float xmax = (float)(W - 1), ymax = (float)(H - 1);
   const bool want_nis = (a.opt_nis != nullptr) || (a.d.nis_gate > 0.f);
 
@@ -139,7 +139,7 @@ int main(int argc, char** argv) {
   CK(hipMemcpy(d_meas, h_meas.data(), N * 16, hipMemcpyHostToDevice)); CK(hipMemcpy(d_state0, h_state.data(), S * HW * 16, hipMemcpyHostToDevice));
   KalmanArgs a{};
   a.flow = (const f32x2*)d_flow; a.sigma_t = d_sig; a.meas = (const f32x4*)d_meas; a.state = (f32x4*)d_state; a.rec = (f32x4*)d_rec;
-  a.d.S = S; a.d.T = T; a.d.H = H; a.d.W = W; a.d.t0 = 1; a.d.reset_period = 500; a.d.min_uncertainty = 1e-5f; a.d.nis_gate = 0.f;
+  a.d.S = S; a.d.T = T; a.d.H = H; a.d.W = W; a.d.t0 = 1; a.d.reset_period = 500; a.d.min_uncertainty = 1e-5; a.eps2 = floor_variance(a.d.min_uncertainty); a.d.nis_gate = 0.f;
   a.d.has_transform = 1;
   const float M[12] = {1, 0, 0, 0.1f, 0, 1, 0, 0.2f, 0, 0, 1, 0.3f};
   for (int i = 0; i < 12; ++i) a.d.transform[i] = M[i];
