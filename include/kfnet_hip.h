@@ -49,7 +49,8 @@ extern "C" {
  * every ABI-12 host working, so the number stays.
  * 13: the constants the reference squares in Python cross the boundary as doubles -- kfn_kalman_desc.min_uncertainty,
  * kfn_coord_loss_desc.dist_threshold / min_uncertainty and the two thresholds of kfn_eval_metrics (layout and signature
- * change: an ABI-12 host must be rebuilt). */
+ * change: an ABI-12 host must be rebuilt); later kfn_frame_channel_sums and kfn_augment_batch (augmenting a training
+ * batch), added exports that leave every ABI-13 host working, so the number stays. */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -706,6 +707,48 @@ int kfn_coord_loss_grad(const kfn_coord_loss_desc* desc, const float* pred, cons
  * evaluated in fp64 from the fp32 variables, each stored value rounded once. */
 int kfn_adam_step(float* w, float* m, float* v, const float* g, long n, double lr_t, double beta1, double beta2,
                   double epsilon, double weight_decay, void* stream);
+
+/* ---- augmenting a training batch (added exports; the ABI number stays 13) --------------------------------------------
+ * data_augmentation of the reference (KFNet/train.py:168-193): tf.image.random_brightness / random_contrast on the frames,
+ * then frames and labels together through image_augmentation (KFNet/util.py:66-136) -- an in-plane rotation
+ * (tf.contrib.image.rotate, NEAREST, fill 0) followed by a zoom into a box (tf.image.crop_and_resize) or by a shrink with
+ * zero padding (tf.image.resize_images + resize_image_with_crop_or_pad) -- with ONE parameter set per batch.  DESIGN.md 6c
+ * lists every operation; the device evaluates exactly that list in unfused fp32, so all derived constants arrive here as
+ * floats the host has rounded once (kfnet_amd.augment.descriptor).  crop_size == image_size only.
+ *
+ * kfn_frame_channel_sums -- sums [B][4] uint32 = the exact sum of each channel of each frame of img [B,H,W,3] uint8, the
+ * fourth word 0 (adjust_contrast's per-channel mean, times H W).  Integer adds: bit-identical from launch to launch.  H and
+ * W multiples of 8, img 16-byte aligned. */
+int kfn_frame_channel_sums(const uint8_t* img, int B, int H, int W, uint32_t* sums, void* stream);
+/* kfn_augment_batch -- frames_out [B,H,W,3] uint8 and, unless labels_in and labels_out are both NULL, labels_out
+ * [B,H/label_stride,W/label_stride,4] = the augmented (xyz, mask) at output pixels (label_stride r, label_stride c) from the
+ * full-resolution labels_in [B,H,W,4]; label_stride 1 or 8 (the loss reads pixel (8r, 8c)).
+ *   mode 0 (translate): the identity map, no rotation.  mode 1 (enlarge): in_y = y0 + i dy, 0 outside [0, H-1], taps floor /
+ *   ceil.  mode 2 (shrink): ii = i - off_y, 0 unless 0 <= ii < new_h, in_y = ii scale_y, taps t = floor, min(t + 1, H - 1).
+ *   value = top + (bot - top) ly with top = tl + (tr - tl) lx, bot alike; each tap is pixel (x, y) of the ROTATED image =
+ *   source pixel (round(sx), round(sy)), sx = (rot0 x + rot1 y) + rot2, sy = (rot3 x + rot4 y) + rot5, round half away from
+ *   zero, 0 outside the image (has_rotation == 0: the pixel itself).
+ *   frames: a tap is ((p + delta) - mean) factor + mean with mean = float(sum / (H W) + delta) per frame and channel when
+ *   has_colour (the fill value 0 is not adjusted), the result clamp(rint(value), 0, 255) (ties to even).
+ *   labels: the four channels interpolated, then mask = value >= 1 ? 1 : 0 (KFNet/train.py:189).
+ * With has_colour the call runs kfn_frame_channel_sums into `sums` [B][4] first, on the same stream; sums may be NULL
+ * otherwise.  H, W >= 8 and multiples of 8.  KFN_ERR_ARG, and nothing launched: other sizes, a stride other than 1 or 8,
+ * frames_out == frames_in (the gather cannot run in place), NULL where a buffer is needed, one label pointer without the
+ * other, a struct_size other than sizeof(kfn_augment_desc). */
+typedef struct kfn_augment_desc {
+  int32_t struct_size;      /* = sizeof(kfn_augment_desc) */
+  int32_t B, H, W;
+  int32_t label_stride;
+  int32_t mode;             /* 0 translate, 1 enlarge, 2 shrink */
+  int32_t has_rotation, has_colour;
+  float rot[6];             /* cos a, -sin a, xo, sin a, cos a, yo */
+  float y0, dy, x0, dx;     /* enlarge: y1 (H - 1), ratio, x1 (W - 1), ratio */
+  int32_t new_h, new_w, off_y, off_x;   /* shrink */
+  float scale_y, scale_x;   /* H / new_h, W / new_w */
+  float delta, factor;      /* brightness delta, contrast factor */
+} kfn_augment_desc;
+int kfn_augment_batch(const kfn_augment_desc* desc, const uint8_t* frames_in, const float* labels_in, uint8_t* frames_out,
+                      float* labels_out, uint32_t* sums, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,9 @@ The flags --base_lr --max_steps --display --stepvalue --snapshot --gamma --weigh
 reference's (KFNet/train.py:14-47); stepvalue and max_steps = 5 * stepvalue follow the scene (set_stepvalue) unless given.
 --loss_clip is off by default: the snapshot's clip at -2.0 (KFNet/KFNet.py:217) zeroes every gradient of an untrained
 network; `--loss_clip -2` reproduces it.  `--synthetic N` trains on N seeded synthetic frames and labels.
+`--augment` applies the reference's data_augmentation (KFNet/train.py:168-193) to every batch on the device, with the
+parameters kfnet_amd.augment.draw(--augment_seed, step); the whole label files are then read, not only the
+pixels the loss uses.
 """
 import argparse
 import os
@@ -62,6 +65,8 @@ def build_parser():
     ap.add_argument('--loss_clip', type=float, default=None)
     ap.add_argument('--smooth_weight', type=float, default=50.0)
     ap.add_argument('--synthetic', type=int, default=0, help='train on this many seeded synthetic frames and labels')
+    ap.add_argument('--augment', action='store_true', help='brightness, contrast, rotation and zoom / shrink per batch')
+    ap.add_argument('--augment_seed', type=int, default=None, help='seed of the augmentation draws (default: --seed)')
     return ap
 
 
@@ -86,7 +91,7 @@ def main(argv=None):
         from ..synth import synthetic_sequence, synthetic_transform
         count = a.synthetic
         all_frames = synthetic_sequence(count, a.height, a.width)
-        all_labels = synthetic_labels(count, grid)
+        all_labels = synthetic_labels(count, size if a.augment else grid)
         transform = synthetic_transform()
 
         def batch_of(idx):
@@ -103,9 +108,25 @@ def main(argv=None):
         count = len(paths)
         from ..KFNet.metrics import read_label_grid
 
+        def read_label(path):
+            if not a.augment:
+                return read_label_grid(path, size, grid)
+            lab = np.fromfile(path, dtype=np.float32)      # the whole label: augmentation interpolates between its pixels
+            if lab.size != size[0] * size[1] * 4:
+                raise ValueError('%s holds %d floats, --augment needs the full-resolution label of %d' %
+                                 (path, lab.size, size[0] * size[1] * 4))
+            return lab.reshape(size[0], size[1], 4)
+
+        if a.augment:
+            try:
+                read_label(label_paths[0])
+            except (OSError, ValueError) as e:
+                print(e, file=sys.stderr)
+                return 1
+
         def batch_of(idx):
             frames = modes.load_images([paths[i] for i in idx], size)
-            return frames, np.stack([read_label_grid(label_paths[i], size, grid) for i in idx])
+            return frames, np.stack([read_label(label_paths[i]) for i in idx])
 
     W, state, step = restore(a.model_folder)
     if W is None:
@@ -119,6 +140,9 @@ def main(argv=None):
                           smooth_weight=a.smooth_weight, device='cuda:%d' % a.gpu)
     if state is not None:
         tr.load_state(state)
+    if a.augment:
+        from ..augment import draw
+        augment_seed = a.seed if a.augment_seed is None else a.augment_seed
     tr.global_step = step if a.reset_step < 0 else a.reset_step
     print('----------------------------------')
     print('scene: ', a.scene)
@@ -131,7 +155,7 @@ def main(argv=None):
     while tr.global_step < max_steps:
         t0 = time.time()
         frames, labels = batch_of(batch_indices(tr.global_step, a.batch, count, a.shuffle, a.seed))
-        stats = tr.step(frames, labels)
+        stats = tr.step(frames, labels, augment=draw(augment_seed, tr.global_step)) if a.augment else tr.step(frames, labels)
         s = tr.global_step
         if s % a.display == 0 or s == max_steps:
             line = dict(stats)           # the read-back waits for the step

@@ -82,6 +82,19 @@ class CoordLossDesc(C.Structure):
             self.struct_size = C.sizeof(CoordLossDesc)
 
 
+class AugmentDesc(C.Structure):
+    """kfn_augment_desc (include/kfnet_hip.h); `struct_size` is filled in here.  kfnet_amd.augment.descriptor derives it."""
+    _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'B', 'H', 'W', 'label_stride', 'mode', 'has_rotation', 'has_colour')] +
+                [('rot', C.c_float * 6)] + [(n, C.c_float) for n in ('y0', 'dy', 'x0', 'dx')] +
+                [(n, C.c_int32) for n in ('new_h', 'new_w', 'off_y', 'off_x')] +
+                [(n, C.c_float) for n in ('scale_y', 'scale_x', 'delta', 'factor')])
+
+    def __init__(self, *args, **kw):
+        super(AugmentDesc, self).__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(AugmentDesc)
+
+
 # name -> (restype, argtypes); every symbol declared in include/kfnet_hip.h
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 SYMBOLS = {
@@ -168,6 +181,9 @@ SYMBOLS = {
     'kfn_pack_conv_weights': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'kfn_coord_loss_grad': (_i, [C.POINTER(CoordLossDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
     'kfn_adam_step': (_i, [_vp, _vp, _vp, _vp, C.c_long, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
+    # augmenting a training batch (added exports, ABI 13)
+    'kfn_frame_channel_sums': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'kfn_augment_batch': (_i, [C.POINTER(AugmentDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

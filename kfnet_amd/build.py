@@ -31,6 +31,8 @@ EXTRA = {
     'kfn_util_ops.hip': ['-ffp-contract=off'],
     # the training loss clips, thresholds and counts per-pixel terms, like the metrics kernel
     'kfn_train_loss.hip': ['-ffp-contract=off'],
+    # the augmentation's index arithmetic and interpolation are a list of rounded fp32 operations
+    'kfn_augment.hip': ['-ffp-contract=off'],
 }
 
 

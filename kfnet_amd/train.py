@@ -3,6 +3,7 @@
 The reference builds the TF-1 graph of KFNet/train.py:268-315 and lets tf.gradients / AdamOptimizer derive the rest.  Here
 one step is a fixed list of launches of libkfnet_hip.so (DESIGN.md "Training"):
 
+    augment      (step(..., augment=params) only) kfn_augment_batch: the raw batch -> self.frames and grid-sized labels
     forward      kfn_first_conv_u8, then kfn_conv2d_nhwc per layer (the direct route, fp32, every output kept)
     loss         kfn_coord_loss_grad: NLL + smoothness on the prepared labels, and d(loss)/d(prediction)
     backward     per layer, last to first: kfn_conv2d_grad_weights; the input gradient on the FORWARD kernel
@@ -153,6 +154,7 @@ class SCoordNetTrainer(object):
             # activations (each layer's output after its ReLU) and the gradients with respect to them
             self.frames = torch.zeros((batch, H, Wd, 3), dtype=torch.uint8, device=self.device)
             self.labels = None
+            self._augmenter = None        # kfnet_amd.augment.Augmenter, made by the first step(..., augment=params)
             self.shapes, self.act, self.dact, self.packs = [], [], [], []
             h, w = H, Wd
             ws_bytes = self._first_ws_bytes(batch, H, Wd, LAYERS[0][3])
@@ -363,13 +365,33 @@ class SCoordNetTrainer(object):
         self._packs_stale = True
         return lr
 
-    def step(self, frames_u8, labels):
+    def _upload_augmented(self, frames_u8, labels, params, stream):
+        """The raw batch goes to the augmenter's staging buffers; kfn_augment_batch writes self.frames and grid-sized labels
+        (output pixels (8r, 8c)), which the loss then reads at label stride 1."""
+        if self._augmenter is None:
+            from .augment import Augmenter
+            H, Wd = self.image_size
+            self._augmenter = Augmenter(self.batch, H, Wd, label_stride=8, device=self.device)
+        aug = self._augmenter
+        if labels is None:
+            raise ValueError('training needs labels')
+        fin, lin = aug.stage(frames_u8, labels)          # ValueError on grid-sized labels
+        self.labels = aug.labels_out
+        aug.launch(params, fin, lin, self.frames, self.labels, stream)
+        return 1
+
+    def step(self, frames_u8, labels, augment=None):
         """One update on a batch: frames uint8 [B,H,W,3], labels float32 [B,H,W,4] or grid-sized [B,H/8,W/8,4] =
-        (gt xyz, mask).  Returns StepStats (loss, l_measure, l_smooth, a_measure, pixels, lr of THIS step's loss, before
-        the update), read back only when accessed."""
+        (gt xyz, mask).  augment: None, or the kfnet_amd.augment.AugmentParams of this batch -- the labels must then be the
+        full-resolution ones, and forward pass, loss and smoothness weights see the augmented frames.  Returns
+        StepStats (loss, l_measure, l_smooth, a_measure, pixels, lr of THIS step's loss, before the update), read back only
+        when accessed."""
         with self.torch.cuda.device(self.device):
             stream = self._stream()
-            stride = self._upload(frames_u8, labels)
+            if augment is None:
+                stride = self._upload(frames_u8, labels)
+            else:
+                stride = self._upload_augmented(frames_u8, labels, augment, stream)
             self.forward(stream)
             self.loss_and_gradients(stride, stream)
             stats = self.stats.clone()

@@ -2,7 +2,10 @@
 frames and labels, the split of a step over its phases, and per layer the weight-gradient launch beside the forward direct
 launch as fractions of the fp32 MFMA peak.
 
-    python tools/mb_train.py [--height 480 --width 640 --batch 4 --steps 10 --warmup 3] [--layers]
+    python tools/mb_train.py [--height 480 --width 640 --batch 4 --steps 10 --warmup 3] [--layers] [--augment]
+
+--augment times the step with the augmentation of DESIGN.md 6c on: full-resolution labels, the parameters of
+kfnet_amd.augment.draw(0, step) in turn (its kernels are channel_sums_kernel and augment_kernel in a kernel trace).
 
 Under `rocprofv3 --kernel-trace --stats -- python tools/mb_train.py --steps 5` the kernel table gives the same split per
 kernel name (wgrad_mfma_kernel, conv_mfma_kernel, ...)."""
@@ -38,6 +41,7 @@ def main(argv=None):
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--layers', action='store_true', help='also time every layer\'s weight-gradient and forward launch')
+    ap.add_argument('--augment', action='store_true', help='time the step with augmentation on')
     a = ap.parse_args(argv)
     import torch
     from kfnet_amd import _lib
@@ -47,12 +51,22 @@ def main(argv=None):
     size = (a.height, a.width)
     tr = SCoordNetTrainer(initial_weights(0), image_size=size, batch=a.batch, transform=synthetic_transform())
     frames = torch.from_numpy(synthetic_sequence(a.batch, a.height, a.width)).cuda()
-    labels = torch.from_numpy(synthetic_labels(a.batch, tr.grid)).cuda()
+    labels = torch.from_numpy(synthetic_labels(a.batch, size if a.augment else tr.grid)).cuda()
+    if a.augment:
+        from kfnet_amd.augment import draw
+        count = [0]
+
+        def step():
+            count[0] += 1
+            tr.step(frames, labels, augment=draw(0, count[0]))
+    else:
+        def step():
+            tr.step(frames, labels)
     for _ in range(a.warmup):
-        tr.step(frames, labels)
-    ms = timed(torch, lambda: tr.step(frames, labels), a.steps)
-    print('%dx%d batch %d: %.2f ms per step (%.1f frames/s), %.1f M parameters' %
-          (a.height, a.width, a.batch, ms, 1e3 * a.batch / ms, tr.num_floats / 1e6))
+        step()
+    ms = timed(torch, step, a.steps)
+    print('%dx%d batch %d%s: %.2f ms per step (%.1f frames/s), %.1f M parameters' %
+          (a.height, a.width, a.batch, ', augmented' if a.augment else '', ms, 1e3 * a.batch / ms, tr.num_floats / 1e6))
     stride = tr._upload(frames, labels)
     fwd = timed(torch, tr.forward, a.steps)
     bwd = timed(torch, lambda: tr.loss_and_gradients(stride), a.steps)
