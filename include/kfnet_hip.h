@@ -50,7 +50,8 @@ extern "C" {
  * 13: the constants the reference squares in Python cross the boundary as doubles -- kfn_kalman_desc.min_uncertainty,
  * kfn_coord_loss_desc.dist_threshold / min_uncertainty and the two thresholds of kfn_eval_metrics (layout and signature
  * change: an ABI-12 host must be rebuilt); later kfn_frame_channel_sums and kfn_augment_batch (augmenting a training
- * batch), added exports that leave every ABI-13 host working, so the number stays. */
+ * batch), added exports that leave every ABI-13 host working, so the number stays; likewise kfn_decode_png_gray16,
+ * kfn_depth_labels and kfn_label_moments (training labels from depth maps and poses). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -71,6 +72,13 @@ int kfn_device_info(int device, int* cu_count, int* lds_bytes_per_cu, char* arch
 #define KFN_PNG_UNSUPPORTED 1
 #define KFN_PNG_ERROR 2
 int kfn_decode_png_rgb8(const char* const* paths, int n, int H, int W, unsigned char* dst, int* status, int threads);
+/* The same call for depth maps (7-Scenes' frame-*.depth.png): n PNG files -> dst [n][H][W] uint16 in host order.  Decodes
+ * non-interlaced colour type 0 at bit depth 16 (big-endian samples in the file), all five filter types, any IDAT split.
+ * Any other colour type or bit depth, an interlaced file or one without the PNG signature is KFN_PNG_UNSUPPORTED: its
+ * frame is untouched and the call succeeds (kfnet_amd.labels.load_depth decodes those with PIL).  A missing, truncated,
+ * corrupt or wrong-sized file is KFN_PNG_ERROR, its frame is untouched, and the call returns KFN_ERR_ARG with
+ * kfn_last_error() naming the first such file.  Host code only. */
+int kfn_decode_png_gray16(const char* const* paths, int n, int H, int W, uint16_t* dst, int* status, int threads);
 
 /* ---- host side of restoring a tf.train.Saver V2 checkpoint (ABI 12) -------------------------------------------------
  * CRC-32C (Castagnoli, reflected polynomial 0x82F63B78, ~0 pre- and post-inversion) of n bytes, extending *crc: *crc == 0
@@ -749,6 +757,55 @@ typedef struct kfn_augment_desc {
 } kfn_augment_desc;
 int kfn_augment_batch(const kfn_augment_desc* desc, const uint8_t* frames_in, const float* labels_in, uint8_t* frames_out,
                       float* labels_out, uint32_t* sums, void* stream);
+
+/* ---- training labels from depth maps and poses (added exports; the ABI number stays 13) -----------------------------
+ * A label is a function of a depth map and a camera-to-world pose.  The device evaluates the list below in
+ * unfused fp32, without division or transcendental: every derived constant arrives as a float the host has rounded once
+ * (kfnet_amd.labels.DepthCamera.descriptor).
+ *
+ * kfn_depth_labels -- depth [B,H,W] uint16 and poses [B][12] float (the rows of [R|t], camera to world) -> labels_out
+ * [B,H/stride,W/stride,ld_out] float; the columns beyond 3 are not written.  Output pixel (r, c) is colour pixel
+ * x = stride c, y = stride r (the pixel the loss reads; the PnP stage's cell (r, c) observes pixel (8c, 8r)).
+ *   depth pixel: (x, y) when registration == 0; else xd = q((float(x) - u) kx + ud), yd = q((float(y) - v) ky + vd), q =
+ *   round half away from zero, kx = float(fx_depth / fx): a gather; a pixel that leaves the depth image is invalid.
+ *   raw = depth[b][yd][xd]; valid iff raw_min <= raw <= raw_max (1 and 65534 exclude 7-Scenes' 0 and 65535).
+ *   z = float(raw) scale; X = ((float(x) - u) inv_fx) z; Y = ((float(y) - v) inv_fy) z   (depth is z, not ray length)
+ *   w_i = ((P[i][0] X + P[i][1] Y) + P[i][2] z) + P[i][3], i = 0..2
+ *   output (w_0, w_1, w_2, 1) where valid, (0, 0, 0, 0) otherwise.
+ * At stride 1 a thread owns 8 adjacent pixels (one 16-byte depth load without registration, eight 16-byte stores when
+ * ld_out is a multiple of 4); at stride 8 there is one thread per output pixel.  depth 16-byte aligned.  KFN_ERR_ARG, and
+ * nothing launched: a struct_size other than sizeof(kfn_depth_labels_desc), a stride other than 1 or 8, H or W not a
+ * multiple of 8 (or below 8), a NULL buffer, ld_out < 4, an empty validity window. */
+typedef struct kfn_depth_labels_desc {
+  int32_t struct_size;      /* = sizeof(kfn_depth_labels_desc) */
+  int32_t B, H, W;
+  int32_t stride;           /* 1 or 8 */
+  int32_t ld_out;           /* floats per output pixel, >= 4 */
+  int32_t registration;     /* 0: the depth pixel is the colour pixel */
+  int32_t raw_min, raw_max; /* 1, 65534 */
+  float u, v;               /* principal point of the colour camera */
+  float inv_fx, inv_fy;     /* float(1 / fx), float(1 / fy) */
+  float kx, ky;             /* float(fx_depth / fx), float(fy_depth / fy) */
+  float ud, vd;             /* principal point of the depth camera */
+  float scale;              /* float(0.001): millimetres to metres */
+} kfn_depth_labels_desc;
+int kfn_depth_labels(const kfn_depth_labels_desc* desc, const uint16_t* depth, const float* poses, float* labels_out,
+                     void* stream);
+
+/* kfn_label_moments -- partial [B][10] double: per frame of labels [B,h,w,ld] float, over the pixels whose mask (column
+ * 3) == 1, with d = double(p) - pivot: n, sum d (x, y, z), and sum d d^T (xx, xy, xz, yy, yz, zz).  The host adds the
+ * frames in index order and derives transform.txt (kfnet_amd.labels.decorrelating_transform); a pivot near the points
+ * (the first frame's camera centre) keeps the second moments free of cancellation.  One workgroup per frame, a fixed
+ * walk and a fixed LDS tree, no atomics: bit-identical from launch to launch.  A frame without a valid pixel gives ten
+ * zeros.  KFN_ERR_ARG, and nothing launched: a wrong struct_size, a non-positive size, ld < 4, a NULL buffer. */
+typedef struct kfn_label_moments_desc {
+  int32_t struct_size;      /* = sizeof(kfn_label_moments_desc) */
+  int32_t B, h, w;
+  int32_t ld;               /* floats per label pixel, >= 4 */
+  int32_t reserved;         /* 0 */
+  double pivot[3];
+} kfn_label_moments_desc;
+int kfn_label_moments(const kfn_label_moments_desc* desc, const float* labels, double* partial, void* stream);
 
 #ifdef __cplusplus
 }

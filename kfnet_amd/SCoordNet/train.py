@@ -14,6 +14,10 @@ network; `--loss_clip -2` reproduces it.  `--synthetic N` trains on N seeded syn
 `--augment` applies the reference's data_augmentation (KFNet/train.py:168-193) to every batch on the device, with the
 parameters kfnet_amd.augment.draw(--augment_seed, step); the whole label files are then read, not only the
 pixels the loss uses.
+`--depth` needs no label files: I then holds image_list.txt, depth_list.txt, pose_list.txt and transform.txt (what `python -m
+kfnet_amd.labels make --no_labels` writes), and every batch's labels are made on the device from its 16-bit depth maps and
+poses -- at the pixels the loss reads, or at full resolution with --augment.  The camera flags are those of
+`labels make`.
 """
 import argparse
 import os
@@ -67,6 +71,9 @@ def build_parser():
     ap.add_argument('--synthetic', type=int, default=0, help='train on this many seeded synthetic frames and labels')
     ap.add_argument('--augment', action='store_true', help='brightness, contrast, rotation and zoom / shrink per batch')
     ap.add_argument('--augment_seed', type=int, default=None, help='seed of the augmentation draws (default: --seed)')
+    ap.add_argument('--depth', action='store_true', help='make the labels on the device from depth_list.txt and pose_list.txt')
+    from ..labels import add_camera_flags
+    add_camera_flags(ap)
     return ap
 
 
@@ -84,6 +91,9 @@ def main(argv=None):
     if a.display < 1 or a.snapshot < 1 or a.batch < 1:
         print('--display, --snapshot and --batch must be >= 1', file=sys.stderr)
         return 1
+    if a.depth and a.synthetic > 0:
+        print('--depth reads depth maps and poses from --input_folder: it does not go with --synthetic', file=sys.stderr)
+        return 1
     size, grid = (a.height, a.width), (a.height // 8, a.width // 8)
     stepvalue, max_steps = schedule(a.scene, a.stepvalue, a.max_steps)
     from ..train import SCoordNetTrainer, batch_indices, restore, synthetic_labels
@@ -96,6 +106,27 @@ def main(argv=None):
 
         def batch_of(idx):
             return all_frames[idx], all_labels[idx]
+    elif a.depth:
+        from .. import labels as L
+        try:
+            camera = L.camera_of(a)
+            for name in L.LISTS + ('transform.txt',):
+                if not os.path.exists(os.path.join(a.input_folder, name)):
+                    raise ValueError('%s has no %s: --depth needs %s and transform.txt' %
+                                     (a.input_folder, name, ', '.join(L.LISTS)))
+            triples = L.read_sequence(a.input_folder)
+            transform = np.loadtxt(os.path.join(a.input_folder, 'transform.txt'), dtype=np.float32)
+            all_poses = L.read_poses([t[2] for t in triples])
+        except (OSError, ValueError) as e:
+            print(e, file=sys.stderr)
+            return 1
+        count = len(triples)
+        labeler = []          # made with the device, below
+
+        def batch_of(idx):
+            frames = modes.load_images([triples[i][0] for i in idx], size)
+            depth = L.load_depth([triples[i][1] for i in idx], size)
+            return frames, labeler[0].labels(depth, all_poses[idx])
     else:
         try:
             paths, label_paths = modes.read_inputs(a.input_folder)
@@ -140,6 +171,8 @@ def main(argv=None):
                           smooth_weight=a.smooth_weight, device='cuda:%d' % a.gpu)
     if state is not None:
         tr.load_state(state)
+    if a.depth:           # grid-sized labels (stride 8) for the loss, full-resolution ones (stride 1) for the augmentation
+        labeler.append(L.DepthLabeler(a.batch, a.height, a.width, 1 if a.augment else 8, camera, 'cuda:%d' % a.gpu))
     if a.augment:
         from ..augment import draw
         augment_seed = a.seed if a.augment_seed is None else a.augment_seed

@@ -95,6 +95,28 @@ class AugmentDesc(C.Structure):
             self.struct_size = C.sizeof(AugmentDesc)
 
 
+class DepthLabelsDesc(C.Structure):
+    """kfn_depth_labels_desc (include/kfnet_hip.h); `struct_size` is filled in here.  kfnet_amd.labels.DepthCamera.descriptor
+    derives it."""
+    _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'B', 'H', 'W', 'stride', 'ld_out', 'registration', 'raw_min', 'raw_max')] +
+                [(n, C.c_float) for n in ('u', 'v', 'inv_fx', 'inv_fy', 'kx', 'ky', 'ud', 'vd', 'scale')])
+
+    def __init__(self, *args, **kw):
+        super(DepthLabelsDesc, self).__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(DepthLabelsDesc)
+
+
+class LabelMomentsDesc(C.Structure):
+    """kfn_label_moments_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
+    _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'B', 'h', 'w', 'ld', 'reserved')] + [('pivot', C.c_double * 3)])
+
+    def __init__(self, *args, **kw):
+        super(LabelMomentsDesc, self).__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(LabelMomentsDesc)
+
+
 # name -> (restype, argtypes); every symbol declared in include/kfnet_hip.h
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 SYMBOLS = {
@@ -184,6 +206,10 @@ SYMBOLS = {
     # augmenting a training batch (added exports, ABI 13)
     'kfn_frame_channel_sums': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'kfn_augment_batch': (_i, [C.POINTER(AugmentDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
+    # training labels from depth maps and poses (added exports, ABI 13)
+    'kfn_decode_png_gray16': (_i, [C.POINTER(C.c_char_p), _i, _i, _i, _vp, C.POINTER(_i), _i]),
+    'kfn_depth_labels': (_i, [C.POINTER(DepthLabelsDesc), _vp, _vp, _vp, _vp]),
+    'kfn_label_moments': (_i, [C.POINTER(LabelMomentsDesc), _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -33,6 +33,8 @@ EXTRA = {
     'kfn_train_loss.hip': ['-ffp-contract=off'],
     # the augmentation's index arithmetic and interpolation are a list of rounded fp32 operations
     'kfn_augment.hip': ['-ffp-contract=off'],
+    # labels from depth maps: back-projection and pose as a list of rounded fp32 operations
+    'kfn_labels.hip': ['-ffp-contract=off'],
 }
 
 

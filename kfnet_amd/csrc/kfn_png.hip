@@ -12,6 +12,10 @@
 // 0 (gray), 2 (RGB), 3 (palette), 4 (gray + alpha), 6 (RGBA); alpha is dropped and gray replicated, as decode_png(channels=3)
 // / PIL's convert('RGB') do.  Interlaced or 16-bit files, and files without the PNG signature, are reported per file as
 // KFN_PNG_UNSUPPORTED and the host decodes those with PIL; a corrupt or wrong-sized file is an error that names the file.  Host code only: no device access.
+//
+// kfn_decode_png_gray16 is the same stream for depth maps (7-Scenes' frame-*.depth.png): non-interlaced colour
+// type 0 at bit depth 16 -> uint16 in host order; every other kind of file is KFN_PNG_UNSUPPORTED.  The two decoders share
+// the file parsing (load_png), the inflate step and the scanline filters.
 #include "kfn_common.h"
 
 #include <zlib.h>
@@ -62,7 +66,16 @@ void unfilter_row(int type, unsigned char* cur, const unsigned char* prev, int b
   }
 }
 
-PngResult decode_one(const char* path, int H, int W, unsigned char* dst) {
+struct PngFile {
+  int depth = 0, ctype = -1, interlace = 0;
+  unsigned char palette[256 * 3] = {0};      // (an index past PLTE's entries reads black, as libpng's readers do)
+  int n_pal = 0;
+  std::vector<unsigned char> idat;
+};
+
+// Reads the file, checks signature, chunk structure, the CRCs of the critical chunks and the image size; on KFN_PNG_OK
+// `png` holds IHDR's fields, the palette and the concatenated IDAT stream.
+PngResult load_png(const char* path, int H, int W, PngFile& png) {
   FILE* f = std::fopen(path, "rb");
   if (!f) return {KFN_PNG_ERROR, std::string("cannot open ") + path};
   std::vector<unsigned char> file;
@@ -80,10 +93,13 @@ PngResult decode_one(const char* path, int H, int W, unsigned char* dst) {
   // (not a PNG at all -- a JPEG in the list, say: the host's general-purpose decoder decides, as it did before this file existed)
   if (std::memcmp(file.data(), sig, 8) != 0) return {KFN_PNG_UNSUPPORTED, std::string(path) + " is not a PNG file (signature)"};
   size_t pos = 8;
-  int w = 0, h = 0, depth = 0, ctype = -1, interlace = 0;
-  unsigned char palette[256 * 3] = {0};      // (an index past PLTE's entries reads black, as libpng's readers do)
-  int n_pal = 0;
-  std::vector<unsigned char> idat;
+  int w = 0, h = 0;
+  int& depth = png.depth;
+  int& ctype = png.ctype;
+  int& interlace = png.interlace;
+  unsigned char* palette = png.palette;
+  int& n_pal = png.n_pal;
+  std::vector<unsigned char>& idat = png.idat;
   idat.reserve(file.size());
   bool seen_end = false, seen_hdr = false;
   while (pos + 12 <= file.size() && !seen_end) {
@@ -123,6 +139,35 @@ PngResult decode_one(const char* path, int H, int W, unsigned char* dst) {
     std::snprintf(b, sizeof b, "%s is %dx%d, expected %dx%d", path, h, w, H, W);
     return {KFN_PNG_ERROR, b};
   }
+  return {KFN_PNG_OK, std::string()};
+}
+
+// inflates the IDAT stream into raw [H][1 + row_bytes] (filter byte, then the filtered line)
+PngResult inflate_rows(const char* path, std::vector<unsigned char>& idat, std::vector<unsigned char>& raw) {
+  z_stream zs;
+  std::memset(&zs, 0, sizeof zs);
+  if (inflateInit(&zs) != Z_OK) return {KFN_PNG_ERROR, "inflateInit failed"};
+  zs.next_in = idat.data();
+  zs.avail_in = (uInt)idat.size();
+  zs.next_out = raw.data();
+  zs.avail_out = (uInt)raw.size();
+  const int rc = inflate(&zs, Z_FINISH);
+  const size_t produced = raw.size() - zs.avail_out;
+  inflateEnd(&zs);
+  // (Z_BUF_ERROR with the output full = data behind the image: tolerated like libpng's "too much image data" warning)
+  if (!(rc == Z_STREAM_END || (rc == Z_BUF_ERROR && produced == raw.size())) || produced != raw.size())
+    return {KFN_PNG_ERROR, std::string(path) + ": corrupt or truncated image data"};
+  return {KFN_PNG_OK, std::string()};
+}
+
+PngResult decode_one(const char* path, int H, int W, unsigned char* dst) {
+  PngFile png;
+  {
+    PngResult r = load_png(path, H, W, png);
+    if (r.status != KFN_PNG_OK) return r;
+  }
+  const int depth = png.depth, ctype = png.ctype, interlace = png.interlace, n_pal = png.n_pal;
+  const unsigned char* palette = png.palette;
   int channels;
   switch (ctype) {
     case 0: channels = 1; break;
@@ -140,19 +185,8 @@ PngResult decode_one(const char* path, int H, int W, unsigned char* dst) {
   const int bpp = (channels * depth + 7) / 8 > 0 ? (channels * depth + 7) / 8 : 1;
   std::vector<unsigned char> raw((size_t)H * (row_bytes + 1));
   {
-    z_stream zs;
-    std::memset(&zs, 0, sizeof zs);
-    if (inflateInit(&zs) != Z_OK) return {KFN_PNG_ERROR, "inflateInit failed"};
-    zs.next_in = idat.data();
-    zs.avail_in = (uInt)idat.size();
-    zs.next_out = raw.data();
-    zs.avail_out = (uInt)raw.size();
-    const int rc = inflate(&zs, Z_FINISH);
-    const size_t produced = raw.size() - zs.avail_out;
-    inflateEnd(&zs);
-    // (Z_BUF_ERROR with the output full = data behind the image: tolerated like libpng's "too much image data" warning)
-    if (!(rc == Z_STREAM_END || (rc == Z_BUF_ERROR && produced == raw.size())) || produced != raw.size())
-      return {KFN_PNG_ERROR, std::string(path) + ": corrupt or truncated image data"};
+    PngResult r = inflate_rows(path, png.idat, raw);
+    if (r.status != KFN_PNG_OK) return r;
   }
   const unsigned char* prev = nullptr;
   for (int y = 0; y < H; ++y) {
@@ -190,28 +224,51 @@ PngResult decode_one(const char* path, int H, int W, unsigned char* dst) {
   return {KFN_PNG_OK, std::string()};
 }
 
-}  // namespace
+// colour type 0 at bit depth 16 only: big-endian samples -> uint16 in host order
+PngResult decode_one_gray16(const char* path, int H, int W, unsigned char* dst_bytes) {
+  PngFile png;
+  {
+    PngResult r = load_png(path, H, W, png);
+    if (r.status != KFN_PNG_OK) return r;
+  }
+  if (png.ctype != 0 || png.depth != 16 || png.interlace != 0)
+    return {KFN_PNG_UNSUPPORTED, std::string(path) + ": not a non-interlaced 16-bit gray PNG"};
+  const int row_bytes = W * 2;
+  std::vector<unsigned char> raw((size_t)H * (row_bytes + 1));
+  {
+    PngResult r = inflate_rows(path, png.idat, raw);
+    if (r.status != KFN_PNG_OK) return r;
+  }
+  // every filter byte is checked before the first sample is written: a file in error leaves its frame as it was
+  for (int y = 0; y < H; ++y)
+    if (raw[(size_t)y * (row_bytes + 1)] > 4) return {KFN_PNG_ERROR, std::string(path) + ": unknown filter type"};
+  uint16_t* dst = reinterpret_cast<uint16_t*>(dst_bytes);
+  const unsigned char* prev = nullptr;
+  for (int y = 0; y < H; ++y) {
+    unsigned char* line = raw.data() + (size_t)y * (row_bytes + 1);
+    unsigned char* cur = line + 1;
+    unfilter_row(line[0], cur, prev, 2, row_bytes);
+    prev = cur;
+    uint16_t* out = dst + (size_t)y * W;
+    for (int x = 0; x < W; ++x) out[x] = (uint16_t)(((unsigned)cur[2 * x] << 8) | cur[2 * x + 1]);
+  }
+  return {KFN_PNG_OK, std::string()};
+}
 
-// Decodes n PNG files into dst [n][H][W][3] (uint8 RGB) on `threads` host threads (<= 0: one per file, at most the
-// hardware's).  status [n] (optional) receives KFN_PNG_OK / KFN_PNG_UNSUPPORTED (interlaced or 16-bit: the caller's
-// fallback decoder should take that file; its frame in dst is untouched) / KFN_PNG_ERROR.  Returns KFN_OK when no file
-// is in error (unsupported files do not fail the call), else KFN_ERR_ARG with kfn_last_error() naming the first bad file.
-extern "C" int kfn_decode_png_rgb8(const char* const* paths, int n, int H, int W, unsigned char* dst, int* status, int threads) {
-  KFN_REQUIRE(n >= 0 && (n == 0 || (paths && dst)) && H > 0 && W > 0, "kfn_decode_png_rgb8: bad argument (n=%d, H=%d, W=%d)", n, H, W);
-  if (n == 0) return KFN_OK;
-  for (int i = 0; i < n; ++i) KFN_REQUIRE(paths[i] != nullptr, "kfn_decode_png_rgb8: paths[%d] is null", i);
+// the files of one call on `threads` host threads; frame i starts at dst + i * frame_bytes
+int decode_files(const char* who, PngResult (*decode)(const char*, int, int, unsigned char*), const char* const* paths, int n,
+                 int H, int W, unsigned char* dst, size_t frame, int* status, int threads) {
   std::vector<PngResult> res((size_t)n);
   int nt = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
   if (nt < 1) nt = 1;
   if (nt > n) nt = n;
   std::atomic<int> next{0};
-  const size_t frame = (size_t)H * W * 3;
   auto worker = [&]() {
     for (;;) {
       const int i = next.fetch_add(1, std::memory_order_relaxed);
       if (i >= n) return;
       try {
-        res[(size_t)i] = decode_one(paths[i], H, W, dst + (size_t)i * frame);
+        res[(size_t)i] = decode(paths[i], H, W, dst + (size_t)i * frame);
       } catch (const std::exception& e) {      // (std::bad_alloc: no exception crosses the C ABI or a thread boundary)
         res[(size_t)i] = {KFN_PNG_ERROR, std::string(paths[i]) + ": " + e.what()};
       }
@@ -231,6 +288,29 @@ extern "C" int kfn_decode_png_rgb8(const char* const* paths, int n, int H, int W
     if (status) status[i] = res[(size_t)i].status;
     if (res[(size_t)i].status == KFN_PNG_ERROR && first_bad < 0) first_bad = i;
   }
-  if (first_bad >= 0) return kfn::fail(KFN_ERR_ARG, "kfn_decode_png_rgb8: %s", res[(size_t)first_bad].what.c_str());
+  if (first_bad >= 0) return kfn::fail(KFN_ERR_ARG, "%s: %s", who, res[(size_t)first_bad].what.c_str());
   return KFN_OK;
+}
+
+}  // namespace
+
+// Decodes n PNG files into dst [n][H][W][3] (uint8 RGB) on `threads` host threads (<= 0: one per file, at most the
+// hardware's).  status [n] (optional) receives KFN_PNG_OK / KFN_PNG_UNSUPPORTED (interlaced or 16-bit: the caller's
+// fallback decoder should take that file; its frame in dst is untouched) / KFN_PNG_ERROR.  Returns KFN_OK when no file
+// is in error (unsupported files do not fail the call), else KFN_ERR_ARG with kfn_last_error() naming the first bad file.
+extern "C" int kfn_decode_png_rgb8(const char* const* paths, int n, int H, int W, unsigned char* dst, int* status, int threads) {
+  KFN_REQUIRE(n >= 0 && (n == 0 || (paths && dst)) && H > 0 && W > 0, "kfn_decode_png_rgb8: bad argument (n=%d, H=%d, W=%d)", n, H, W);
+  if (n == 0) return KFN_OK;
+  for (int i = 0; i < n; ++i) KFN_REQUIRE(paths[i] != nullptr, "kfn_decode_png_rgb8: paths[%d] is null", i);
+  return decode_files("kfn_decode_png_rgb8", decode_one, paths, n, H, W, dst, (size_t)H * W * 3, status, threads);
+}
+
+// The same call for depth maps: dst [n][H][W] uint16.  Only non-interlaced 16-bit gray files are decoded; any other PNG (and
+// a file without the signature) is KFN_PNG_UNSUPPORTED with its frame untouched.
+extern "C" int kfn_decode_png_gray16(const char* const* paths, int n, int H, int W, uint16_t* dst, int* status, int threads) {
+  KFN_REQUIRE(n >= 0 && (n == 0 || (paths && dst)) && H > 0 && W > 0, "kfn_decode_png_gray16: bad argument (n=%d, H=%d, W=%d)", n, H, W);
+  if (n == 0) return KFN_OK;
+  for (int i = 0; i < n; ++i) KFN_REQUIRE(paths[i] != nullptr, "kfn_decode_png_gray16: paths[%d] is null", i);
+  return decode_files("kfn_decode_png_gray16", decode_one_gray16, paths, n, H, W, reinterpret_cast<unsigned char*>(dst),
+                      (size_t)H * W * 2, status, threads);
 }

@@ -2,10 +2,12 @@
 frames and labels, the split of a step over its phases, and per layer the weight-gradient launch beside the forward direct
 launch as fractions of the fp32 MFMA peak.
 
-    python tools/mb_train.py [--height 480 --width 640 --batch 4 --steps 10 --warmup 3] [--layers] [--augment]
+    python tools/mb_train.py [--height 480 --width 640 --batch 4 --steps 10 --warmup 3] [--layers] [--augment] [--depth]
 
 --augment times the step with the augmentation of DESIGN.md 6c on: full-resolution labels, the parameters of
 kfnet_amd.augment.draw(0, step) in turn (its kernels are channel_sums_kernel and augment_kernel in a kernel trace).
+--depth makes every step's labels on the device from synthetic depth maps and poses that stay there (stride 8,
+or stride 1 with --augment; depth_labels_grid_kernel / depth_labels_full_kernel in a kernel trace).
 
 Under `rocprofv3 --kernel-trace --stats -- python tools/mb_train.py --steps 5` the kernel table gives the same split per
 kernel name (wgrad_mfma_kernel, conv_mfma_kernel, ...)."""
@@ -42,6 +44,7 @@ def main(argv=None):
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--layers', action='store_true', help='also time every layer\'s weight-gradient and forward launch')
     ap.add_argument('--augment', action='store_true', help='time the step with augmentation on')
+    ap.add_argument('--depth', action='store_true', help='make the labels of every step from depth maps and poses')
     a = ap.parse_args(argv)
     import torch
     from kfnet_amd import _lib
@@ -52,21 +55,34 @@ def main(argv=None):
     tr = SCoordNetTrainer(initial_weights(0), image_size=size, batch=a.batch, transform=synthetic_transform())
     frames = torch.from_numpy(synthetic_sequence(a.batch, a.height, a.width)).cuda()
     labels = torch.from_numpy(synthetic_labels(a.batch, size if a.augment else tr.grid)).cuda()
+    if a.depth:
+        from kfnet_amd.labels import DepthLabeler, pose_rows
+        rng = np.random.default_rng(0)
+        depth = torch.from_numpy(rng.integers(500, 4000, size=(a.batch,) + size).astype(np.uint16).view(np.int16)).cuda()
+        poses = torch.from_numpy(pose_rows(np.tile(np.eye(4), (a.batch, 1, 1)))).cuda()
+        labeler = DepthLabeler(a.batch, a.height, a.width, 1 if a.augment else 8)
+
+        def labels_of_step():
+            return labeler.labels(depth, poses)
+    else:
+        def labels_of_step():
+            return labels
     if a.augment:
         from kfnet_amd.augment import draw
         count = [0]
 
         def step():
             count[0] += 1
-            tr.step(frames, labels, augment=draw(0, count[0]))
+            tr.step(frames, labels_of_step(), augment=draw(0, count[0]))
     else:
         def step():
-            tr.step(frames, labels)
+            tr.step(frames, labels_of_step())
     for _ in range(a.warmup):
         step()
     ms = timed(torch, step, a.steps)
     print('%dx%d batch %d%s: %.2f ms per step (%.1f frames/s), %.1f M parameters' %
-          (a.height, a.width, a.batch, ', augmented' if a.augment else '', ms, 1e3 * a.batch / ms, tr.num_floats / 1e6))
+          (a.height, a.width, a.batch, (', augmented' if a.augment else '') + (', labels from depth' if a.depth else ''), ms,
+           1e3 * a.batch / ms, tr.num_floats / 1e6))
     stride = tr._upload(frames, labels)
     fwd = timed(torch, tr.forward, a.steps)
     bwd = timed(torch, lambda: tr.loss_and_gradients(stride), a.steps)
