@@ -20,12 +20,9 @@ poses -- at the pixels the loss reads, or at full resolution with
 `labels make`.
 """
 import argparse
-import os
 import sys
 import time
 from datetime import datetime
-
-import numpy as np
 
 from .. import modes
 
@@ -85,80 +82,19 @@ def main(argv=None):
     if not a.model_folder:
         print('--model_folder is required: the snapshots go there', file=sys.stderr)
         return 1
-    if a.height % 8 or a.width % 8 or a.height <= 0 or a.width <= 0:
-        print('--height and --width must be multiples of 8', file=sys.stderr)
-        return 1
     if a.display < 1 or a.snapshot < 1 or a.batch < 1:
         print('--display, --snapshot and --batch must be >= 1', file=sys.stderr)
         return 1
-    if a.depth and a.synthetic > 0:
-        print('--depth reads depth maps and poses from --input_folder: it does not go with --synthetic', file=sys.stderr)
-        return 1
-    size, grid = (a.height, a.width), (a.height // 8, a.width // 8)
     stepvalue, max_steps = schedule(a.scene, a.stepvalue, a.max_steps)
-    from ..train import SCoordNetTrainer, batch_indices, restore, synthetic_labels
-    if a.synthetic > 0:
-        from ..synth import synthetic_sequence, synthetic_transform
-        count = a.synthetic
-        all_frames = synthetic_sequence(count, a.height, a.width)
-        all_labels = synthetic_labels(count, size if a.augment else grid)
-        transform = synthetic_transform()
-
-        def batch_of(idx):
-            return all_frames[idx], all_labels[idx]
-    elif a.depth:
-        from .. import labels as L
-        try:
-            camera = L.camera_of(a)
-            for name in L.LISTS + ('transform.txt',):
-                if not os.path.exists(os.path.join(a.input_folder, name)):
-                    raise ValueError('%s has no %s: --depth needs %s and transform.txt' %
-                                     (a.input_folder, name, ', '.join(L.LISTS)))
-            triples = L.read_sequence(a.input_folder)
-            transform = np.loadtxt(os.path.join(a.input_folder, 'transform.txt'), dtype=np.float32)
-            all_poses = L.read_poses([t[2] for t in triples])
-        except (OSError, ValueError) as e:
-            print(e, file=sys.stderr)
-            return 1
-        count = len(triples)
-        labeler = []          # made with the device, below
-
-        def batch_of(idx):
-            frames = modes.load_images([triples[i][0] for i in idx], size)
-            depth = L.load_depth([triples[i][1] for i in idx], size)
-            return frames, labeler[0].labels(depth, all_poses[idx])
-    else:
-        try:
-            paths, label_paths = modes.read_inputs(a.input_folder)
-            if label_paths is None:
-                raise ValueError('%s has no label_list.txt: training needs labels' % a.input_folder)
-            transform = np.loadtxt(os.path.join(a.input_folder, 'transform.txt'), dtype=np.float32)
-        except (OSError, ValueError) as e:
-            print(e, file=sys.stderr)
-            return 1
-        count = len(paths)
-        from ..KFNet.metrics import read_label_grid
-
-        def read_label(path):
-            if not a.augment:
-                return read_label_grid(path, size, grid)
-            lab = np.fromfile(path, dtype=np.float32)      # the whole label: augmentation interpolates between its pixels
-            if lab.size != size[0] * size[1] * 4:
-                raise ValueError('%s holds %d floats, --augment needs the full-resolution label of %d' %
-                                 (path, lab.size, size[0] * size[1] * 4))
-            return lab.reshape(size[0], size[1], 4)
-
-        if a.augment:
-            try:
-                read_label(label_paths[0])
-            except (OSError, ValueError) as e:
-                print(e, file=sys.stderr)
-                return 1
-
-        def batch_of(idx):
-            frames = modes.load_images([paths[i] for i in idx], size)
-            return frames, np.stack([read_label(label_paths[i]) for i in idx])
-
+    from ..batches import open_source
+    from ..staging import check_size
+    from ..train import SCoordNetTrainer, batch_indices, restore
+    try:
+        check_size(a.height, a.width, '--height and --width')
+        source = open_source(a, SCoordNetTrainer.needs_full_resolution(a.augment))
+    except (OSError, ValueError) as e:
+        print(e, file=sys.stderr)
+        return 1
     W, state, step = restore(a.model_folder)
     if W is None:
         from ..weights import initial_weights
@@ -166,20 +102,17 @@ def main(argv=None):
         print('no snapshot in %s: starting from untrained weights (seed %d)' % (a.model_folder, a.seed))
     import torch
     torch.cuda.set_device(a.gpu)
-    tr = SCoordNetTrainer(W, image_size=size, batch=a.batch, transform=transform, base_lr=a.base_lr, gamma=a.gamma,
-                          stepvalue=stepvalue, weight_decay=a.weight_decay, loss_clip=a.loss_clip,
+    tr = SCoordNetTrainer(W, image_size=(a.height, a.width), batch=a.batch, transform=source.transform, base_lr=a.base_lr,
+                          gamma=a.gamma, stepvalue=stepvalue, weight_decay=a.weight_decay, loss_clip=a.loss_clip,
                           smooth_weight=a.smooth_weight, device='cuda:%d' % a.gpu)
     if state is not None:
         tr.load_state(state)
-    if a.depth:           # grid-sized labels (stride 8) for the loss, full-resolution ones (stride 1) for the augmentation
-        labeler.append(L.DepthLabeler(a.batch, a.height, a.width, 1 if a.augment else 8, camera, 'cuda:%d' % a.gpu))
-    if a.augment:
-        from ..augment import draw
-        augment_seed = a.seed if a.augment_seed is None else a.augment_seed
     tr.global_step = step if a.reset_step < 0 else a.reset_step
+    from ..augment import draw
+    augment_seed = a.seed if a.augment_seed is None else a.augment_seed
     print('----------------------------------')
     print('scene: ', a.scene)
-    print('training image number: ', count)
+    print('training image number: ', source.count)
     print('batch size: ', a.batch)
     print('step value: ', stepvalue)
     print('max steps: ', max_steps)
@@ -187,12 +120,14 @@ def main(argv=None):
     print('----------------------------------')
     while tr.global_step < max_steps:
         t0 = time.time()
-        frames, labels = batch_of(batch_indices(tr.global_step, a.batch, count, a.shuffle, a.seed))
-        stats = tr.step(frames, labels, augment=draw(augment_seed, tr.global_step)) if a.augment else tr.step(frames, labels)
+        params = draw(augment_seed, tr.global_step) if a.augment else None
+        indices = batch_indices(tr.global_step, a.batch, source.count, a.shuffle, a.seed)
+        frames, labels = source.batch(indices, tr.needs_full_resolution(a.augment))
+        stats = tr.step(frames, labels, augment=params)
         s = tr.global_step
         if s % a.display == 0 or s == max_steps:
             line = dict(stats)           # the read-back waits for the step
-            print(format_line(datetime.now(), (s * a.batch) // count, s, max_steps, line, time.time() - t0), flush=True)
+            print(format_line(datetime.now(), (s * a.batch) // source.count, s, max_steps, line, time.time() - t0), flush=True)
         if s % a.snapshot == 0 or s == max_steps:
             print('snapshot: %s, %s' % tr.save(a.model_folder, s), flush=True)
     torch.cuda.synchronize()

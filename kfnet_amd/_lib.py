@@ -33,19 +33,24 @@ class KfnError(RuntimeError):
     pass
 
 
-class ConvDesc(C.Structure):
-    """kfn_conv_desc (include/kfnet_hip.h).  `struct_size` is filled in here: the library copies that many bytes and
-    reads every later field as 0, so the struct can grow at its end without breaking older hosts
-    (tests/test_host_logic.py::test_conv_desc_matches_header_and_integration_doc keeps the three field lists equal)."""
+class SizedStructure(C.Structure):
+    """A descriptor whose first field is `struct_size`: filled in here with the size of the concrete structure unless the
+    caller set it.  The library copies that many bytes and reads every later field as 0, so such a struct can grow at its
+    end without breaking older hosts."""
+
+    def __init__(self, *args, **kw):
+        super(SizedStructure, self).__init__(*args, **kw)
+        if not self.struct_size:
+            self.struct_size = C.sizeof(type(self))
+
+
+class ConvDesc(SizedStructure):
+    """kfn_conv_desc (include/kfnet_hip.h); tests/test_host_logic.py::test_conv_desc_matches_header_and_integration_doc
+    keeps its field list equal to the header's and INTEGRATION.md's."""
     _fields_ = [(n, C.c_int32) for n in (
         'struct_size', 'N', 'H', 'W', 'Cin', 'ldx', 'Cout', 'cout_pad', 'ldy', 'kh', 'kw', 'stride',
         'transposed', 'relu', 'epilogue', 'config', 'operand_dtype', 'wino_order', 'wino_form',
         'x_dtype', 'y_dtype', 'k_step', 'weights_path', 'x_layout', 'y_layout')]
-
-    def __init__(self, *args, **kw):
-        super(ConvDesc, self).__init__(*args, **kw)
-        if not self.struct_size:
-            self.struct_size = C.sizeof(ConvDesc)
 
 
 class KalmanDesc(C.Structure):
@@ -55,20 +60,15 @@ class KalmanDesc(C.Structure):
                 ('has_transform', C.c_int32), ('transform', C.c_float * 12)]
 
 
-class PnPDesc(C.Structure):
+class PnPDesc(SizedStructure):
     """kfn_pnp_desc (include/kfnet_hip.h, ABI 11); `struct_size` is filled in here, as for ConvDesc."""
     _fields_ = [('struct_size', C.c_int32), ('B', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('ld', C.c_int32),
                 ('t0', C.c_int32), ('seed', C.c_uint32), ('hypotheses', C.c_int32), ('refine_iters', C.c_int32),
                 ('min_points', C.c_int32), ('fx', C.c_float), ('fy', C.c_float), ('u', C.c_float), ('v', C.c_float),
                 ('cell_stride', C.c_int32), ('min_confidence', C.c_float), ('inlier_px', C.c_float)]
 
-    def __init__(self, *args, **kw):
-        super(PnPDesc, self).__init__(*args, **kw)
-        if not self.struct_size:
-            self.struct_size = C.sizeof(PnPDesc)
 
-
-class CoordLossDesc(C.Structure):
+class CoordLossDesc(SizedStructure):
     """kfn_coord_loss_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
     _fields_ = [('struct_size', C.c_int32), ('B', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('ld_pred', C.c_int32),
                 ('ld_dpred', C.c_int32), ('label_stride', C.c_int32), ('img_stride', C.c_int32),
@@ -76,45 +76,25 @@ class CoordLossDesc(C.Structure):
                 ('loss_clip', C.c_float), ('smooth_weight', C.c_float), ('dist_threshold', C.c_double),
                 ('min_uncertainty', C.c_double)]
 
-    def __init__(self, *args, **kw):
-        super(CoordLossDesc, self).__init__(*args, **kw)
-        if not self.struct_size:
-            self.struct_size = C.sizeof(CoordLossDesc)
 
-
-class AugmentDesc(C.Structure):
+class AugmentDesc(SizedStructure):
     """kfn_augment_desc (include/kfnet_hip.h); `struct_size` is filled in here.  kfnet_amd.augment.descriptor derives it."""
     _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'B', 'H', 'W', 'label_stride', 'mode', 'has_rotation', 'has_colour')] +
                 [('rot', C.c_float * 6)] + [(n, C.c_float) for n in ('y0', 'dy', 'x0', 'dx')] +
                 [(n, C.c_int32) for n in ('new_h', 'new_w', 'off_y', 'off_x')] +
                 [(n, C.c_float) for n in ('scale_y', 'scale_x', 'delta', 'factor')])
 
-    def __init__(self, *args, **kw):
-        super(AugmentDesc, self).__init__(*args, **kw)
-        if not self.struct_size:
-            self.struct_size = C.sizeof(AugmentDesc)
 
-
-class DepthLabelsDesc(C.Structure):
+class DepthLabelsDesc(SizedStructure):
     """kfn_depth_labels_desc (include/kfnet_hip.h); `struct_size` is filled in here.  kfnet_amd.labels.DepthCamera.descriptor
     derives it."""
     _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'B', 'H', 'W', 'stride', 'ld_out', 'registration', 'raw_min', 'raw_max')] +
                 [(n, C.c_float) for n in ('u', 'v', 'inv_fx', 'inv_fy', 'kx', 'ky', 'ud', 'vd', 'scale')])
 
-    def __init__(self, *args, **kw):
-        super(DepthLabelsDesc, self).__init__(*args, **kw)
-        if not self.struct_size:
-            self.struct_size = C.sizeof(DepthLabelsDesc)
 
-
-class LabelMomentsDesc(C.Structure):
+class LabelMomentsDesc(SizedStructure):
     """kfn_label_moments_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
     _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'B', 'h', 'w', 'ld', 'reserved')] + [('pivot', C.c_double * 3)])
-
-    def __init__(self, *args, **kw):
-        super(LabelMomentsDesc, self).__init__(*args, **kw)
-        if not self.struct_size:
-            self.struct_size = C.sizeof(LabelMomentsDesc)
 
 
 # name -> (restype, argtypes); every symbol declared in include/kfnet_hip.h

@@ -14,6 +14,7 @@ import math
 import numpy as np
 
 from . import _lib
+from .staging import check_size, current_stream, stage
 
 TRANSLATE, ENLARGE, SHRINK = 0, 1, 2
 MAX_ANGLE = 30.0              # degrees, KFNet/util.py:92,110
@@ -91,8 +92,9 @@ class Augmenter(object):
 
     def __init__(self, B, H, W, label_stride=8, device='cuda:0'):
         import torch
-        if B < 1 or H < 8 or W < 8 or H % 8 or W % 8:
-            raise ValueError('augmentation needs a height and width that are multiples of 8, got %dx%dx%d' % (B, H, W))
+        if B < 1:
+            raise ValueError('batch must be >= 1')
+        check_size(H, W, 'the height and width of an augmented batch')
         if label_stride not in (1, 8):
             raise ValueError('label_stride must be 1 or 8')
         self.lib = _lib.load()
@@ -116,12 +118,10 @@ class Augmenter(object):
         """Copies a batch into the staging buffers; returns (frames, labels or None) on the device."""
         torch = self.torch
         B, H, W = self.shape
-        fr = frames_u8 if torch.is_tensor(frames_u8) else torch.from_numpy(np.ascontiguousarray(frames_u8))
-        if tuple(fr.shape) != (B, H, W, 3) or fr.dtype != torch.uint8:
-            raise ValueError('frames must be uint8 [%d,%d,%d,3], got %s %s' % (B, H, W, fr.dtype, tuple(fr.shape)))
-        self.frames_in.copy_(fr, non_blocking=True)
+        stage(self.frames_in, frames_u8, torch.uint8, (B, H, W, 3), 'frames')
         if labels is None:
             return self.frames_in, None
+        # labels of any float type are converted, and the buffer is made only for labels that pass: torch's own copy
         lb = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.float32))
         if tuple(lb.shape) != (B, H, W, 4):
             raise ValueError('augmentation needs full-resolution labels float32 [%d,%d,%d,4], got %s: interpolating an '
@@ -137,5 +137,5 @@ class Augmenter(object):
             if self.frames_out is None:
                 self.frames_out = self.torch.zeros_like(self.frames_in)
             lout = None if lin is None else self.labels_out
-            self.launch(params, fin, lin, self.frames_out, lout, self.torch.cuda.current_stream(self.device).cuda_stream)
+            self.launch(params, fin, lin, self.frames_out, lout, current_stream(self.device))
         return self.frames_out, lout

@@ -29,6 +29,16 @@ BACKBONE = (
 HEAD = ('prediction', 1, 4, 1)   # 3 scene coordinates + log-uncertainty, no activation
 
 
+def layers():
+    """(name, kernel size, Cin, Cout, stride, relu) per layer, Cin chained from the image's 3 channels: what the training
+    path (kfnet_amd.train.LAYERS) and the variable shapes (kfnet_amd.weights.variable_specs) are built from."""
+    out, cin = [], 3
+    for name, ksize, channels, stride in BACKBONE + (HEAD,):
+        out.append((name, ksize, cin, channels, stride, name != HEAD[0]))
+        cin = channels
+    return out
+
+
 class SCoordNet(Network):
     def __init__(self, inputs, is_training, focal_x, focal_y, u, v, dropout_rate=0.5, seed=None, reuse=False):
         # like the reference, the graph is built (setup) before the camera fields are stored

@@ -30,6 +30,7 @@ import sys
 import numpy as np
 
 from . import _lib
+from .staging import check_size, current_stream
 from .tools.io import read_lines
 
 LISTS = ('image_list.txt', 'depth_list.txt', 'pose_list.txt')
@@ -87,8 +88,9 @@ class DepthLabeler(object):
 
     def __init__(self, batch, H, W, stride=8, camera=None, device='cuda:0'):
         import torch
-        if batch < 1 or H < 8 or W < 8 or H % 8 or W % 8:
-            raise ValueError('labels need a height and width that are multiples of 8, got %dx%dx%d' % (batch, H, W))
+        if batch < 1:
+            raise ValueError('batch must be >= 1')
+        check_size(H, W, 'the height and width of depth labels')
         if stride not in (1, 8):
             raise ValueError('stride must be 1 or 8')
         self.lib = _lib.load()
@@ -99,9 +101,6 @@ class DepthLabeler(object):
             self.depth = torch.zeros((batch, H, W), dtype=torch.int16, device=self.device)     # the uint16 bits
             self.poses = torch.zeros((batch, 12), dtype=torch.float32, device=self.device)
             self.out = torch.zeros((batch, H // stride, W // stride, 4), dtype=torch.float32, device=self.device)
-
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
 
     def labels(self, depth_u16, poses):
         torch = self.torch
@@ -130,7 +129,7 @@ class DepthLabeler(object):
             self.poses[:n].copy_(ps, non_blocking=True)
             d = self.camera.descriptor(n, H, W, self.stride)
             _lib.check(self.lib.kfn_depth_labels(C.byref(d), self.depth.data_ptr(), self.poses.data_ptr(), self.out.data_ptr(),
-                                                 self._stream()), 'kfn_depth_labels')
+                                                 current_stream(self.device)), 'kfn_depth_labels')
         return self.out[:n]
 
     def moments(self, labels, pivot):
@@ -145,8 +144,8 @@ class DepthLabeler(object):
         d.pivot = (C.c_double * 3)(*[float(x) for x in pivot])
         with torch.cuda.device(self.device):
             partial = torch.zeros((n, 10), dtype=torch.float64, device=self.device)
-            _lib.check(self.lib.kfn_label_moments(C.byref(d), labels.data_ptr(), partial.data_ptr(), self._stream()),
-                       'kfn_label_moments')
+            _lib.check(self.lib.kfn_label_moments(C.byref(d), labels.data_ptr(), partial.data_ptr(),
+                                                  current_stream(self.device)), 'kfn_label_moments')
         return partial
 
 
@@ -314,13 +313,11 @@ def make(a):
     if not a.output_folder:
         print('labels make: --output_folder is required', file=sys.stderr)
         return 1
-    if a.height % 8 or a.width % 8 or a.height <= 0 or a.width <= 0:
-        print('--height and --width must be multiples of 8', file=sys.stderr)
-        return 1
     if a.batch < 1:
         print('--batch must be >= 1', file=sys.stderr)
         return 1
     try:
+        check_size(a.height, a.width, '--height and --width')
         camera = camera_of(a)
         triples = []
         for s in a.sequence:

@@ -24,13 +24,10 @@ import os
 
 import numpy as np
 
-from . import _lib
+from . import _lib, staging
+from .cnn_wrapper.SCoordNet import layers
 
-# cnn_wrapper/SCoordNet.py:21-32: (name, kernel, Cin, Cout, stride, relu)
-LAYERS = [('conv1a', 3, 3, 64, 1, True), ('conv1b', 3, 64, 64, 1, True), ('conv2a', 3, 64, 256, 2, True),
-          ('conv2b', 3, 256, 256, 1, True), ('conv3a', 3, 256, 512, 2, True), ('conv3b', 3, 512, 512, 1, True),
-          ('conv4a', 3, 512, 1024, 2, True), ('conv4b', 3, 1024, 1024, 1, True), ('conv5', 3, 1024, 512, 1, True),
-          ('conv6', 3, 512, 256, 1, True), ('conv7', 1, 256, 128, 1, True), ('prediction', 1, 128, 4, 1, False)]
+LAYERS = layers()                                 # (name, kernel, Cin, Cout, stride, relu), the architecture's own table
 SCOPE = 'ScoreNet'
 BETA1, BETA2, EPSILON = 0.9, 0.999, 1e-8          # tf.train.AdamOptimizer defaults (KFNet/train.py:313)
 WEIGHTS_NAME = 'kfnet_weights-%d.npz'             # tools.io.get_snapshot's kind: SCoordNet.eval --model_folder reads it
@@ -117,8 +114,7 @@ class SCoordNetTrainer(object):
         mapped by it, KFNet/train.py:279-280), None = identity.  loss_clip: None (no clip) or the reference's -2.0."""
         import torch
         H, Wd = image_size
-        if H % 8 or Wd % 8 or H <= 0 or Wd <= 0:
-            raise ValueError('training needs an image size whose height and width are multiples of 8, got %dx%d' % (H, Wd))
+        staging.check_size(H, Wd, 'the height and width of a training batch')
         if batch < 1:
             raise ValueError('batch must be >= 1')
         self.lib = _lib.load()
@@ -137,10 +133,10 @@ class SCoordNetTrainer(object):
         # flat parameter buffer: kernel then bias per layer, TF HWIO order (every offset a multiple of 4 floats)
         self.slots = {}
         off = 0
-        for name, k, ci, co, _, _ in LAYERS:
+        for li, (name, k, ci, co, _, _) in enumerate(LAYERS):
             for kind, shape in (('kernel', (k, k, ci, co)), ('bias', (co,))):
                 n = int(np.prod(shape))
-                self.slots['%s/%s/%s' % (SCOPE, name, kind)] = (off, n, shape)
+                self.slots[self.variable(li, kind)] = (off, n, shape)
                 off += -(-n // 4) * 4
         self.num_floats = off
         with torch.cuda.device(self.device):
@@ -199,23 +195,27 @@ class SCoordNetTrainer(object):
         return _lib.ConvDesc(N=self.batch, H=hin, W=win, Cin=ci, ldx=ci, Cout=co, cout_pad=-(-co // 32) * 32, ldy=co,
                              kh=k, kw=k, stride=s, transposed=0, relu=int(relu))
 
-    def _view(self, buf, name):
-        off, n, shape = self.slots[name]
-        return buf[off:off + n]
+    @staticmethod
+    def variable(li, kind):
+        """The TF name of layer li's 'kernel' or 'bias'."""
+        return '%s/%s/%s' % (SCOPE, LAYERS[li][0], kind)
 
-    def _ptr(self, buf, name):
-        return buf.data_ptr() + 4 * self.slots[name][0]
+    def _ptr(self, buf, li, kind):
+        return buf.data_ptr() + 4 * self.slots[self.variable(li, kind)][0]
 
     # ---- weights and optimiser state ---------------------------------------------------------------------------------
-    def set_weights(self, weights):
-        torch = self.torch
+    def _fill(self, buf, arrays, prefix=''):
+        """Every variable's slot of the flat buffer `buf` from arrays[prefix + its name]."""
         for name, (off, n, shape) in self.slots.items():
-            if name not in weights:
-                raise KeyError('weights lack %s' % name)
-            a = np.ascontiguousarray(np.asarray(weights[name], dtype=np.float32))
+            if prefix + name not in arrays:
+                raise KeyError('weights lack %s%s' % (prefix, name))
+            a = np.ascontiguousarray(np.asarray(arrays[prefix + name], dtype=np.float32))
             if a.shape != tuple(shape):
-                raise ValueError('%s has shape %s, expected %s' % (name, a.shape, tuple(shape)))
-            self.params[off:off + n].copy_(torch.from_numpy(a.reshape(-1)))
+                raise ValueError('%s%s has shape %s, expected %s' % (prefix, name, a.shape, tuple(shape)))
+            buf[off:off + n].copy_(self.torch.from_numpy(a.reshape(-1)))
+
+    def set_weights(self, weights):
+        self._fill(self.params, weights)
         self._packs_stale = True
 
     def _named(self, buf, prefix=''):
@@ -239,13 +239,8 @@ class SCoordNetTrainer(object):
         return st
 
     def load_state(self, st):
-        torch = self.torch
-        for buf, prefix in ((self.m, 'adam_m/'), (self.v, 'adam_v/')):
-            for name, (off, n, shape) in self.slots.items():
-                a = np.ascontiguousarray(np.asarray(st[prefix + name], dtype=np.float32))
-                if a.shape != tuple(shape):
-                    raise ValueError('%s%s has shape %s, expected %s' % (prefix, name, a.shape, tuple(shape)))
-                buf[off:off + n].copy_(torch.from_numpy(a.reshape(-1)))
+        self._fill(self.m, st, 'adam_m/')
+        self._fill(self.v, st, 'adam_v/')
         self.global_step = int(st['global_step'])
         self.adam_t = int(st['adam_t'])
 
@@ -260,63 +255,112 @@ class SCoordNetTrainer(object):
         return wp, sp
 
     # ---- one step ----------------------------------------------------------------------------------------------------
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
+    @staticmethod
+    def needs_full_resolution(augmented):
+        """The one statement of which labels a step needs: an augmented step (`augmented` true) the full-resolution ones,
+        because it interpolates between label pixels; any other step only the pixels (8r, 8c) that the loss reads."""
+        return bool(augmented)
+
+    def label_shape(self, augmented=False):
+        """The shape of the labels that a step expects, augmented (step(..., augment=params)) or not."""
+        (H, Wd), (h, w) = self.image_size, self.grid
+        return (self.batch, H, Wd, 4) if self.needs_full_resolution(augmented) else (self.batch, h, w, 4)
 
     def _repack(self, stream):
         for li, (name, k, ci, co, s, relu) in enumerate(LAYERS):
             if li == 0:
                 continue          # conv1a's forward matrix [27][C] is the master copy
             fwd, back, kind = self.packs[li]
-            w = self._ptr(self.params, '%s/%s/kernel' % (SCOPE, name))
+            w = self._ptr(self.params, li, 'kernel')
             _lib.check(self.lib.kfn_pack_conv_weights(w, k, k, ci, co, _lib.PACK_FORWARD, fwd.data_ptr(), stream),
                        'kfn_pack_conv_weights[%s]' % name)
             _lib.check(self.lib.kfn_pack_conv_weights(w, k, k, ci, co, kind, back.data_ptr(), stream),
                        'kfn_pack_conv_weights[%s, input gradient]' % name)
         self._packs_stale = False
 
-    def _upload(self, frames_u8, labels):
+    def stage(self, frames_u8, labels, augment=None, stream=None):
+        """Brings a batch to self.frames and self.labels and returns the stride at which the loss reads the labels.  Without
+        `augment` the labels may be grid-sized (stride 1) or full-resolution (stride 8).  With it the raw batch goes to the
+        augmenter's staging buffers and kfn_augment_batch writes self.frames and grid-sized labels (output pixels (8r, 8c))."""
         torch = self.torch
         B, (H, Wd), (h, w) = self.batch, self.image_size, self.grid
-        fr = frames_u8 if torch.is_tensor(frames_u8) else torch.from_numpy(np.ascontiguousarray(frames_u8))
-        if tuple(fr.shape) != (B, H, Wd, 3) or fr.dtype != torch.uint8:
-            raise ValueError('frames must be uint8 [%d,%d,%d,3], got %s %s' % (B, H, Wd, fr.dtype, tuple(fr.shape)))
-        self.frames.copy_(fr, non_blocking=True)
+        if augment is not None:
+            if self._augmenter is None:
+                from .augment import Augmenter
+                self._augmenter = Augmenter(B, H, Wd, label_stride=8, device=self.device)
+            aug = self._augmenter
+            if labels is None:
+                raise ValueError('training needs labels')
+            fin, lin = aug.stage(frames_u8, labels)          # ValueError on grid-sized labels
+            self.labels = aug.labels_out
+            stream = staging.current_stream(self.device) if stream is None else stream
+            aug.launch(augment, fin, lin, self.frames, self.labels, stream)
+            return 1
+        staging.stage(self.frames, frames_u8, torch.uint8, (B, H, Wd, 3), 'frames')
+        # the labels of either size, converted to float32: their shape picks the stride, so the copy is torch's own
         lb = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.float32))
-        if tuple(lb.shape) == (B, H, Wd, 4):
-            stride = 8
-        elif tuple(lb.shape) == (B, h, w, 4):
-            stride = 1
-        else:
+        if tuple(lb.shape) not in ((B, H, Wd, 4), (B, h, w, 4)):
             raise ValueError('labels must be float32 [%d,%d,%d,4] or grid-sized [%d,%d,%d,4], got %s'
                              % (B, H, Wd, B, h, w, tuple(lb.shape)))
         if self.labels is None or self.labels.shape != lb.shape:
             self.labels = torch.zeros(tuple(lb.shape), dtype=torch.float32, device=self.device)
         self.labels.copy_(lb.to(torch.float32), non_blocking=True)
-        return stride
+        return 8 if tuple(lb.shape) == (B, H, Wd, 4) else 1
+
+    def forward_layer(self, li, stream):
+        """Layer li's forward launch: self.act[li] from self.act[li - 1] (conv1a: from self.frames)."""
+        name, co = LAYERS[li][0], LAYERS[li][3]
+        bias = self._ptr(self.params, li, 'bias')
+        if li == 0:
+            H, Wd = self.image_size
+            _lib.check(self.lib.kfn_first_conv_u8(self.frames.data_ptr(), self.batch, H, Wd, self._ptr(self.params, 0, 'kernel'),
+                                                  bias, self.act[0].data_ptr(), co, None, None, None, 0, stream),
+                       'kfn_first_conv_u8')
+            return
+        d = self._fwd_desc(li)
+        _lib.check(self.lib.kfn_conv2d_nhwc(C.byref(d), self.act[li - 1].data_ptr(), self.packs[li][0].data_ptr(), bias,
+                                            self.act[li].data_ptr(), stream), 'kfn_conv2d_nhwc[%s]' % name)
+
+    def weight_gradient(self, li, stream):
+        """Layer li's kernel and bias gradients into self.grads, from its input and self.dact[li]."""
+        name, co = LAYERS[li][0], LAYERS[li][3]
+        dw, db = self._ptr(self.grads, li, 'kernel'), self._ptr(self.grads, li, 'bias')
+        if li == 0:
+            H, Wd = self.image_size
+            _lib.check(self.lib.kfn_first_conv_u8_grad_weights(self.frames.data_ptr(), self.batch, H, Wd,
+                                                               self.dact[0].data_ptr(), co, dw, db,
+                                                               self.workspace.data_ptr(), stream),
+                       'kfn_first_conv_u8_grad_weights')
+            return
+        gd = self._fwd_desc(li)
+        gd.ldy = self.dact[li].shape[3]
+        _lib.check(self.lib.kfn_conv2d_grad_weights(C.byref(gd), self.act[li - 1].data_ptr(), self.dact[li].data_ptr(), dw, db,
+                                                    self.workspace.data_ptr(), stream), 'kfn_conv2d_grad_weights[%s]' % name)
+
+    def input_gradient(self, li, stream):
+        """self.dact[li - 1] from self.dact[li] (li >= 1): the forward kernel on dZ with the pack kfn_pack_conv_weights made
+        for it, then the ReLU of layer li - 1."""
+        name, k, ci, co, s, relu = LAYERS[li]
+        hin, win, ho, wo = self.shapes[li]
+        dz, ldz = self.dact[li], self.dact[li].shape[3]
+        bd = _lib.ConvDesc(N=self.batch, H=ho, W=wo, Cin=ldz, ldx=ldz, Cout=ci, cout_pad=-(-ci // 32) * 32, ldy=ci, kh=k,
+                           kw=k, stride=s, transposed=int(s == 2), relu=0)
+        _lib.check(self.lib.kfn_conv2d_nhwc(C.byref(bd), dz.data_ptr(), self.packs[li][1].data_ptr(), None,
+                                            self.dact[li - 1].data_ptr(), stream), 'kfn_conv2d_nhwc[%s, input gradient]' % name)
+        _lib.check(self.lib.kfn_relu_grad(self.act[li - 1].data_ptr(), ci, self.dact[li - 1].data_ptr(), ci,
+                                          self.batch * hin * win, ci, stream), 'kfn_relu_grad[%s]' % LAYERS[li - 1][0])
 
     def forward(self, stream=None):
         """The forward pass on the uploaded frames; every layer's output stays in self.act."""
-        lib = self.lib
-        stream = self._stream() if stream is None else stream
+        stream = staging.current_stream(self.device) if stream is None else stream
         if self._packs_stale:
             self._repack(stream)
-        H, Wd = self.image_size
-        n0 = LAYERS[0][0]
-        _lib.check(lib.kfn_first_conv_u8(self.frames.data_ptr(), self.batch, H, Wd,
-                                         self._ptr(self.params, '%s/%s/kernel' % (SCOPE, n0)),
-                                         self._ptr(self.params, '%s/%s/bias' % (SCOPE, n0)), self.act[0].data_ptr(),
-                                         LAYERS[0][3], None, None, None, 0, stream), 'kfn_first_conv_u8')
-        for li in range(1, len(LAYERS)):
-            d = self._fwd_desc(li)
-            _lib.check(lib.kfn_conv2d_nhwc(C.byref(d), self.act[li - 1].data_ptr(), self.packs[li][0].data_ptr(),
-                                           self._ptr(self.params, '%s/%s/bias' % (SCOPE, LAYERS[li][0])),
-                                           self.act[li].data_ptr(), stream), 'kfn_conv2d_nhwc[%s]' % LAYERS[li][0])
+        for li in range(len(LAYERS)):
+            self.forward_layer(li, stream)
 
     def loss_and_gradients(self, label_stride, stream=None):
         """Loss on self.act[-1], then the backward pass into self.grads."""
-        lib = self.lib
-        stream = self._stream() if stream is None else stream
+        stream = staging.current_stream(self.device) if stream is None else stream
         B, (h, w) = self.batch, self.grid
         last = len(LAYERS) - 1
         d = _lib.CoordLossDesc(B=B, h=h, w=w, ld_pred=LAYERS[last][3], ld_dpred=self.dact[last].shape[3],
@@ -325,36 +369,17 @@ class SCoordNetTrainer(object):
                                smooth_weight=self.smooth_weight, dist_threshold=0.05, min_uncertainty=1e-5)
         if self.transform is not None:
             d.transform = (C.c_float * 12)(*[float(x) for x in self.transform[:3].reshape(-1)])
-        _lib.check(lib.kfn_coord_loss_grad(C.byref(d), self.act[last].data_ptr(), self.labels.data_ptr(),
-                                           self.frames.data_ptr(), self.dact[last].data_ptr(), self.stats.data_ptr(), stream),
-                   'kfn_coord_loss_grad')
+        _lib.check(self.lib.kfn_coord_loss_grad(C.byref(d), self.act[last].data_ptr(), self.labels.data_ptr(),
+                                                self.frames.data_ptr(), self.dact[last].data_ptr(), self.stats.data_ptr(),
+                                                stream), 'kfn_coord_loss_grad')
         for li in range(last, 0, -1):
-            name, k, ci, co, s, relu = LAYERS[li]
-            hin, win, ho, wo = self.shapes[li]
-            dz, ldz = self.dact[li], self.dact[li].shape[3]
-            gd = self._fwd_desc(li)
-            gd.ldy = ldz
-            _lib.check(lib.kfn_conv2d_grad_weights(C.byref(gd), self.act[li - 1].data_ptr(), dz.data_ptr(),
-                                                   self._ptr(self.grads, '%s/%s/kernel' % (SCOPE, name)),
-                                                   self._ptr(self.grads, '%s/%s/bias' % (SCOPE, name)),
-                                                   self.workspace.data_ptr(), stream), 'kfn_conv2d_grad_weights[%s]' % name)
-            # d/d(input): the forward kernel on dZ with the pack kfn_pack_conv_weights made for it
-            bd = _lib.ConvDesc(N=B, H=ho, W=wo, Cin=ldz, ldx=ldz, Cout=ci, cout_pad=-(-ci // 32) * 32, ldy=ci, kh=k, kw=k,
-                               stride=s, transposed=int(s == 2), relu=0)
-            _lib.check(lib.kfn_conv2d_nhwc(C.byref(bd), dz.data_ptr(), self.packs[li][1].data_ptr(), None,
-                                           self.dact[li - 1].data_ptr(), stream), 'kfn_conv2d_nhwc[%s, input gradient]' % name)
-            _lib.check(lib.kfn_relu_grad(self.act[li - 1].data_ptr(), ci, self.dact[li - 1].data_ptr(), ci,
-                                         B * hin * win, ci, stream), 'kfn_relu_grad[%s]' % LAYERS[li - 1][0])
-        n0, c1 = LAYERS[0][0], LAYERS[0][3]
-        H, Wd = self.image_size
-        _lib.check(lib.kfn_first_conv_u8_grad_weights(self.frames.data_ptr(), B, H, Wd, self.dact[0].data_ptr(), c1,
-                                                      self._ptr(self.grads, '%s/%s/kernel' % (SCOPE, n0)),
-                                                      self._ptr(self.grads, '%s/%s/bias' % (SCOPE, n0)),
-                                                      self.workspace.data_ptr(), stream), 'kfn_first_conv_u8_grad_weights')
+            self.weight_gradient(li, stream)
+            self.input_gradient(li, stream)
+        self.weight_gradient(0, stream)
 
     def apply_gradients(self, stream=None):
         """TensorFlow's Adam on the flat buffer, with the regulariser's weight_decay * w folded into the gradient."""
-        stream = self._stream() if stream is None else stream
+        stream = staging.current_stream(self.device) if stream is None else stream
         lr = learning_rate(self.base_lr, self.gamma, self.stepvalue, self.global_step)
         t = self.adam_t + 1
         _lib.check(self.lib.kfn_adam_step(self.params.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.grads.data_ptr(),
@@ -365,21 +390,6 @@ class SCoordNetTrainer(object):
         self._packs_stale = True
         return lr
 
-    def _upload_augmented(self, frames_u8, labels, params, stream):
-        """The raw batch goes to the augmenter's staging buffers; kfn_augment_batch writes self.frames and grid-sized labels
-        (output pixels (8r, 8c)), which the loss then reads at label stride 1."""
-        if self._augmenter is None:
-            from .augment import Augmenter
-            H, Wd = self.image_size
-            self._augmenter = Augmenter(self.batch, H, Wd, label_stride=8, device=self.device)
-        aug = self._augmenter
-        if labels is None:
-            raise ValueError('training needs labels')
-        fin, lin = aug.stage(frames_u8, labels)          # ValueError on grid-sized labels
-        self.labels = aug.labels_out
-        aug.launch(params, fin, lin, self.frames, self.labels, stream)
-        return 1
-
     def step(self, frames_u8, labels, augment=None):
         """One update on a batch: frames uint8 [B,H,W,3], labels float32 [B,H,W,4] or grid-sized [B,H/8,W/8,4] =
         (gt xyz, mask).  augment: None, or the kfnet_amd.augment.AugmentParams of this batch -- the labels must then be the
@@ -387,11 +397,8 @@ class SCoordNetTrainer(object):
         StepStats (loss, l_measure, l_smooth, a_measure, pixels, lr of THIS step's loss, before the update), read back only
         when accessed."""
         with self.torch.cuda.device(self.device):
-            stream = self._stream()
-            if augment is None:
-                stride = self._upload(frames_u8, labels)
-            else:
-                stride = self._upload_augmented(frames_u8, labels, augment, stream)
+            stream = staging.current_stream(self.device)
+            stride = self.stage(frames_u8, labels, augment, stream)
             self.forward(stream)
             self.loss_and_gradients(stride, stream)
             stats = self.stats.clone()

@@ -22,14 +22,13 @@ benchmarks and parity tests (no trained weights are reachable from this environm
 """
 import numpy as np
 
+from .cnn_wrapper.SCoordNet import layers as scoordnet_layers
+
+
 # (name, kind, shape)  -- generation order == SURVEY.md App. B order
 def variable_specs():
     specs = []
-    sc = [('conv1a', 3, 3, 64), ('conv1b', 3, 64, 64), ('conv2a', 3, 64, 256),
-          ('conv2b', 3, 256, 256), ('conv3a', 3, 256, 512), ('conv3b', 3, 512, 512),
-          ('conv4a', 3, 512, 1024), ('conv4b', 3, 1024, 1024), ('conv5', 3, 1024, 512),
-          ('conv6', 3, 512, 256), ('conv7', 1, 256, 128), ('prediction', 1, 128, 4)]
-    for n, k, ci, co in sc:  # cnn_wrapper/SCoordNet.py:21-32
+    for n, k, ci, co, _, _ in scoordnet_layers():  # the reference's cnn_wrapper/SCoordNet.py:21-32
         specs.append(('ScoreNet/' + n, 'conv', (k, k, ci, co)))
     ft = [('feat1', 3, 16), ('feat2', 16, 32), ('feat3', 32, 32), ('feat4', 32, 64),
           ('feat5', 64, 64), ('feat6', 64, 128), ('feat7', 128, 32)]

@@ -1,6 +1,6 @@
-"""CPU tests of the training path (kfnet_amd/train.py, kfnet_amd/SCoordNet/train.py; DESIGN.md "Training"): schedules,
-label preparation, snapshot naming, initial weights, the new exports' argument checks, the command line's refusals, and
-the reference loss of tests/train_ref.py against finite differences."""
+"""CPU tests of the training path (kfnet_amd/train.py, kfnet_amd/batches.py, kfnet_amd/SCoordNet/train.py; DESIGN.md
+"Training"): schedules, label preparation, snapshot naming, initial weights, the new exports' argument checks, the command
+line's refusals, the batch sources, and the reference loss of tests/train_ref.py against finite differences."""
 import ctypes as C
 import os
 import subprocess
@@ -256,3 +256,64 @@ def test_inputs_of_the_gpu_loss_tests_keep_clear_of_the_squared_threshold():
     assert G._seam_inputs()[4] > 0
     G._clip_inputs(3)
     G._clip_inputs(7, flat=True, B=4, h=60, w=80)
+
+
+def test_batch_sources_return_the_frames_and_labels_of_the_indices(tmp_path):
+    """The three sources of kfnet_amd.batches have one shape; the synthetic one and the one over label files run without a
+    device.  Indices of steps 0-2 at batch 2 of 5 frames: the third batch wraps."""
+    from types import SimpleNamespace
+    from PIL import Image
+    from kfnet_amd.batches import LabelFileSource, SyntheticSource, open_source
+    from kfnet_amd.KFNet.metrics import read_label_grid
+    from kfnet_amd.synth import synthetic_sequence, synthetic_transform
+    from kfnet_amd.train import batch_indices, synthetic_labels
+    H, W, count = 64, 96, 5
+    batches = [batch_indices(s, 2, count) for s in range(3)]
+    assert batches[2] == [4, 0]
+    frames = synthetic_sequence(count, H, W)
+    args = SimpleNamespace(height=H, width=W, synthetic=count, depth=False, input_folder=str(tmp_path), batch=2, gpu=0)
+    src = open_source(args, False)
+    assert isinstance(src, SyntheticSource) and src.count == count
+    np.testing.assert_array_equal(src.transform, synthetic_transform())
+    for full, hw in ((False, (8, 12)), (True, (H, W))):
+        for idx in batches:
+            f, l = src.batch(idx, full)
+            assert f.dtype == np.uint8 and l.dtype == np.float32
+            np.testing.assert_array_equal(f, frames[idx])
+            np.testing.assert_array_equal(l, synthetic_labels(count, hw)[idx])
+
+    rng = np.random.default_rng(4)
+    labels = rng.normal(size=(count, H, W, 4)).astype(np.float32)
+    M = rng.normal(size=(4, 4)).astype(np.float32)
+    images, label_files = [], []
+    for i in range(count):
+        images.append(str(tmp_path / ('image_%d.png' % i)))
+        label_files.append(str(tmp_path / ('label_%d.bin' % i)))
+        Image.fromarray(frames[i]).save(images[i])
+        labels[i].tofile(label_files[i])
+    (tmp_path / 'image_list.txt').write_text(''.join(p + '\n' for p in images))
+    (tmp_path / 'label_list.txt').write_text(''.join(p + '\n' for p in label_files))
+    np.savetxt(str(tmp_path / 'transform.txt'), M)
+    args.synthetic = 0
+    for full in (False, True):
+        src = open_source(args, full)
+        assert isinstance(src, LabelFileSource) and src.count == count
+        np.testing.assert_array_equal(src.transform, np.loadtxt(str(tmp_path / 'transform.txt'), dtype=np.float32))
+        for idx in batches:
+            f, l = src.batch(idx, full)
+            assert f.dtype == np.uint8 and l.dtype == np.float32
+            np.testing.assert_array_equal(f, frames[idx])
+            want = np.stack([labels[i] if full else read_label_grid(label_files[i], (H, W), (8, 12)) for i in idx])
+            assert l.shape == want.shape and l.tobytes() == want.tobytes()
+
+    labels[0, :8].tofile(label_files[0])                     # a label file of the wrong size, first in the list
+    with pytest.raises(ValueError, match='label_0.bin'):
+        open_source(args, True)
+    src = open_source(args, False)                           # grid-sized reads open only the files of a batch
+    for full in (False, True):
+        with pytest.raises(ValueError, match='label_0.bin'):
+            src.batch(batches[2], full)
+        assert src.batch(batches[1], full)[1].shape[0] == 2
+    args.depth, args.synthetic = True, count
+    with pytest.raises(ValueError, match='--synthetic'):
+        open_source(args, False)

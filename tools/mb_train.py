@@ -12,7 +12,6 @@ or stride 1 with --augment; depth_labels_grid_kernel / depth_labels_full_kernel 
 Under `rocprofv3 --kernel-trace --stats -- python tools/mb_train.py --steps 5` the kernel table gives the same split per
 kernel name (wgrad_mfma_kernel, conv_mfma_kernel, ...)."""
 import argparse
-import ctypes as C
 import os
 import sys
 
@@ -49,45 +48,41 @@ def main(argv=None):
     import torch
     from kfnet_amd import _lib
     from kfnet_amd.synth import synthetic_sequence, synthetic_transform
-    from kfnet_amd.train import LAYERS, SCOPE, SCoordNetTrainer, synthetic_labels
+    from kfnet_amd.train import LAYERS, SCoordNetTrainer, synthetic_labels
     from kfnet_amd.weights import initial_weights
     size = (a.height, a.width)
     tr = SCoordNetTrainer(initial_weights(0), image_size=size, batch=a.batch, transform=synthetic_transform())
     frames = torch.from_numpy(synthetic_sequence(a.batch, a.height, a.width)).cuda()
-    labels = torch.from_numpy(synthetic_labels(a.batch, size if a.augment else tr.grid)).cuda()
+    labels = torch.from_numpy(synthetic_labels(a.batch, tr.label_shape(a.augment)[1:3])).cuda()
     if a.depth:
         from kfnet_amd.labels import DepthLabeler, pose_rows
         rng = np.random.default_rng(0)
         depth = torch.from_numpy(rng.integers(500, 4000, size=(a.batch,) + size).astype(np.uint16).view(np.int16)).cuda()
         poses = torch.from_numpy(pose_rows(np.tile(np.eye(4), (a.batch, 1, 1)))).cuda()
-        labeler = DepthLabeler(a.batch, a.height, a.width, 1 if a.augment else 8)
+        labeler = DepthLabeler(a.batch, a.height, a.width, 1 if tr.needs_full_resolution(a.augment) else 8)
 
         def labels_of_step():
             return labeler.labels(depth, poses)
     else:
         def labels_of_step():
             return labels
-    if a.augment:
-        from kfnet_amd.augment import draw
-        count = [0]
+    from kfnet_amd.augment import draw
+    count = [0]
 
-        def step():
-            count[0] += 1
-            tr.step(frames, labels_of_step(), augment=draw(0, count[0]))
-    else:
-        def step():
-            tr.step(frames, labels_of_step())
+    def step():
+        count[0] += 1
+        tr.step(frames, labels_of_step(), augment=draw(0, count[0]) if a.augment else None)
     for _ in range(a.warmup):
         step()
     ms = timed(torch, step, a.steps)
     print('%dx%d batch %d%s: %.2f ms per step (%.1f frames/s), %.1f M parameters' %
           (a.height, a.width, a.batch, (', augmented' if a.augment else '') + (', labels from depth' if a.depth else ''), ms,
            1e3 * a.batch / ms, tr.num_floats / 1e6))
-    stride = tr._upload(frames, labels)
+    stride = tr.stage(frames, labels)
     fwd = timed(torch, tr.forward, a.steps)
     bwd = timed(torch, lambda: tr.loss_and_gradients(stride), a.steps)
     lib = tr.lib
-    stream = tr._stream()
+    stream = torch.cuda.current_stream().cuda_stream
     adam = timed(torch, lambda: _lib.check(lib.kfn_adam_step(tr.params.data_ptr(), tr.m.data_ptr(), tr.v.data_ptr(),
                                                              tr.grads.data_ptr(), tr.num_floats, 0.0, 0.9, 0.999, 1e-8, 0.0,
                                                              stream), 'adam'), a.steps)
@@ -100,20 +95,13 @@ def main(argv=None):
     for li in range(1, len(LAYERS)):
         name, k, ci, co, s, relu = LAYERS[li]
         hin, win, ho, wo = tr.shapes[li]
-        d = tr._fwd_desc(li)
-        gd = tr._fwd_desc(li)
-        gd.ldy = tr.dact[li].shape[3]
         P = a.batch * ho * wo
         # FLOPs the weight-gradient MFMAs execute: whole 128 x (64 | 128) tiles, the bias row included
         bn = 64 if co <= 64 else 128
         executed = 2.0 * P * (-(-(k * k * ci + 1) // 128) * 128) * (-(-co // bn) * bn)
         nominal = 2.0 * P * k * k * ci * co
-        tw = timed(torch, lambda: _lib.check(lib.kfn_conv2d_grad_weights(
-            C.byref(gd), tr.act[li - 1].data_ptr(), tr.dact[li].data_ptr(), tr._ptr(tr.grads, '%s/%s/kernel' % (SCOPE, name)),
-            tr._ptr(tr.grads, '%s/%s/bias' % (SCOPE, name)), tr.workspace.data_ptr(), stream), 'wgrad'), a.steps)
-        tf = timed(torch, lambda: _lib.check(lib.kfn_conv2d_nhwc(
-            C.byref(d), tr.act[li - 1].data_ptr(), tr.packs[li][0].data_ptr(), tr._ptr(tr.params, '%s/%s/bias' % (SCOPE, name)),
-            tr.act[li].data_ptr(), stream), 'forward'), a.steps)
+        tw = timed(torch, lambda: tr.weight_gradient(li, stream), a.steps)
+        tf = timed(torch, lambda: tr.forward_layer(li, stream), a.steps)
         tot_w += tw
         tot_f += tf
         print('%-11s %10.3f %9.1f %6.1f%% | %10.3f %9.1f %6.1f%%' %
