@@ -395,12 +395,10 @@ class KFNet():
         # the loader-generated volume feeds the DIRECT kernel: conv0 may have been built as a Winograd layer (3x3
         # stride 1, 32 channels, 8x8 grid), whose kernel variable is packed [Cin/8][16][Cout][8] -- reset the packers
         # to the [cout_pad][9 Cin] layout kfn_cost_volume_conv reads (silently wrong flow otherwise)
-        from ..graph import pack_bias, pack_conv_kernel
+        from ..routing import direct
         if conv0.kernel.storage is not None:
             return   # already uploaded in another layout: keep the unfused pair of launches
-        conv0.kernel.pack = pack_conv_kernel
-        if conv0.bias is not None:
-            conv0.bias.pack = pack_bias
+        conv0.reroute(direct(conv0))     # (also hands back a workspace the Winograd route held)
         fused = CostVolumeConvOp(feat_map1, feat_map2, conv0.y, conv0.kernel, conv0.bias, conv0.relu, window_size)
         g.ops[g.ops.index(conv0)] = fused
         g.ops.remove(cv[0])

@@ -12,11 +12,8 @@ NotImplementedError (there is deliberately no CPU/eager fallback in the product 
 import numpy as np
 
 from .. import _lib
-from ..graph import (Conv64RowsF16Op, ConvOp, CopyChannelsOp, FirstConvOp, pack_conv64_rows_kernel, Storage, Tensor, WinogradConvOp, WinogradFusedConvOp,
-                     WinogradS2ConvOp, WinogradF43ConvOp, WindowFcConvOp, as_f16, pack_winograd_f43_kernel, pack_winograd_f43_kernel_b, pack_winograd_s2_kernel_b, pack_winograd_s2_kernel_c,
-                     as_f16x3, pack_bias, pack_conv_kernel, pack_deconv_kernel, pack_first_kernel,
-                     pack_bias_x4, pack_window_fc_kernel, pack_winograd_fused_kernel, pack_winograd_kernel,
-                     pack_winograd_s2_kernel, current_scope, pack_conv_kernel_chunked)
+from .. import routing
+from ..graph import ConvOp, CopyChannelsOp, FirstConvOp, Tensor, as_f16, current_scope, pack_bias, pack_deconv_kernel, pack_first_kernel
 
 # Zero padding in default. 'VALID' gives no padding.
 DEFAULT_PADDING = 'SAME'
@@ -108,7 +105,6 @@ class Network(object):
         of the file is assigned to the variable <scope>/<op_name>/<param_name>; an entry WITHOUT such a variable raises
         unless `ignore_missing` -- variables the file does not mention keep what they hold (a per-scope file therefore
         loads into a graph that also holds the other scope's networks, KFNet/eval.py:66-68)."""
-        from ..graph import current_scope
         from ..weights import from_network_load_dict
         table = np.load(data_path, allow_pickle=True).item()
         flat = from_network_load_dict(table, current_scope())
@@ -158,34 +154,17 @@ class Network(object):
     def set_epilogue(self, layer_name, epilogue):
         """Fuse a head operation (KFN_EPI_*: l2_normalize, exp on channel 3, exp * 1e-2) into the
         launch that produces `layer_name`.  Only the direct MFMA convolution carries these
-        epilogues; a layer that was routed to the Winograd path is re-routed to the direct
+        epilogues; a layer that was routed to another kernel is re-routed to the direct
         kernel here (its weights are then packed for that kernel), so that a routing heuristic
         can never silently drop e.g. tf.nn.l2_normalize (KFNet/KFNet.py:340)."""
-        from ..graph import pack_conv_kernel as _direct_pack
         hits = [op for op in self.ops if op.name == layer_name and isinstance(op, ConvOp)]
         if len(hits) != 1:
             raise KeyError('set_epilogue: %d convolution launches are named %r' % (len(hits), layer_name))
         op = hits[0]
-        if isinstance(op, (WinogradConvOp, WinogradFusedConvOp, WinogradS2ConvOp, WinogradF43ConvOp, Conv64RowsF16Op)):
-            if op.kernel.storage is not None:
-                raise RuntimeError('set_epilogue(%r): weights are already packed for the %s kernel'
-                                   % (layer_name, type(op).__name__))
-            # in place (the op object may already sit in other launch lists): same tensors and
-            # variables, direct-kernel weight layout.  The fp16-operand forms keep their operand type: the direct
-            # kernel reads fp16 activations with chunk-major weights (Network.conv's own rule for that case).
-            if op.operand_dtype == _lib.OPERAND_F16:
-                chunked = op.x.dtype == 'f16' or op.y.dtype == 'f16'
-                op.kernel.pack = as_f16(pack_conv_kernel_chunked if chunked else _direct_pack)
-            else:
-                op.kernel.pack = _direct_pack
-            op.__class__ = ConvOp
-            op.workspace = None
-            for attr in ('eight_wave',):        # routing state of the class the op just left (desc() no longer reads it)
-                op.__dict__.pop(attr, None)
-            op.epilogue = epilogue
-            return op
         if op.operand_dtype == _lib.OPERAND_F32 and op.y.shape[3] > 32 and epilogue == _lib.EPI_L2NORM:
             raise ValueError('the l2_normalize epilogue needs <= 32 output channels (one MFMA column block)')
+        if type(op).launch is not ConvOp.launch:       # (the window matrix is the direct kernel's 1x1 path: it stays)
+            op.reroute(routing.direct(op))
         op.epilogue = epilogue
         return op
 
@@ -232,124 +211,10 @@ class Network(object):
             raise NotImplementedError('%s: an fp16 activation can only feed an fp16-operand convolution' % name)
         y = g.tensor((n, _same_out(h, strides), _same_out(w, strides), filters),
                      dtype=self._act_dtype(filters) if f16 else 'f32', name=name)
-        bias = g.variable(name + '/bias', (filters,), pack_bias) if biased else None
-        wmin = g.winograd_min_channels
-        # (measured, 16 frames: conv3b 2.07 vs 2.31 ms direct fp16, conv4b 1.81 vs 2.59, conv5 1.00 vs 1.25; at
-        #  Cin = 256 the direct kernel is as fast -- conv2b 2.56 vs 2.48 -- and stays)
-        if (f16 and input.dtype == 'f32' and y.dtype == 'f32' and k == 3 and strides == 1 and g.winograd_fused and cin >= 512
-                and WinogradFusedConvOp.supported(input.shape, cin, filters, _lib.OPERAND_F16)):
-            # BASELINE config 5: the four-wave Winograd kernel on fp16 MFMAs (transform in fp32, V and U rounded to fp16)
-            kern = g.variable(name + '/kernel', (k, k, cin, filters), as_f16(pack_winograd_fused_kernel))
-            self._emit(WinogradFusedConvOp(name, input, y, kern, bias, relu, operand_dtype=_lib.OPERAND_F16))
-            return y
-        # (the fp16 instantiation of the polyphase stride-2 kernel exists and is tested, but at fp16 MFMA rates it is
-        #  latency-bound and the direct fp16 kernel is faster: conv3a 1.20 vs 1.68 ms -- Graph.winograd_s2_f16 = False)
-        if (f16 and input.dtype == 'f32' and y.dtype == 'f32' and k == 3 and strides == 2 and g.winograd_s2_f16 and cin >= 64
-                and filters >= 128 and WinogradS2ConvOp.supported(input.shape, cin, filters)):
-            kern = g.variable(name + '/kernel', (k, k, cin, filters), as_f16(pack_winograd_s2_kernel))
-            self._emit(WinogradS2ConvOp(name, input, y, kern, bias, relu, operand_dtype=_lib.OPERAND_F16))
-            return y
-        if (f16 and k == 3 and strides == 1 and h == 2 and w == 2 and g.window_fc and biased and (4 * cin) % 32 == 0
-                and filters % 8 == 0 and input.dtype == 'f32' and y.dtype == 'f32'):
-            # OFlowNet's 2x2 level in the fp16-operand mode: the same dense window matrix, operands rounded to fp16
-            kern = g.variable(name + '/kernel', (k, k, cin, filters), as_f16(pack_window_fc_kernel))
-            bias.pack = pack_bias_x4
-            op = WindowFcConvOp(name, input, y, kern, bias, relu)
-            op.operand_dtype = _lib.OPERAND_F16
-            self._emit(op)
-            return y
-        if (f16 and g.conv64_rows_f16 and k == 3 and strides == 1 and biased
-                and Conv64RowsF16Op.supported(input, y, cin, filters)):
-            # (measured, 16 frames of 540x960: 1.05 ms on the 256x64 implicit-GEMM tile, LDS-bound at 0.23 of the fp16 peak)
-            kern = g.variable(name + '/kernel', (k, k, cin, filters), pack_conv64_rows_kernel)
-            self._emit(Conv64RowsF16Op(name, input, y, kern, bias, relu))
-            return y
-        if f16:
-            # fp16 activations on either side: the tap-innermost kernels with chunk-major weights
-            pk = pack_conv_kernel_chunked if (input.dtype == 'f16' or y.dtype == 'f16') else pack_conv_kernel
-            kern = g.variable(name + '/kernel', (k, k, cin, filters), as_f16(pk))
-            self._emit(ConvOp(name, input, y, kern, bias, k, k, strides, relu, operand_dtype=_lib.OPERAND_F16))
-            return y
-        if g.conv_operands == 'f16x3' and cin % 32 == 0 and cin >= g.f16x3_min_channels:
-            kern = g.variable(name + '/kernel', (k, k, cin, filters), as_f16x3(pack_conv_kernel))
-            self._emit(ConvOp(name, input, y, kern, bias, k, k, strides, relu, operand_dtype=_lib.OPERAND_F16X3))
-            return y
-        if (k == 3 and strides == 1 and h == 2 and w == 2 and g.window_fc and biased and cin % 8 == 0 and filters % 8 == 0
-                and g.conv_operands == 'f32'):
-            # OFlowNet's 2x2 level: dense window matrix (16 Cin Cout products per window instead of 36)
-            kern = g.variable(name + '/kernel', (k, k, cin, filters), pack_window_fc_kernel)
-            bias.pack = pack_bias_x4
-            self._emit(WindowFcConvOp(name, input, y, kern, bias, relu))
-            return y
-        f43 = g.winograd_f43_min_channels
-        # (measured at batch 32, F(2x2,3x3) -> F(4x4,3x3), profiles/r04_wino4_microbench.log: conv2b 10.02 -> 6.99 ms,
-        #  conv3b 9.30 -> 6.41, conv4b 9.18 -> 6.26, conv5 4.61 -> 3.28, conv6 1.24 -> 0.85, conv1b 3.66 -> 2.77, feat5 0.23 -> 0.18;
-        #  with 32 output channels -- feat3 -- half of the workgroup idles: 0.31 -> 0.47, stays on wino2_kernel)
-        fmin = g.winograd_fused_min_channels
-        fused_ok = (k == 3 and strides == 1 and g.winograd_fused and fmin and cin >= fmin and filters >= fmin
-                    and cin <= g.winograd_fused_max_channels
-                    and min(h, w) >= 8 and WinogradFusedConvOp.supported(input.shape, cin, filters)
-                    and g.winograd_lds_fits(1, cin, filters))
-        # A launch of fewer than winograd_f43_min_workgroups workgroups (of 32 tiles x 64 channels, one per CU) leaves
-        # most of the 256 CUs idle and the smaller F(2x2,3x3) workgroups win -- single frames only (batch 1, F(4x4) ->
-        # F(2x2): conv5 80 workgroups 0.287 -> 0.238 ms, conv6 40: 0.151 -> 0.123, feat5 40: 0.031 -> 0.022; from 160
-        # workgroups up F(4x4) is ahead: conv4b at batch 1 0.288 against 0.479; profiles/r04_wino4_microbench.log, r4z)
-        e8 = bool(g.winograd_f43_eight_wave)
-        wgs = WinogradF43ConvOp.workgroups((n, h, w, cin), filters)
-        ksplit = 1
-        if e8 and g.winograd_f43_max_k_split > 1:
-            ksplit = WinogradF43ConvOp.best_k_split(wgs, cin, n * h * w * filters * 4, g.winograd_f43_max_k_split)
-        f43_fills = (not fused_ok or wgs * ksplit >= g.winograd_f43_min_workgroups)
-        if (k == 3 and strides == 1 and g.winograd_fused and f43 and cin >= f43 and filters >= f43 and f43_fills
-                and WinogradF43ConvOp.supported(input.shape, cin, filters, input.ld, y.ld, y.ch_off)
-                and g.winograd_lds_fits(1, cin, filters, _lib.WINO_FORM_F43_EIGHT_WAVE if e8 else _lib.WINO_FORM_F43_FOUR_WAVE)):
-            kern = g.variable(name + '/kernel', (k, k, cin, filters), pack_winograd_f43_kernel_b if e8 else pack_winograd_f43_kernel)
-            op = WinogradF43ConvOp(name, input, y, kern, bias, relu, eight_wave=e8, k_split=ksplit)
-            if ksplit > 1:
-                # a PRIVATE workspace: the two towers run on two streams, a shared one would race (single frames only:
-                # 29-59 MB per split layer at batch 1)
-                op.workspace = Storage((op.workspace_bytes() + 3) // 4, 'f32')
-                g.storages.append(op.workspace)
-            self._emit(op)
-            return y
-        # (measured, 16-frame batch, single-kernel vs two-kernel form: conv1b 2.3 ms vs 3.3 direct, conv2b 5.60 vs
-        #  7.10, conv3b 5.05 vs 5.99, conv4b 4.93 vs 5.42, conv5 2.49 vs 2.73, conv6 0.63 vs 0.77)
-        if fused_ok:
-            kern = g.variable(name + '/kernel', (k, k, cin, filters), pack_winograd_fused_kernel)
-            self._emit(WinogradFusedConvOp(name, input, y, kern, bias, relu))
-            return y
-        smin = g.winograd_s2_min_channels
-        # 3x3 stride-2 layers (SCoordNet conv2a / conv3a / conv4a): polyphase + F(2,2), 25/36 of the direct MFMAs
-        e8 = bool(g.winograd_s2_eight_wave)
-        if (k == 3 and strides == 2 and smin and cin >= smin and filters >= 128
-                and WinogradS2ConvOp.supported(input.shape, cin, filters)
-                and g.winograd_lds_fits(2, cin, filters, _lib.WINO_FORM_S2_EIGHT_WAVE if e8 else 0)):
-            if (g.winograd_s2_f42 and WinogradS2ConvOp.f42_supported(input.shape, cin, filters)
-                    and WinogradS2ConvOp.f42_workgroups(y.shape) >= g.winograd_s2_f42_min_workgroups
-                    and g.winograd_lds_fits(2, cin, filters, _lib.WINO_FORM_S2_F42)):
-                kern = g.variable(name + '/kernel', (k, k, cin, filters), pack_winograd_s2_kernel_c)
-                self._emit(WinogradS2ConvOp(name, input, y, kern, bias, relu, f42=True))
-                return y
-            kern = g.variable(name + '/kernel', (k, k, cin, filters), pack_winograd_s2_kernel_b if e8 else pack_winograd_s2_kernel)
-            ksplit = 1
-            if e8 and g.winograd_s2_max_k_split > 1 and filters % 4 == 0:
-                ksplit = WinogradS2ConvOp.best_k_split(WinogradS2ConvOp.base_workgroups(y.shape), cin,
-                                                       y.shape[0] * y.shape[1] * y.shape[2] * filters * 4, g.winograd_s2_max_k_split)
-            op = WinogradS2ConvOp(name, input, y, kern, bias, relu, eight_wave=e8, k_split=ksplit)
-            if ksplit > 1:
-                op.workspace = Storage((op.workspace_bytes() + 3) // 4, 'f32')     # private: see the F(4x4) split above
-                g.storages.append(op.workspace)
-            self._emit(op)
-            return y
-        if (k == 3 and strides == 1 and wmin and cin >= wmin and filters >= wmin and filters % 4 == 0
-                and min(h, w) >= 8):
-            kern = g.variable(name + '/kernel', (k, k, cin, filters), pack_winograd_kernel)
-            op = WinogradConvOp(name, input, y, kern, bias, relu, None)
-            op.workspace = g.winograd_workspace(op.workspace_bytes())
-            self._emit(op)
-            return y
-        kern = g.variable(name + '/kernel', (k, k, cin, filters), pack_conv_kernel)
-        self._emit(ConvOp(name, input, y, kern, bias, k, k, strides, relu))
+        route = routing.choose(g, input, y, k, strides, biased)
+        bias = g.variable(name + '/bias', (filters,), route.bias_pack) if biased else None
+        kern = g.variable(name + '/kernel', (k, k, cin, filters), route.kernel_pack)
+        self._emit(ConvOp.routed(route, name, input, y, kern, bias, k, k, strides, relu))
         return y
 
     @layer

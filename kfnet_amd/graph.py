@@ -10,6 +10,7 @@ PyTorch is used only as the device allocator / stream provider.  Shape inference
 graph construction work without a GPU (device=None); running does not.
 """
 import contextlib
+import copy
 import ctypes as C
 
 import numpy as np
@@ -484,6 +485,56 @@ class ConvOp(Op):
         self.k_step = 0           # 0 = the library's choice
         self._desc = None
 
+    # -- the kernel route (kfnet_amd.routing names them; only these methods put an op on one) -----------------------
+    ROUTE_OPTIONS = ('eight_wave', 'k_split', 'f42')      # per-class routing state: an op carries those of its class only
+    workspace = None                                      # Storage of a route that needs one
+
+    @staticmethod
+    def routed(route, name, x, y, kernel, bias, kh, kw, stride, relu):
+        """A new op on `route`; its variables were created with the route's packers."""
+        op = ConvOp(name, x, y, kernel, bias, kh, kw, stride, relu)
+        op._take(route)
+        op._attach_workspace(route.workspace)
+        return op
+
+    def reroute(self, route):
+        """Move this op to another route in place (the object may already sit in several launch lists): same tensors and
+        variables, the new route's class, options, weight layout and workspace; nothing of the old route stays.  Refused when
+        the weights are already on the device in another layout."""
+        if self.kernel.storage is not None and route.kernel_pack is not self.kernel.pack:
+            there = copy.copy(self)
+            there._take(route)
+            lib = _lib.load()
+            raise _lib.KfnError('%s: weights are already packed for %s, the layer cannot move to %s'
+                                % (self.name, self.kernel_name(lib), there.kernel_name(lib)))
+        self.kernel.pack = route.kernel_pack
+        if self.bias is not None:
+            self.bias.pack = route.bias_pack
+        g = self.x.graph
+        if self.workspace is not None and self.workspace is not g.winograd_ws and self.workspace in g.storages:
+            g.storages.remove(self.workspace)         # a private split-K workspace leaves with the route
+        self.__dict__.pop('workspace', None)
+        self._take(route)
+        self._attach_workspace(route.workspace)
+        return self
+
+    def _take(self, route):
+        for opt in self.ROUTE_OPTIONS:
+            self.__dict__.pop(opt, None)
+        self.__class__ = route.op_class
+        self.operand_dtype = route.operand_dtype
+        for opt in self.ROUTE_OPTIONS:
+            if getattr(route, opt) is not None:
+                setattr(self, opt, getattr(route, opt))
+
+    def _attach_workspace(self, kind):
+        g = self.x.graph
+        if kind == 'shared':
+            self.workspace = g.winograd_workspace(self.workspace_bytes())
+        elif kind == 'private':
+            self.workspace = Storage((self.workspace_bytes() + 3) // 4, 'f32')
+            g.storages.append(self.workspace)
+
     def desc(self):
         n, h, w, cin = self.x.shape
         cout = self.y.shape[3]
@@ -559,21 +610,8 @@ class ConvOp(Op):
 class WindowFcConvOp(ConvOp):
     """3x3 stride-1 SAME conv on 2x2 images (OFlowNet's bottleneck level) as one dense [4 Cin] x [4 Cout] matrix per
     window through the 1x1 path of kfn_conv2d_nhwc (pack_window_fc_kernel): 16/36 of the nine-tap form's MFMAs.
-    Needs both tensors pixel-contiguous; `resolve()` (called by Graph.finalize, after every concat has re-bound its
-    producers) falls back to the plain convolution otherwise."""
-
-    def __init__(self, name, x, y, kernel, bias, relu):
-        ConvOp.__init__(self, name, x, y, kernel, bias, 3, 3, 1, relu)
-
-    def resolve(self):
-        if self.x.ld == self.x.shape[3] and self.y.ld == self.y.shape[3]:
-            return
-        if self.kernel.storage is not None:
-            raise _lib.KfnError('%s: weights already packed as a window matrix' % self.name)
-        self.kernel.pack = as_f16(pack_conv_kernel) if self.operand_dtype == _lib.OPERAND_F16 else pack_conv_kernel
-        if self.bias is not None:
-            self.bias.pack = pack_bias
-        self.__class__ = ConvOp
+    Needs both tensors pixel-contiguous; Graph.resolve_routes (after every concat has re-bound its producers) falls back to
+    the plain convolution otherwise."""
 
     def desc(self):
         n, h, w, cin = self.x.shape
@@ -590,11 +628,8 @@ class WindowFcConvOp(ConvOp):
 
 
 class WinogradConvOp(ConvOp):
-    """3x3 stride-1 SAME conv through kfn_conv2d_winograd (2.25x fewer MFMA FLOPs)."""
-
-    def __init__(self, name, x, y, kernel, bias, relu, workspace):
-        ConvOp.__init__(self, name, x, y, kernel, bias, 3, 3, 1, relu)
-        self.workspace = workspace  # Storage shared by all Winograd layers of the graph
+    """3x3 stride-1 SAME conv through kfn_conv2d_winograd (2.25x fewer MFMA FLOPs); `workspace` is the Storage all such
+    layers of the graph share."""
 
     def kernel_name(self, lib):
         d = self.desc()
@@ -625,9 +660,6 @@ class WinogradFusedConvOp(ConvOp):
     picks the form: four waves sharing one input transform through LDS (wino3_kernel, 128 output channels
     per workgroup) when Cout >= 128 and Cin % 32 == 0, two waves sharing it (wino3_pair_kernel) for 33 .. 64 output
     channels with Cin % 16 == 0, else one wave per 32 output channels (wino2_kernel)."""
-
-    def __init__(self, name, x, y, kernel, bias, relu, operand_dtype=_lib.OPERAND_F32):
-        ConvOp.__init__(self, name, x, y, kernel, bias, 3, 3, 1, relu, operand_dtype=operand_dtype)
 
     @staticmethod
     def supported(x_shape, cin, cout, operand_dtype=_lib.OPERAND_F32):
@@ -688,13 +720,8 @@ class WinogradF43ConvOp(ConvOp):
     """3x3 stride-1 SAME conv through kfn_conv2d_winograd_f43 (csrc/kfn_wino4.hip): F(4x4,3x3), one launch, no workspace.
     eight_wave (Graph.winograd_f43_eight_wave, the default): wino4b_kernel -- two waves per SIMD on 16x16x4 MFMA tiles, 36
     accumulators of 4 registers per wave, weights packed per pair of positions (pack_winograd_f43_kernel_b); else
-    wino4_kernel -- four waves on 32x32x2 tiles, 18 accumulators of 16 registers (pack_winograd_f43_kernel)."""
-
-    def __init__(self, name, x, y, kernel, bias, relu, eight_wave=True, k_split=1, workspace=None):
-        ConvOp.__init__(self, name, x, y, kernel, bias, 3, 3, 1, relu)
-        self.eight_wave = eight_wave
-        self.k_split = int(k_split)      # > 1: kfn_conv2d_winograd_f43_splitk (eight-wave form only) with the graph's shared workspace
-        self.workspace = workspace
+    wino4_kernel -- four waves on 32x32x2 tiles, 18 accumulators of 16 registers (pack_winograd_f43_kernel).
+    k_split > 1: kfn_conv2d_winograd_f43_splitk (eight-wave form only) with a private workspace."""
 
     SS_US = 3.8      # one super-step (16 input channels) of a workgroup: 144 MFMAs of 32 cycles on each of two waves per SIMD
 
@@ -728,25 +755,6 @@ class WinogradF43ConvOp(ConvOp):
                 and ldy % 4 == 0 and y_ch_off % 4 == 0
                 and 2 * h * w * ldx * 4 < (1 << 30) and 2 * h * w * ldy * 4 < (1 << 31)
                 and 36 * (-(-cout // 32) * 32) * cin * 4 < (1 << 31))
-
-    def resolve(self):
-        """Graph.finalize: a later concat may have re-bound the output into a wider buffer; if the F(4x4,3x3) launcher
-        would now reject it, fall back to the fused F(2x2,3x3) kernel (dword stores for unaligned outputs) or the direct
-        one -- the weights are not packed yet."""
-        n, h, w, cin = self.x.shape
-        if self.supported(self.x.shape, cin, self.y.shape[3], self.x.ld, self.y.ld, self.y.ch_off):
-            return
-        if self.kernel.storage is not None:
-            raise _lib.KfnError('%s: weights already packed for the F(4x4,3x3) kernel' % self.name)
-        self.__dict__.pop('eight_wave', None)
-        self.__dict__.pop('k_split', None)
-        self.workspace = None
-        if WinogradFusedConvOp.supported(self.x.shape, cin, self.y.shape[3]) and min(h, w) >= 8:
-            self.kernel.pack = pack_winograd_fused_kernel
-            self.__class__ = WinogradFusedConvOp
-        else:
-            self.kernel.pack = pack_conv_kernel
-            self.__class__ = ConvOp
 
     @staticmethod
     def workgroups(x_shape, cout):
@@ -806,9 +814,6 @@ class Conv64RowsF16Op(ConvOp):
     resident in registers, every input row read from LDS once for the three output rows it feeds -- SCoordNet's conv1b in
     BASELINE config 5."""
 
-    def __init__(self, name, x, y, kernel, bias, relu):
-        ConvOp.__init__(self, name, x, y, kernel, bias, 3, 3, 1, relu, operand_dtype=_lib.OPERAND_F16)
-
     @staticmethod
     def supported(x, y, cin, cout):
         n, h, w, _ = x.shape
@@ -835,23 +840,14 @@ class Conv64RowsF16Op(ConvOp):
 
 class WinogradS2ConvOp(ConvOp):
     """3x3 stride-2 SAME conv of an even-sized image through kfn_conv2d_winograd_s2 (polyphase + F(2,2):
-    25 MFMA streams into 9 accumulators per 2x2 outputs instead of 36 direct taps)."""
+    25 MFMA streams into 9 accumulators per 2x2 outputs instead of 36 direct taps).  Three forms, fp32 operands only beyond
+    the first:
+    f42: wino_s2c_kernel -- polyphase + F(4,2) on 4x4 output tiles, 81 instead of 100 products per 16 outputs (H, W multiples
+      of 8; weights pack_winograd_s2_kernel_c).  Blocks of 16x16 output pixels: for launches that fill the chip several times.
+    eight_wave: wino_s2b_kernel (two waves per SIMD on 16x16x4 MFMA tiles; weights packed per pair of fragments,
+      pack_winograd_s2_kernel_b) instead of wino_s2_kernel; k_split > 1: kfn_conv2d_winograd_s2_splitk with a private workspace."""
 
     SS_US = 5.3      # one super-step of wino_s2b_kernel: 200 MFMAs of 32 cycles on each of two waves per SIMD
-
-    def __init__(self, name, x, y, kernel, bias, relu, operand_dtype=_lib.OPERAND_F32, eight_wave=False, k_split=1, workspace=None,
-                 f42=False):
-        ConvOp.__init__(self, name, x, y, kernel, bias, 3, 3, 2, relu, operand_dtype=operand_dtype)
-        # wino_s2c_kernel: polyphase + F(4,2) on 4x4 output tiles, 81 instead of 100 products per 16 outputs (fp32; H, W multiples
-        # of 8; weights pack_winograd_s2_kernel_c).  Blocks of 16x16 output pixels: for launches that fill the chip several times.
-        self.f42 = bool(f42) and operand_dtype == _lib.OPERAND_F32
-        if self.f42:
-            eight_wave, k_split = False, 1
-        self.k_split = int(k_split)      # > 1: kfn_conv2d_winograd_s2_splitk (eight-wave form, fp32) with a private workspace
-        self.workspace = workspace
-        # wino_s2b_kernel (two waves per SIMD on 16x16x4 MFMA tiles; fp32 operands; weights packed per pair of fragments,
-        # pack_winograd_s2_kernel_b) instead of wino_s2_kernel
-        self.eight_wave = bool(eight_wave) and operand_dtype == _lib.OPERAND_F32
 
     def desc(self):
         d = ConvOp.desc(self)
@@ -883,22 +879,12 @@ class WinogradS2ConvOp(ConvOp):
         th, tw = -(-ho // 4), -(-wo // 4)
         return (-(-tw // 4)) * (-(-(n * th) // 4)) * (-(-cout // 128))
 
-    def resolve(self):
-        """After every concat has re-bound its producers: the F(4,2) form and the split-K form store 16 bytes at a time."""
-        y = self.y
-        if self.f42 and not self.f42_supported(self.x.shape, self.x.shape[3], y.shape[3], y.ld, y.ch_off):
-            if self.kernel.storage is not None:
-                raise _lib.KfnError('%s: output window (ld %d, channel offset %d) cannot take the F(4,2) stride-2 form and its weights '
-                                    'are already uploaded in that layout' % (self.name, y.ld, y.ch_off))
-            self.f42, self.eight_wave = False, True          # the F(2,2) eight-wave form has a dword-store path
-            self.kernel.pack = pack_winograd_s2_kernel_b
-        if self.k_split > 1 and (y.ld % 4 != 0 or y.ch_off % 4 != 0):
-            # (ADVICE r5) kfn_conv2d_winograd_s2_splitk needs a 16-byte aligned output with ldy % 4 == 0; the plain eight-wave
-            # launch takes the dword-store path instead
-            self.k_split = 1
-            if self.workspace is not None and self.workspace in self.x.graph.storages:
-                self.x.graph.storages.remove(self.workspace)
-            self.workspace = None
+    @staticmethod
+    def base_workgroups(y_shape):
+        """Blocks of 8 x 4 tiles of 2x2 OUTPUT pixels (batch rows packed) x column blocks of 128 output channels."""
+        n, ho, wo, cout = y_shape
+        th, tw = (ho + 1) // 2, (wo + 1) // 2
+        return (-(-tw // 8)) * (-(-(n * th) // 4)) * (-(-cout // 128))
 
     def kernel_name(self, lib):
         if self.f42:
@@ -925,19 +911,12 @@ class WinogradS2ConvOp(ConvOp):
         return 2.0 * 25 * tiles * (-(-cout // 128) * 128) * self.x.shape[3]
 
     def workgroups(self, lib=None):
-        """Blocks of 8 x 4 tiles of 2x2 OUTPUT pixels (batch rows packed) x column blocks of 128 output channels."""
+        """Workgroups of this op's launch: of the frames it actually runs, every split-K run counted."""
         n, ho, wo, cout = self.y.shape
-        n = _scaled(n, self.x.graph)
+        shape = (_scaled(n, self.x.graph), ho, wo, cout)
         if self.f42:
-            return self.f42_workgroups((n, ho, wo, cout))
-        th, tw = (ho + 1) // 2, (wo + 1) // 2
-        return (-(-tw // 8)) * (-(-(n * th) // 4)) * (-(-cout // 128)) * max(1, self.k_split)
-
-    @staticmethod
-    def base_workgroups(y_shape):
-        n, ho, wo, cout = y_shape
-        th, tw = (ho + 1) // 2, (wo + 1) // 2
-        return (-(-tw // 8)) * (-(-(n * th) // 4)) * (-(-cout // 128))
+            return self.f42_workgroups(shape)
+        return self.base_workgroups(shape) * max(1, self.k_split)
 
     @classmethod
     def best_k_split(cls, workgroups, cin, out_bytes, max_split=8, cus=256):
@@ -1537,8 +1516,8 @@ class Graph(object):
         # 3x3 stride-2 layers of even-sized images with at least this many input / 128 output channels take the
         # polyphase F(2,2) kernel (kfn_conv2d_winograd_s2); 0 = always the direct implicit GEMM
         self.winograd_s2_min_channels = 64
-        self.winograd_s2_f16 = False
-        self.window_fc = True   # 3x3 stride-1 layers on 2x2 images as one dense matrix per window (WindowFcConvOp)   # fp16-operand mode: stride-2 layers stay on the direct fp16 kernel (faster)
+        self.winograd_s2_f16 = False   # fp16-operand mode: stride-2 layers stay on the direct fp16 kernel (faster)
+        self.window_fc = True   # 3x3 stride-1 layers on 2x2 images as one dense matrix per window (WindowFcConvOp)
         # conv0 of OFlowNet by linearity: per-pixel class convolutions + a gather instead of a
         # 3x3 conv on every one of the 64 window cells (see kfn_cost_volume_gather)
         self.factor_cost_volume = True
@@ -1609,13 +1588,20 @@ class Graph(object):
                                 'gfx950 device (there is no CPU fallback)')
         _lib.load()
         self.device = torch.device(device)
-        for op in self.ops:          # routing decisions that depend on the final buffer bindings
-            if hasattr(op, 'resolve'):
-                op.resolve()
+        self.resolve_routes()
         self.assign_layouts()
         for s in self.storages:
             s.allocate(self.device)
         return self
+
+    def resolve_routes(self):
+        """The routing decisions that depend on the final buffer bindings: a later concat may have re-bound a convolution's
+        output into a window its kernel cannot take (kfnet_amd.routing.after_binding)."""
+        from .routing import after_binding
+        for op in self.ops:
+            route = after_binding(op) if isinstance(op, ConvOp) else None
+            if route is not None:
+                op.reroute(route)
 
     @staticmethod
     def _tensor_refs(op):
@@ -1636,7 +1622,7 @@ class Graph(object):
                 yield r
 
     def assign_layouts(self):
-        """Channel-blocked layout for the tensors that only Winograd launches touch (after resolve(): the routes are final).
+        """Channel-blocked layout for the tensors that only Winograd launches touch (after resolve_routes(): the routes are final).
         A tensor qualifies when it is a dense fp32 root tensor of the graph with C % 16 == 0, EVERY reference any op holds is
         the tensor itself (no views), exactly one op writes it (as .y) and all others read it as .x, and all of them launch a
         kernel that takes KFN_LAYOUT_C16.  Anything else -- inputs, outputs, concat members, tensors the cost volume, the

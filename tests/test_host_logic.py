@@ -50,9 +50,7 @@ def test_assign_layouts_blocks_only_what_winograd_launches_own():
     conv6 (read by the 1x1 conv7) stay NHWC, and so does everything at batch 1, where the stride-2 layers take the F(2,2) kernel.  A
     tensor somebody else also reads, a concat member and a view disqualify; blocked tensors refuse channel views and re-binding."""
     def blocked(g):
-        for op in g.ops:
-            if hasattr(op, 'resolve'):
-                op.resolve()
+        g.resolve_routes()
         return sorted(g.assign_layouts())
     chain = ['conv1b', 'conv2a', 'conv2b', 'conv3a', 'conv3b', 'conv4a', 'conv4b', 'conv5']
     g20, net20 = _build(20)
@@ -183,10 +181,10 @@ def test_default_routes_of_the_3x3_layers():
     assert all(op.kernel_name(lib).startswith('wino_s2b_kernel') for op in s2_layers(g1))
     gn, _ = _build(20, winograd_s2_f42=False)
     assert all(op.kernel_name(lib) == 'wino_s2b_kernel' for op in s2_layers(gn))
-    # a concat that re-binds the output to a window the 16-byte stores cannot take: resolve() falls back to the F(2,2) form
+    # a concat that re-binds the output to a window the 16-byte stores cannot take: resolve_routes() falls back to the F(2,2) form
     kf = s2_layers(g20)[2]
     kf.y._ld, kf.y._off = kf.y.shape[3] + 2, 2
-    kf.resolve()
+    g20.resolve_routes()
     assert kf.kernel_name(lib) == 'wino_s2b_kernel' and kf.kernel.pack.__name__ == 'pack_winograd_s2_kernel_b' and kf.desc().wino_form == 4
     gs, _ = _build(4, winograd_s2_eight_wave=False, winograd_s2_f42=False)
     ks = [op for op in gs.ops if op.name == 'conv3a'][0]
