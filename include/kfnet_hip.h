@@ -51,7 +51,8 @@ extern "C" {
  * kfn_coord_loss_desc.dist_threshold / min_uncertainty and the two thresholds of kfn_eval_metrics (layout and signature
  * change: an ABI-12 host must be rebuilt); later kfn_frame_channel_sums and kfn_augment_batch (augmenting a training
  * batch), added exports that leave every ABI-13 host working, so the number stays; likewise kfn_decode_png_gray16,
- * kfn_depth_labels and kfn_label_moments (training labels from depth maps and poses). */
+ * kfn_depth_labels and kfn_label_moments (training labels from depth maps and poses), and kfn_measurement_map,
+ * kfn_filter_loss_grad, kfn_filter_backward_scratch_bytes and kfn_filter_backward (fine-tuning SCoordNet through the filter). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -806,6 +807,73 @@ typedef struct kfn_label_moments_desc {
   double pivot[3];
 } kfn_label_moments_desc;
 int kfn_label_moments(const kfn_label_moments_desc* desc, const float* labels, double* partial, void* stream);
+
+/* ---- fine-tuning SCoordNet through the Kalman filter, OFlowNet frozen (added exports; the ABI number stays 13) ---------
+ * Stage 3 of the reference under --fix_flownet (KFNet/train.py:268-298, KFNet.GetKFCoordBatch KFNet/KFNet.py:102-146;
+ * DESIGN.md 6e).  A step sees S groups of T frames.  The forward filter is kfn_kalman_scan_ex with opt_temp and opt_kf, a
+ * reset on frame 0 of every group, raw_on_reset = 0, no NIS gate and no transform: training and eval share that launch.
+ *
+ * kfn_measurement_map -- meas [pixels][4] = (x, y, z, exp(log sigma)) from SCoordNet's raw output pred [pixels][ld_pred]
+ * (KFNet.GetMeasureCoord, KFNet/KFNet.py:60-68): what the scan reads as the measurement.  meas 16-byte aligned. */
+int kfn_measurement_map(const float* pred, int ld_pred, float* meas, long pixels, void* stream);
+
+/* kfn_filter_loss_grad -- L = weight_measure L_m + weight_temporal L_t + weight_kf L_KF (0.2, 0.2, 0.6: KFNet/train.py:293-295),
+ * each term CoordLossWithUncertainty (KFNet/KFNet.py:192-232) + smooth_weight SmoothLoss (:430-467) of one of the three
+ * outputs (MeasureCoordLoss :234-254, TemporalCoordLoss :256-278, KFCoordLoss :280-300) on the labels kfn_coord_loss_grad
+ * reads, with one valid = sum(mask) + 1 over the whole batch.
+ *   pred    [B,h,w,ld_pred]  the raw prediction (x, y, z, log sigma): sigma = exp(ch3)
+ *   temp, kf [B,h,w,4]       the scan's opt_temp / opt_kf, B = S T: (x, sigma), the uncertainty u = max(sigma, min_uncertainty)
+ *   labels, img, the clip, the threshold and the smoothness: as for kfn_coord_loss_grad
+ *   dpred   [B,h,w,ld_dpred] channels 0..3 = weight_measure dL_m/dpred, as kfn_coord_loss_grad writes them
+ *   d_temp, d_kf [B,h,w,4]   the DIRECT gradients dL/d(x, sigma) of the two filter outputs (kfn_filter_backward's input)
+ *   stats[16] = (L, NLL of m / t / KF, smoothness of m / t / KF, accuracy of m / t / KF, valid, [11] not written here,
+ *               the three terms NLL + smooth_weight smoothness, 0); L is formed in fp32 from the three rounded terms.
+ * One workgroup, any grid; per-pixel terms in unfused fp32, sums in fp64 over a fixed tree; the smoothness never reaches
+ * across a frame seam.  With weights (1, 0, 0) stats and dpred equal kfn_coord_loss_grad's bit for bit. */
+typedef struct kfn_filter_loss_desc {
+  int32_t struct_size;      /* = sizeof(kfn_filter_loss_desc) */
+  int32_t B, h, w;
+  int32_t ld_pred, ld_dpred;
+  int32_t label_stride, img_stride;
+  int32_t has_transform;
+  float transform[12];      /* first 3 rows of transform.txt, row-major */
+  int32_t has_loss_clip;
+  float loss_clip;
+  float smooth_weight;      /* 50 */
+  float weight_measure, weight_temporal, weight_kf;   /* 0.2, 0.2, 0.6 */
+  double dist_threshold;    /* 0.05: compared as float(dist_threshold * dist_threshold), 0x3B23D70A */
+  double min_uncertainty;   /* 1e-5 */
+} kfn_filter_loss_desc;
+int kfn_filter_loss_grad(const kfn_filter_loss_desc* desc, const float* pred, const float* temp, const float* kf,
+                         const float* labels, const uint8_t* img, float* dpred, float* d_temp, float* d_kf, float* stats,
+                         void* stream);
+
+/* kfn_filter_backward -- the reverse scan t = T-1 .. 0 per sequence: d_temp[t] and d_kf[t] go back through BuildKFCoord
+ * (KFNet/KFNet.py:148-162: K, both max(1-K, 0) gates, the square root) to (z_t, sigma_z,t) and to (x^-, sigma^-); sigma^- through
+ * the variance chain (:393-401) to s_l, zero where s_l^2 is below the floor float(min_uncertainty^2); (x^-, s_l) through the
+ * transpose of tools.util.bilinear_sampler (tools/util.py:36-93, clamped corners, weights from the clamped corners) onto
+ * KF_{t-1}, added to d_kf[t-1].  At t = 0 d_temp[0] + d_kf[0] fall on the measurement (KFNet.py:122-126).  The measurement's
+ * gradients are added to dpred: channels 0..2 as they are, channel 3 times sigma_z.  Flow and sigma_trans are constants.
+ *   flow_xy [S,T,HW,2], meas / temp / kf [S,T,HW,4]: the scan's inputs and outputs; frame 0's flow is not read
+ *   d_temp  [S,T,HW,4] in;  d_kf [S,T,HW,4] in / out: on return the total gradient with respect to every KF_t
+ *   dpred   [S T HW, ld_dpred] in / out;  scratch: kfn_filter_backward_scratch_bytes(), 16-byte aligned
+ *   stats   word 11 receives, as a uint32, the number of pixels of frames >= 1 with |u| or |v| > radius (or NaN): their
+ *           gradient would be lost, the caller must refuse the step when it is not 0.
+ * The transpose is a gather: every source cell sums, rows then columns ascending, the targets within radius + 1 of it,
+ * recomputing their corners and weights from the flow -- no floating-point atomics, so the result is bit-identical from
+ * launch to launch and correct for every flow inside the radius.  T stream-ordered launches of S HW threads, any grid. */
+typedef struct kfn_filter_backward_desc {
+  int32_t struct_size;      /* = sizeof(kfn_filter_backward_desc) */
+  int32_t S, T, H, W;
+  int32_t ld_dpred;
+  int32_t radius;           /* >= 4: the soft-argmax over offsets -4..3 cannot leave 4 */
+  int32_t reserved;         /* 0 */
+  double min_uncertainty;   /* 1e-5, as kfn_kalman_desc's */
+} kfn_filter_backward_desc;
+int kfn_filter_backward_scratch_bytes(const kfn_filter_backward_desc* desc, size_t* bytes);
+int kfn_filter_backward(const kfn_filter_backward_desc* desc, const float* flow_xy, const float* meas, const float* temp,
+                        const float* kf, const float* d_temp, float* d_kf, float* dpred, float* stats, void* scratch,
+                        void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,127 @@
+"""Stage 3 of the reference README's "Training" with OFlowNet frozen: fine-tune SCoordNet through the Kalman filter.
+
+    python -m kfnet_amd.KFNet.train --input_folder I --model_folder M --scene S --fix_flownet --scoordnet A --oflownet B
+
+I is the folder of `python -m kfnet_amd.SCoordNet.train` (image_list.txt, label_list.txt, transform.txt; or, with --depth,
+depth_list.txt and pose_list.txt).  A step trains --groups groups of four consecutive frames, forward or reversed
+(get_indexes, KFNet/train.py:60-147), on 0.2 L_measure + 0.2 L_temporal + 0.6 L_KF (:293-295); the gradients reach ScoreNet/*
+through the Kalman update, the variance chain and the warp of the previous estimate.  Temporal/* is used as it
+is restored and written back unchanged.
+
+Restoring follows KFNet/train.py:398-408: first the newest snapshot of M (all scopes, with its Adam slots), then ScoreNet/*
+from the newest snapshot of --scoordnet, then Temporal/* from that of --oflownet; a scope that nothing restores starts from an
+untrained graph's values.  With both --scoordnet and --oflownet the step starts at 4 * stepvalue (set_stepvalue, :348-350).
+Snapshots go to M as kfnet_weights-<step>.npz (both scopes: `python -m kfnet_amd.KFNet.eval --model_folder M` reads it as it
+is) and kfnet_train_state-<step>.npz.
+
+The flags are the reference's (KFNet/train.py:14-47) and stage 1's.  Without --fix_flownet the program stops: training
+OFlowNet is not built.  --augment is refused: the reference's stage 3 has none.  --loss_clip is off by default, as in stage 1.
+"""
+import argparse
+import sys
+import time
+from datetime import datetime
+
+from .. import modes
+from ..SCoordNet.train import build_parser as stage1_parser, schedule
+
+FORMAT = ('[%s] epoch %d, step %d/%d, %5d~%5d~%5d~%5d, loss=%.3f, l_measure=%.3f, l_temp=%.3f, l_KF= %.3f, '
+          'a_measure=%.3f, a_temp=%.3f,a_KF=%.3f, #pixels=%d, lr = %.6f (%.3f sec/step)')       # KFNet/train.py:427-428
+
+
+def format_line(now, epoch, step, max_steps, group, s, duration):
+    """KFNet/train.py:427-432."""
+    return FORMAT % (now, epoch, step, max_steps, group[0], group[1], group[2], group[3], s['loss'], s['l_measure'], s['l_temp'],
+                     s['l_KF'], s['a_measure'], s['a_temp'], s['a_KF'], s['pixels'], s['lr'], duration)
+
+
+def build_parser():
+    ap = stage1_parser()
+    ap.description = __doc__
+    ap.add_argument('--scoordnet', default='', help='model folder whose newest snapshot gives ScoreNet/*')
+    ap.add_argument('--oflownet', default='', help='model folder whose newest snapshot gives Temporal/*')
+    ap.add_argument('--fix_flownet', action='store_true', help='keep OFlowNet as restored (required)')
+    ap.add_argument('--groups', type=int, default=1, help='groups of four frames per step')
+    ap.add_argument('--sequence_length', type=int, default=None, help='frames per range of get_indexes (500 for stairs, else 1000)')
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    if a.scene not in modes.SCENES:
+        print('Invalid scene:', a.scene)
+        return 1
+    if not a.fix_flownet:
+        print('training OFlowNet is not built: run with --fix_flownet (OFlowNet stays as restored)', file=sys.stderr)
+        return 1
+    if a.augment:
+        print('--augment is refused: stage 3 of the reference trains without augmentation', file=sys.stderr)
+        return 1
+    if not a.model_folder:
+        print('--model_folder is required: the snapshots go there', file=sys.stderr)
+        return 1
+    if a.display < 1 or a.snapshot < 1 or a.groups < 1:
+        print('--display, --snapshot and --groups must be >= 1', file=sys.stderr)
+        return 1
+    from ..train_kfnet import GROUP, group_indices, group_list, sequence_length, start_step
+    stepvalue, max_steps = schedule(a.scene, a.stepvalue, a.max_steps)
+    length = sequence_length(a.scene) if a.sequence_length is None else a.sequence_length
+    from ..batches import open_source
+    from ..staging import check_size
+    a.batch = a.groups * GROUP                       # what a DepthSource sizes its labeler by
+    try:
+        check_size(a.height, a.width, '--height and --width')
+        if length < GROUP:
+            raise ValueError('--sequence_length must be at least %d' % GROUP)
+        source = open_source(a, False)
+        groups = group_list(source.count, length)
+        if not groups:
+            raise ValueError('%d frames hold no group of %d consecutive frames' % (source.count, GROUP))
+    except (OSError, ValueError) as e:
+        print(e, file=sys.stderr)
+        return 1
+    from ..train_kfnet import FLOW_SCOPE, KFNetTrainer, restore
+    from ..train import SCOPE
+    try:
+        W, state, step = restore(a.model_folder, a.scoordnet, a.oflownet)
+    except (OSError, ValueError) as e:
+        print(e, file=sys.stderr)
+        return 1
+    from ..weights import initial_weights
+    for scope in (SCOPE, FLOW_SCOPE):
+        if not any(k.startswith(scope + '/') for k in W):
+            W.update(initial_weights(a.seed, scopes=(scope,)))
+            print('nothing restores %s/*: starting from untrained weights (seed %d)' % (scope, a.seed))
+    import torch
+    torch.cuda.set_device(a.gpu)
+    tr = KFNetTrainer(W, image_size=(a.height, a.width), groups=a.groups, transform=source.transform, base_lr=a.base_lr,
+                      gamma=a.gamma, stepvalue=stepvalue, weight_decay=a.weight_decay, loss_clip=a.loss_clip,
+                      smooth_weight=a.smooth_weight, device='cuda:%d' % a.gpu)
+    if state is not None:
+        tr.load_state(state)
+    tr.global_step = start_step(step, stepvalue, a.reset_step, a.scoordnet, a.oflownet)
+    print('----------------------------------')
+    print('scene: ', a.scene)
+    print('training image number: ', source.count)
+    print('batch size: ', a.groups * GROUP)
+    print('step value: ', stepvalue)
+    print('max steps: ', max_steps)
+    print('current step: ', tr.global_step)
+    print('----------------------------------')
+    while tr.global_step < max_steps:
+        t0 = time.time()
+        indices = group_indices(tr.global_step, a.groups, groups, a.shuffle, a.seed)
+        frames, labels = source.batch(indices, False)
+        stats = tr.step(frames, labels)
+        s = tr.global_step
+        if s % a.display == 0 or s == max_steps:
+            line = dict(stats)           # the read-back waits for the step
+            print(format_line(datetime.now(), s // source.count, s, max_steps, indices[:GROUP], line, time.time() - t0), flush=True)
+        if s % a.snapshot == 0 or s == max_steps:
+            print('snapshot: %s, %s' % tr.save(a.model_folder, s), flush=True)
+    torch.cuda.synchronize()
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -97,6 +97,22 @@ class LabelMomentsDesc(SizedStructure):
     _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'B', 'h', 'w', 'ld', 'reserved')] + [('pivot', C.c_double * 3)])
 
 
+class FilterLossDesc(SizedStructure):
+    """kfn_filter_loss_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
+    _fields_ = [('struct_size', C.c_int32), ('B', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('ld_pred', C.c_int32),
+                ('ld_dpred', C.c_int32), ('label_stride', C.c_int32), ('img_stride', C.c_int32),
+                ('has_transform', C.c_int32), ('transform', C.c_float * 12), ('has_loss_clip', C.c_int32),
+                ('loss_clip', C.c_float), ('smooth_weight', C.c_float), ('weight_measure', C.c_float),
+                ('weight_temporal', C.c_float), ('weight_kf', C.c_float), ('dist_threshold', C.c_double),
+                ('min_uncertainty', C.c_double)]
+
+
+class FilterBackwardDesc(SizedStructure):
+    """kfn_filter_backward_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
+    _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'S', 'T', 'H', 'W', 'ld_dpred', 'radius', 'reserved')] +
+                [('min_uncertainty', C.c_double)])
+
+
 # name -> (restype, argtypes); every symbol declared in include/kfnet_hip.h
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 SYMBOLS = {
@@ -190,6 +206,11 @@ SYMBOLS = {
     'kfn_decode_png_gray16': (_i, [C.POINTER(C.c_char_p), _i, _i, _i, _vp, C.POINTER(_i), _i]),
     'kfn_depth_labels': (_i, [C.POINTER(DepthLabelsDesc), _vp, _vp, _vp, _vp]),
     'kfn_label_moments': (_i, [C.POINTER(LabelMomentsDesc), _vp, _vp, _vp]),
+    # fine-tuning SCoordNet through the Kalman filter (added exports, ABI 13)
+    'kfn_measurement_map': (_i, [_vp, _i, _vp, C.c_long, _vp]),
+    'kfn_filter_loss_grad': (_i, [C.POINTER(FilterLossDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'kfn_filter_backward_scratch_bytes': (_i, [C.POINTER(FilterBackwardDesc), C.POINTER(_sz)]),
+    'kfn_filter_backward': (_i, [C.POINTER(FilterBackwardDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -35,6 +35,8 @@ EXTRA = {
     'kfn_augment.hip': ['-ffp-contract=off'],
     # labels from depth maps: back-projection and pose as a list of rounded fp32 operations
     'kfn_labels.hip': ['-ffp-contract=off'],
+    # the filter's loss and reverse scan: the loss's per-pixel terms and the forward scan's sampler weights, rounded alike
+    'kfn_train_filter.hip': ['-ffp-contract=off'],
 }
 
 

@@ -358,8 +358,8 @@ class SCoordNetTrainer(object):
         for li in range(len(LAYERS)):
             self.forward_layer(li, stream)
 
-    def loss_and_gradients(self, label_stride, stream=None):
-        """Loss on self.act[-1], then the backward pass into self.grads."""
+    def loss(self, label_stride, stream=None):
+        """The loss launch: self.stats, and d(loss)/d(prediction) into self.dact[-1]."""
         stream = staging.current_stream(self.device) if stream is None else stream
         B, (h, w) = self.batch, self.grid
         last = len(LAYERS) - 1
@@ -372,10 +372,20 @@ class SCoordNetTrainer(object):
         _lib.check(self.lib.kfn_coord_loss_grad(C.byref(d), self.act[last].data_ptr(), self.labels.data_ptr(),
                                                 self.frames.data_ptr(), self.dact[last].data_ptr(), self.stats.data_ptr(),
                                                 stream), 'kfn_coord_loss_grad')
+
+    def backward(self, stream=None):
+        """The backward pass from self.dact[-1] (the gradient with respect to the prediction) into self.grads."""
+        stream = staging.current_stream(self.device) if stream is None else stream
+        last = len(LAYERS) - 1
         for li in range(last, 0, -1):
             self.weight_gradient(li, stream)
             self.input_gradient(li, stream)
         self.weight_gradient(0, stream)
+
+    def loss_and_gradients(self, label_stride, stream=None):
+        """Loss on self.act[-1], then the backward pass into self.grads."""
+        self.loss(label_stride, stream)
+        self.backward(stream)
 
     def apply_gradients(self, stream=None):
         """TensorFlow's Adam on the flat buffer, with the regulariser's weight_decay * w folded into the gradient."""

@@ -1,0 +1,289 @@
+"""Fine-tuning SCoordNet through the Kalman filter with OFlowNet frozen: stage 3 of the reference's procedure ("Train KFNet")
+under --fix_flownet (KFNet/train.py:268-298 with KFNet.GetKFCoordBatch, KFNet/KFNet.py:102-162).
+
+A step sees S groups of T consecutive frames (T = 4 on the command line).  Its launches, on top of kfnet_amd.train's:
+
+    flow        OFlowNetEngine.heavy on the Temporal/* weights, on a stream of its own: flow and sigma_trans of every frame
+                from the frame before it in group order -- constants of the step (slot 0 of a group means nothing)
+    forward     SCoordNetTrainer.forward on the S T frames
+    measurement kfn_measurement_map: (z, exp(log sigma)) from the raw prediction
+    filter      kfn_kalman_scan_ex with a reset on frame 0 of every group: the launch eval runs, writing the temporal and KF maps
+    loss        kfn_filter_loss_grad: 0.2 L_measure + 0.2 L_temporal + 0.6 L_KF and the direct gradients of the three outputs
+    backward    kfn_filter_backward: the reverse scan, whose measurement gradients join d(loss)/d(prediction);
+                then SCoordNetTrainer.backward, Adam and the packs as in stage 1
+
+Only ScoreNet/* is trained and regularised; Temporal/* is handed through unchanged.  There is no fallback: a missing entry
+point raises, and so does a flow outside the radius the reverse scan gathers over.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib, staging
+from .train import LAYERS, SCOPE, SCoordNetTrainer, snapshot_paths
+
+FLOW_SCOPE = 'Temporal'
+GROUP = 4                                 # frames per group, KFNet/train.py:60-66
+LOSS_WEIGHTS = (0.2, 0.2, 0.6)            # measure, temporal, KF: KFNet/train.py:293-295
+RADIUS = 4                                # the soft-argmax over the offsets -4..3 cannot leave it
+MIN_UNCERTAINTY = 1e-5
+FLOW_MESSAGE = '%d pixels have a flow beyond the radius %d of kfn_filter_backward: their gradient would be lost'
+
+
+def sequence_length(scene):
+    """The length of the ranges get_indexes draws its groups from (KFNet/train.py:75-141)."""
+    return 500 if scene == 'stairs' else 1000
+
+
+def group_list(count, length, group=GROUP):
+    """KFNet/train.py:60-66 over the ranges [k length, min((k + 1) length, count)): every [i, .., i + group - 1] inside a range
+    followed by its reverse.  A range shorter than `group` yields nothing."""
+    groups = []
+    for start in range(0, count, length):
+        end = min(start + length, count)
+        for i in range(start, end - (group - 1)):
+            fwd = list(range(i, i + group))
+            groups.append(fwd)
+            groups.append(fwd[::-1])
+    return groups
+
+
+def group_indices(step, S, groups, shuffle=False, seed=0):
+    """The frames of update number `step` (from 0): groups step S .. step S + S - 1 of the list, wrapping round; with `shuffle`
+    position q of the stream is entry q % n of a permutation drawn per epoch q // n from (seed, epoch).  A function of its
+    arguments alone, so a resumed run continues the same stream.  Returns S T indices, group after group."""
+    from .train import batch_indices
+    out = []
+    for g in batch_indices(step, S, len(groups), shuffle, seed):
+        out.extend(groups[g])
+    return out
+
+
+def start_step(snapshot_step, stepvalue, reset_step, scoordnet, oflownet):
+    """set_stepvalue's rule (KFNet/train.py:348-350, :364-365): with both --scoordnet and --oflownet the step is reset to 4
+    stepvalue; otherwise an explicit --reset_step wins over the snapshot's step."""
+    if scoordnet and oflownet:
+        return 4 * stepvalue
+    return snapshot_step if reset_step < 0 else reset_step
+
+
+class StepStats(object):
+    """What a step reports, read from the device on first access (so that steps queue): loss, l_measure, l_temp, l_KF (each
+    NLL + 50 smoothness, as the reference logs them), a_measure, a_temp, a_KF, pixels, lr.  The read-back raises when a flow
+    left the radius of the reverse scan."""
+    KEYS = ('loss', 'l_measure', 'l_temp', 'l_KF', 'a_measure', 'a_temp', 'a_KF', 'pixels', 'lr')
+
+    def __init__(self, stats_dev, lr, radius):
+        self._dev, self._lr, self._radius, self._host = stats_dev, lr, radius, None
+
+    def keys(self):
+        return list(self.KEYS)
+
+    def __getitem__(self, k):
+        if self._host is None:
+            s = self._dev.cpu().numpy()
+            check_flow_count(s, self._radius)
+            self._host = dict(loss=float(s[0]), l_measure=float(s[12]), l_temp=float(s[13]), l_KF=float(s[14]),
+                              a_measure=float(s[7]), a_temp=float(s[8]), a_KF=float(s[9]), pixels=float(s[10]) - 1.0,
+                              lr=self._lr)
+        return self._host[k]
+
+
+def check_flow_count(stats_host, radius):
+    n = int(np.asarray(stats_host, dtype=np.float32).view(np.uint32)[11])
+    if n:
+        raise _lib.KfnError(FLOW_MESSAGE % (n, radius))
+
+
+class KFNetTrainer(object):
+    def __init__(self, weights, image_size=(480, 640), groups=1, group=GROUP, transform=None, base_lr=1e-4, gamma=0.5,
+                 stepvalue=80000, weight_decay=1e-4, loss_clip=None, smooth_weight=50.0, loss_weights=LOSS_WEIGHTS,
+                 radius=RADIUS, device='cuda:0'):
+        """weights: {TF name: array} holding ScoreNet/* and Temporal/*.  groups = S, group = T.  The other arguments are
+        SCoordNetTrainer's; loss_weights = (measure, temporal, KF)."""
+        import torch
+        from .engine import OFlowNetEngine
+        if groups < 1 or group < 2:
+            raise ValueError('groups must be >= 1 and group >= 2')
+        self.S, self.T = int(groups), int(group)
+        B = self.S * self.T
+        self.sc = SCoordNetTrainer(weights, image_size=image_size, batch=B, transform=transform, base_lr=base_lr, gamma=gamma,
+                                   stepvalue=stepvalue, weight_decay=weight_decay, loss_clip=loss_clip,
+                                   smooth_weight=smooth_weight, device=device)
+        sc = self.sc
+        self.torch, self.lib, self.device = torch, sc.lib, sc.device
+        self.loss_weights = tuple(float(x) for x in loss_weights)
+        self.radius = int(radius)
+        self.flow_weights = {k: np.asarray(v, dtype=np.float32).copy() for k, v in weights.items()
+                             if k.startswith(FLOW_SCOPE + '/')}
+        h, w = sc.grid
+        with torch.cuda.device(self.device):
+            self.flow_stream = torch.cuda.Stream(device=self.device)
+            self.ev_frames, self.ev_flow = torch.cuda.Event(), torch.cuda.Event()
+            with torch.cuda.stream(self.flow_stream):
+                self.engine = OFlowNetEngine(self.flow_weights, image_size=image_size, batch=self.T, max_chunk=B, device=device)
+            self.flow_stream.synchronize()
+            f32 = dict(dtype=torch.float32, device=self.device)
+            self.meas = torch.zeros((B, h, w, 4), **f32)
+            self.temp = torch.zeros((B, h, w, 4), **f32)
+            self.kf = torch.zeros((B, h, w, 4), **f32)
+            self.d_temp = torch.zeros((B, h, w, 4), **f32)
+            self.d_kf = torch.zeros((B, h, w, 4), **f32)
+            self.records = torch.zeros((B, h, w, 4), **f32)
+            self.filter_state = torch.zeros((self.S, h, w, 4), **f32)
+            self.stats = torch.zeros(16, **f32)
+            self._flow_count = torch.zeros(1, dtype=torch.int32).pin_memory()
+            self.ev_count = torch.cuda.Event()
+            # frame 0 of every group is a reset frame (t0 = 0, reset_period = T): both estimates equal the measurement
+            self.scan_desc = _lib.KalmanDesc(S=self.S, T=self.T, H=h, W=w, t0=0, reset_period=self.T,
+                                             min_uncertainty=MIN_UNCERTAINTY, nis_gate=0.0, has_transform=0)
+            need = C.c_size_t(0)
+            _lib.check(self.lib.kfn_kalman_scan_scratch_bytes(C.byref(self.scan_desc), C.byref(need)),
+                       'kfn_kalman_scan_scratch_bytes')
+            self.scan_scratch = torch.zeros(-(-need.value // 4), **f32) if need.value else None
+            self.back_desc = _lib.FilterBackwardDesc(S=self.S, T=self.T, H=h, W=w, ld_dpred=sc.dact[-1].shape[3],
+                                                     radius=self.radius, min_uncertainty=MIN_UNCERTAINTY)
+            _lib.check(self.lib.kfn_filter_backward_scratch_bytes(C.byref(self.back_desc), C.byref(need)),
+                       'kfn_filter_backward_scratch_bytes')
+            self.back_scratch = torch.zeros(-(-need.value // 4), **f32)
+
+    # ---- what the stage-1 trainer keeps ------------------------------------------------------------------------------
+    global_step = property(lambda self: self.sc.global_step, lambda self, v: setattr(self.sc, 'global_step', v))
+    adam_t = property(lambda self: self.sc.adam_t)
+
+    def weights(self):
+        """Both scopes: ScoreNet/* as trained, Temporal/* as given -- what KFNet.eval --model_folder reads."""
+        W = self.sc.weights()
+        W.update({k: v.copy() for k, v in self.flow_weights.items()})
+        return W
+
+    def gradients(self):
+        return self.sc.gradients()
+
+    def state(self):
+        return self.sc.state()
+
+    def load_state(self, st):
+        self.sc.load_state(st)
+
+    def save(self, folder, step=None):
+        """Writes kfnet_weights-<step>.npz (both scopes) and kfnet_train_state-<step>.npz; returns the two paths."""
+        from .weights import save_npz
+        step = self.global_step if step is None else step
+        os.makedirs(folder, exist_ok=True)
+        wp, sp = snapshot_paths(folder, step)
+        save_npz(wp, self.weights())
+        np.savez(sp, **self.sc.state())
+        return wp, sp
+
+    # ---- one step ----------------------------------------------------------------------------------------------------
+    def flow(self, main):
+        """The frozen OFlowNet on the staged frames, on its own stream, ordered against `main` by events: it starts when the
+        frames are staged, and `main` waits for it in front of the filter."""
+        self.ev_frames.record(main)
+        self.flow_stream.wait_event(self.ev_frames)
+        with self.torch.cuda.stream(self.flow_stream):
+            self.engine.heavy(self.sc.frames, self.S * self.T)
+            self.ev_flow.record(self.flow_stream)
+
+    def forward(self, stream=None):
+        """SCoordNet, the measurement map and the filter: self.meas, self.temp, self.kf.  The flow must have been launched
+        (self.flow) on the same frames."""
+        sc = self.sc
+        main = self.torch.cuda.current_stream(self.device)
+        stream = main.cuda_stream if stream is None else stream
+        sc.forward(stream)
+        B, (h, w) = sc.batch, sc.grid
+        _lib.check(self.lib.kfn_measurement_map(sc.act[-1].data_ptr(), LAYERS[-1][3], self.meas.data_ptr(), B * h * w, stream),
+                   'kfn_measurement_map')
+        main.wait_event(self.ev_flow)
+        _lib.check(self.lib.kfn_memset(self.filter_state.data_ptr(), 0, self.filter_state.numel() * 4, stream),
+                   'kfn_memset state')
+        eng = self.engine
+        _lib.check(self.lib.kfn_kalman_scan_ex(C.byref(self.scan_desc), eng.c_flow.ptr, eng.c_sigma.ptr, self.meas.data_ptr(),
+                                               self.filter_state.data_ptr(), self.records.data_ptr(), self.temp.data_ptr(), None,
+                                               self.kf.data_ptr(), 0,
+                                               self.scan_scratch.data_ptr() if self.scan_scratch is not None else None, stream),
+                   'kfn_kalman_scan_ex')
+
+    def loss(self, label_stride, stream=None):
+        sc = self.sc
+        stream = staging.current_stream(self.device) if stream is None else stream
+        B, (h, w) = sc.batch, sc.grid
+        d = _lib.FilterLossDesc(B=B, h=h, w=w, ld_pred=LAYERS[-1][3], ld_dpred=sc.dact[-1].shape[3], label_stride=label_stride,
+                                img_stride=8, has_transform=int(sc.transform is not None),
+                                has_loss_clip=int(sc.loss_clip is not None), loss_clip=sc.loss_clip or 0.0,
+                                smooth_weight=sc.smooth_weight, weight_measure=self.loss_weights[0],
+                                weight_temporal=self.loss_weights[1], weight_kf=self.loss_weights[2], dist_threshold=0.05,
+                                min_uncertainty=MIN_UNCERTAINTY)
+        if sc.transform is not None:
+            d.transform = (C.c_float * 12)(*[float(x) for x in sc.transform[:3].reshape(-1)])
+        _lib.check(self.lib.kfn_filter_loss_grad(C.byref(d), sc.act[-1].data_ptr(), self.temp.data_ptr(), self.kf.data_ptr(),
+                                                 sc.labels.data_ptr(), sc.frames.data_ptr(), sc.dact[-1].data_ptr(),
+                                                 self.d_temp.data_ptr(), self.d_kf.data_ptr(), self.stats.data_ptr(), stream),
+                   'kfn_filter_loss_grad')
+
+    def filter_backward(self, stream=None):
+        stream = staging.current_stream(self.device) if stream is None else stream
+        eng = self.engine
+        _lib.check(self.lib.kfn_filter_backward(C.byref(self.back_desc), eng.c_flow.ptr, self.meas.data_ptr(),
+                                                self.temp.data_ptr(), self.kf.data_ptr(), self.d_temp.data_ptr(),
+                                                self.d_kf.data_ptr(), self.sc.dact[-1].data_ptr(), self.stats.data_ptr(),
+                                                self.back_scratch.data_ptr(), stream), 'kfn_filter_backward')
+
+    def step(self, frames_u8, labels):
+        """One update on S groups: frames uint8 [S T,H,W,3] group after group in group order, labels float32 [S T,H,W,4] or
+        grid-sized.  Returns StepStats of THIS step's loss, before the update, read back only when accessed.  Raises, before the
+        update is queued, when a flow left the radius of the reverse scan."""
+        sc, torch = self.sc, self.torch
+        with torch.cuda.device(self.device):
+            main = torch.cuda.current_stream(self.device)
+            stream = main.cuda_stream
+            stride = sc.stage(frames_u8, labels, None, stream)
+            self.flow(main)
+            self.forward(stream)
+            self.loss(stride, stream)
+            self.filter_backward(stream)
+            self._flow_count.copy_(self.stats.view(torch.int32)[11:12], non_blocking=True)
+            self.ev_count.record(main)
+            sc.backward(stream)
+            stats = self.stats.clone()
+            # the one wait of a step: for the reverse scan's counter, while the backward pass is still queued
+            self.ev_count.synchronize()
+            if int(self._flow_count[0]):
+                raise _lib.KfnError(FLOW_MESSAGE % (int(self._flow_count[0]), self.radius))
+            lr = sc.apply_gradients(stream)
+            sc._repack(stream)
+        return StepStats(stats, lr, self.radius)
+
+
+def restore(model_folder, scoordnet='', oflownet='', verbose=True):
+    """The reference's restore order (KFNet/train.py:398-408): the newest snapshot of model_folder (all scopes), then
+    ScoreNet/* from the newest snapshot of `scoordnet`, then Temporal/* from that of `oflownet`.  Returns (weights -- possibly
+    lacking a scope --, Adam state or None, step of model_folder's snapshot)."""
+    from .tools.io import get_snapshot
+    from .weights import load_snapshot
+    W, state, step = {}, None, 0
+    snapshot, s = get_snapshot(model_folder) if model_folder and os.path.isdir(model_folder) else (None, 0)
+    if snapshot is not None:
+        W.update(load_snapshot(snapshot, verbose=verbose))
+        step = s
+        sp = snapshot_paths(model_folder, step)[1]
+        if os.path.exists(sp):
+            with np.load(sp) as z:
+                state = {k: z[k] for k in z.files}
+        if verbose:
+            print('Adam slots restored from %s' % sp if state is not None else
+                  'no %s: the Adam slots start at zero' % os.path.basename(sp))
+    for folder, scope in ((scoordnet, SCOPE), (oflownet, FLOW_SCOPE)):
+        if not folder:
+            continue
+        snapshot, _ = get_snapshot(folder)
+        if snapshot is None:
+            raise ValueError('no kfnet_weights*.npz or model.ckpt-*.index in %s' % folder)
+        if verbose:
+            print('Restore from scope', scope, ':', snapshot)
+        part = load_snapshot(snapshot, scopes=(scope,), verbose=verbose)
+        W.update({k: v for k, v in part.items() if k.startswith(scope + '/')})
+    return W, state, step

@@ -3,11 +3,15 @@ frames and labels, the split of a step over its phases, and per layer the weight
 launch as fractions of the fp32 MFMA peak.
 
     python tools/mb_train.py [--height 480 --width 640 --batch 4 --steps 10 --warmup 3] [--layers] [--augment] [--depth]
+    python tools/mb_train.py --kfnet [--groups 1]
 
 --augment times the step with the augmentation of DESIGN.md 6c on: full-resolution labels, the parameters of
 kfnet_amd.augment.draw(0, step) in turn (its kernels are channel_sums_kernel and augment_kernel in a kernel trace).
 --depth makes every step's labels on the device from synthetic depth maps and poses that stay there (stride 8,
 or stride 1 with --augment; depth_labels_grid_kernel / depth_labels_full_kernel in a kernel trace).
+--kfnet times kfnet_amd.train_kfnet.KFNetTrainer instead: ms per step on --groups groups of four frames, and
+the launches it adds to stage 1's step -- the OFlowNet forward, the measurement map and the scan, the three-term loss, the
+reverse scan -- each alone and as a share of the step.
 
 Under `rocprofv3 --kernel-trace --stats -- python tools/mb_train.py --steps 5` the kernel table gives the same split per
 kernel name (wgrad_mfma_kernel, conv_mfma_kernel, ...)."""
@@ -34,6 +38,45 @@ def timed(torch, fn, reps):
     return a.elapsed_time(b) / reps
 
 
+def kfnet(a):
+    import torch
+    from kfnet_amd.synth import synthetic_sequence, synthetic_transform
+    from kfnet_amd.train import synthetic_labels
+    from kfnet_amd.train_kfnet import GROUP, KFNetTrainer
+    from kfnet_amd.weights import initial_weights, synthetic_weights
+    W = initial_weights(0)
+    W.update({k: v for k, v in synthetic_weights(1234).items() if k.startswith('Temporal/')})
+    B = a.groups * GROUP
+    tr = KFNetTrainer(W, image_size=(a.height, a.width), groups=a.groups, transform=synthetic_transform())
+    frames = torch.from_numpy(synthetic_sequence(B, a.height, a.width)).cuda()
+    labels = torch.from_numpy(synthetic_labels(B, tr.sc.grid)).cuda()
+    for _ in range(a.warmup):
+        tr.step(frames, labels)
+    ms = timed(torch, lambda: tr.step(frames, labels), a.steps)
+    print('%dx%d, %d group(s) of %d: %.2f ms per step (%.1f frames/s)' % (a.height, a.width, a.groups, GROUP, ms, 1e3 * B / ms))
+    main = torch.cuda.current_stream()
+    stride = tr.sc.stage(frames, labels, None, main.cuda_stream)
+
+    def flow():
+        tr.flow(main)
+        main.wait_event(tr.ev_flow)
+    tr.flow(main)
+    parts = [('OFlowNet forward', flow), ('SCoordNet forward + measurement map + scan', tr.forward),
+             ('SCoordNet forward', tr.sc.forward), ('three-term loss', lambda: tr.loss(stride)),
+             ('reverse scan', tr.filter_backward), ('SCoordNet backward', tr.sc.backward)]
+    t = {}
+    for name, fn in parts:
+        t[name] = timed(torch, fn, a.steps)
+    scan = t['SCoordNet forward + measurement map + scan'] - t['SCoordNet forward']
+    new = t['OFlowNet forward'] + scan + t['three-term loss'] + t['reverse scan']
+    for name, v in (('OFlowNet forward (alone; in a step it overlaps SCoordNet\'s forward)', t['OFlowNet forward']),
+                    ('measurement map + scan', scan), ('three-term loss', t['three-term loss']), ('reverse scan', t['reverse scan'])):
+        print('%-72s %7.3f ms  %5.1f%% of the step' % (name, v, 100 * v / ms))
+    print('the new launches together %.3f ms = %.1f%% of the step; SCoordNet forward %.2f ms, backward %.2f ms' %
+          (new, 100 * new / ms, t['SCoordNet forward'], t['SCoordNet backward']))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--height', type=int, default=480)
@@ -44,7 +87,11 @@ def main(argv=None):
     ap.add_argument('--layers', action='store_true', help='also time every layer\'s weight-gradient and forward launch')
     ap.add_argument('--augment', action='store_true', help='time the step with augmentation on')
     ap.add_argument('--depth', action='store_true', help='make the labels of every step from depth maps and poses')
+    ap.add_argument('--kfnet', action='store_true', help='time the step of KFNetTrainer (SCoordNet through the filter)')
+    ap.add_argument('--groups', type=int, default=1, help='--kfnet: groups of four frames per step')
     a = ap.parse_args(argv)
+    if a.kfnet:
+        return kfnet(a)
     import torch
     from kfnet_amd import _lib
     from kfnet_amd.synth import synthetic_sequence, synthetic_transform
