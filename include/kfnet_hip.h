@@ -52,7 +52,8 @@ extern "C" {
  * change: an ABI-12 host must be rebuilt); later kfn_frame_channel_sums and kfn_augment_batch (augmenting a training
  * batch), added exports that leave every ABI-13 host working, so the number stays; likewise kfn_decode_png_gray16,
  * kfn_depth_labels and kfn_label_moments (training labels from depth maps and poses), and kfn_measurement_map,
- * kfn_filter_loss_grad, kfn_filter_backward_scratch_bytes and kfn_filter_backward (fine-tuning SCoordNet through the filter). */
+ * kfn_filter_loss_grad, kfn_filter_backward_scratch_bytes and kfn_filter_backward (fine-tuning SCoordNet through the filter),
+ * and kfn_cost_volume_backward, kfn_flow_head_backward, kfn_l2norm_backward and kfn_flow_loss_grad (training OFlowNet). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -874,6 +875,65 @@ int kfn_filter_backward_scratch_bytes(const kfn_filter_backward_desc* desc, size
 int kfn_filter_backward(const kfn_filter_backward_desc* desc, const float* flow_xy, const float* meas, const float* temp,
                         const float* kf, const float* d_temp, float* d_kf, float* dpred, float* stats, void* scratch,
                         void* stream);
+
+/* ---- training OFlowNet: stage 2 of the reference's procedure (added exports; the ABI number stays 13) -------------------
+ * The backward pass of the Temporal scope (cnn_wrapper/OFlowNet.py:17-57, KFNet/KFNet.py:315-403) outside its convolutions,
+ * and the loss of stage 2 (the reference's OFlowNet/train.py is absent, the loss is a stated deviation).
+ * A step sees P pairs (a, b) of frames on the grid h x w = H/8 x W/8.  No floating-point atomics in any of the four: two
+ * launches give the same bits.
+ *
+ * kfn_cost_volume_backward -- the transpose of kfn_cost_volume with window 8 (KFNet.BuildCoordVolume, KFNet/KFNet.py:343-359):
+ *   d_vol [N H W, 8, 8, C] in;  d_f2, d_f1 [N,H,W,C] out (C % 4 == 0, all three 16-byte aligned)
+ *   d_f2[p] =   sum_{i,j} d_vol[p, i, j]
+ *   d_f1[q] = - sum_{i,j} d_vol[q - (i-4, j-4), i, j]   over the (i, j) whose cell q - (i-4, j-4) lies in q's frame
+ * Both are gathers.  ORDER: each output element starts from +0.0f and adds its terms one by one in fp32, i ascending and j
+ * ascending inside i; d_f1 skips the cells outside the grid and negates the finished sum.  A float32 restatement with the
+ * same sequential adds is bit-identical. */
+int kfn_cost_volume_backward(const float* d_vol, float* d_f2, float* d_f1, int N, int H, int W, int C, void* stream);
+
+/* kfn_flow_head_backward -- through kfn_flow_softargmax (softmax over the 64 cells, cnn_wrapper/OFlowNet.py:45-47; flow =
+ * sum_k prob_k o_k with o_k = (j-4, i-4), k = 8 i + j, KFNet/KFNet.py:381-385) and through sigma_trans = exp(pre) 1e-2
+ * (OFlowNet.py:56):
+ *   d_flow [N,2], prob [N,64], d_sigma [N], sigma_trans [N] in
+ *   d_logits [N 64, ld_logits]: channel 0 of row 64 n + k = prob_k (o_k . g - sum_j prob_j o_j . g), g = d_flow[n]; the
+ *            other ld_logits - 1 channels are zeroed (the padded gradient buffer of 'prediction'; ld_logits % 4 == 0)
+ *   d_pre    [N, ld_pre]: channel 0 = d_sigma sigma_trans, the others zeroed (the padded gradient buffer of 'uncertainty') */
+int kfn_flow_head_backward(const float* d_flow, const float* prob, const float* d_sigma, const float* sigma_trans,
+                           float* d_logits, int ld_logits, float* d_pre, int ld_pre, long N, void* stream);
+
+/* kfn_l2norm_backward -- through tf.nn.l2_normalize over feat7's channels (KFNet/KFNet.py:335-338),
+ * y = x r with r = rsqrt(max(sum x^2, 1e-12)):  dx = r (g - y (y . g)) where sum x^2 > 1e-12, dx = 1e6 g where it is not.
+ *   x [pixels, ldx] the tower's output BEFORE the normalisation, g [pixels, ldg] = dL/dy, dx [pixels, ld_dx]; C = 32 only;
+ *   strides multiples of 4, buffers 16-byte aligned. */
+int kfn_l2norm_backward(const float* x, int ldx, const float* g, int ldg, float* dx, int ld_dx, long pixels, int C,
+                        void* stream);
+
+/* kfn_flow_loss_grad -- the loss of stage 2 and its gradients.  Pair p is frames a = 2p and b = 2p + 1 of `labels`.
+ *   flow_xy [P,h,w,2] = (u, v), sigma_trans [P,h,w]: OFlowNet's outputs for the pair, on frame b's grid
+ *   labels  [2P, h label_stride, w label_stride, 4] = (gt xyz, mask), read as kfn_coord_loss_grad reads them; m = (mask == 1);
+ *           no transform: the loss is invariant under a rigid one
+ *   (px, py) = (x + u, y + v);  x^- = tools.util.bilinear_sampler (tools/util.py:36-93: clamped corners, weights from the
+ *           clamped corners, add_n order) of label a's xyz at (px, py)
+ *   valid_a = 1 where the four unclamped corners (floor px, floor py) + {0,1}^2 lie in the grid and have m_a = 1
+ *   sigma^- = sqrt(eps2 + max(sigma_trans^2, eps2)), eps2 = float(min_uncertainty^2);  u = max(sigma^-, min_uncertainty)
+ *   M = m_b valid_a,  d = sum_c (x^-_c - g_b,c)^2,  l = 3 log u + d / (2 u^2),  l = min(l, loss_clip) when has_loss_clip
+ *   L = sum(M l) / (sum(M) + 1) over the whole batch
+ *   d_flow  [P,h,w,2] = dL/d(u, v) through the sampler's weights (corner indices and M piecewise constant)
+ *   d_sigma [P,h,w]   = M / (sum M + 1) (3/u - d/u^3) [sigma^- > min_uncertainty] [sigma_trans^2 > eps2] sigma_trans / sigma^-
+ *   stats[16] = (L, accuracy = (valid - #{M d > dist_threshold^2}) / valid, valid = sum M + 1, #{valid_a == 0}, 0 ...)
+ * One workgroup, any grid; per-cell terms in unfused fp32, sums in fp64 over a fixed tree. */
+typedef struct kfn_flow_loss_desc {
+  int32_t struct_size;      /* = sizeof(kfn_flow_loss_desc) */
+  int32_t P, h, w;
+  int32_t label_stride;
+  int32_t has_loss_clip;
+  float loss_clip;
+  int32_t reserved;         /* 0 */
+  double dist_threshold;    /* 0.05: compared as float(dist_threshold * dist_threshold), 0x3B23D70A */
+  double min_uncertainty;   /* 1e-5: the floor of u, and squared (rounded once) the floor of both variances */
+} kfn_flow_loss_desc;
+int kfn_flow_loss_grad(const kfn_flow_loss_desc* desc, const float* flow_xy, const float* sigma_trans, const float* labels,
+                       float* d_flow, float* d_sigma, float* stats, void* stream);
 
 #ifdef __cplusplus
 }

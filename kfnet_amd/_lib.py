@@ -113,6 +113,13 @@ class FilterBackwardDesc(SizedStructure):
                 [('min_uncertainty', C.c_double)])
 
 
+class FlowLossDesc(SizedStructure):
+    """kfn_flow_loss_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
+    _fields_ = [('struct_size', C.c_int32), ('P', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('label_stride', C.c_int32),
+                ('has_loss_clip', C.c_int32), ('loss_clip', C.c_float), ('reserved', C.c_int32),
+                ('dist_threshold', C.c_double), ('min_uncertainty', C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/kfnet_hip.h
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 SYMBOLS = {
@@ -211,6 +218,11 @@ SYMBOLS = {
     'kfn_filter_loss_grad': (_i, [C.POINTER(FilterLossDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'kfn_filter_backward_scratch_bytes': (_i, [C.POINTER(FilterBackwardDesc), C.POINTER(_sz)]),
     'kfn_filter_backward': (_i, [C.POINTER(FilterBackwardDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # training OFlowNet (added exports, ABI 13)
+    'kfn_cost_volume_backward': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'kfn_flow_head_backward': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, C.c_long, _vp]),
+    'kfn_l2norm_backward': (_i, [_vp, _i, _vp, _i, _vp, _i, C.c_long, _i, _vp]),
+    'kfn_flow_loss_grad': (_i, [C.POINTER(FlowLossDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

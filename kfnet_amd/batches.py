@@ -35,11 +35,12 @@ class SyntheticSource(object):
 class LabelFileSource(object):
     """image_list.txt, label_list.txt (one [H,W,4] float32 file per image) and transform.txt of an input folder."""
 
-    def __init__(self, input_folder, size):
+    def __init__(self, input_folder, size, needs_transform=True):
         self.paths, self.label_paths = modes.read_inputs(input_folder)
         if self.label_paths is None:
             raise ValueError('%s has no label_list.txt: training needs labels' % input_folder)
-        self.transform = np.loadtxt(os.path.join(input_folder, 'transform.txt'), dtype=np.float32)
+        # stage 2's loss is invariant under the rigid transform: OFlowNet.train neither needs nor reads the file
+        self.transform = np.loadtxt(os.path.join(input_folder, 'transform.txt'), dtype=np.float32) if needs_transform else None
         self.count, self.size = len(self.paths), size
 
     def label(self, i, full_resolution):
@@ -82,8 +83,9 @@ class DepthSource(object):
         return frames, self._labelers[full_resolution].labels(depth, self.poses[indices])
 
 
-def open_source(a, full_resolution):
-    """The source that the parsed arguments of SCoordNet.train ask for.  ValueError or OSError, with the message for the
+def open_source(a, full_resolution, needs_transform=True):
+    """The source that the parsed arguments of SCoordNet.train ask for (needs_transform = False: OFlowNet.train's, whose label
+    files go without transform.txt).  ValueError or OSError, with the message for the
     user, when the arguments or the folder do not make one; with `full_resolution` the first label file is read here, so
     that grid-sized label files are refused at once."""
     size = (a.height, a.width)
@@ -93,7 +95,7 @@ def open_source(a, full_resolution):
         return SyntheticSource(a.synthetic, size)
     if a.depth:
         return DepthSource(a.input_folder, size, a.batch, L.camera_of(a), 'cuda:%d' % a.gpu)
-    source = LabelFileSource(a.input_folder, size)
+    source = LabelFileSource(a.input_folder, size, needs_transform)
     if full_resolution:
         source.label(0, True)
     return source

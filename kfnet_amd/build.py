@@ -37,6 +37,8 @@ EXTRA = {
     'kfn_labels.hip': ['-ffp-contract=off'],
     # the filter's loss and reverse scan: the loss's per-pixel terms and the forward scan's sampler weights, rounded alike
     'kfn_train_filter.hip': ['-ffp-contract=off'],
+    # training OFlowNet: the loss's per-cell terms as the filter's, and gather sums that a sequential fp32 restatement repeats
+    'kfn_train_flow.hip': ['-ffp-contract=off'],
 }
 
 

@@ -417,16 +417,16 @@ class SCoordNetTrainer(object):
         return StepStats(stats, lr)
 
 
-def restore(model_folder, verbose=True):
-    """The newest snapshot of a model folder for resuming: (weights or None, state or None, step).  The snapshot may be a TF
-    checkpoint or a kfnet_weights*.npz, with or without a kfnet_train_state-<step>.npz beside it."""
+def restore(model_folder, verbose=True, scope=SCOPE):
+    """The newest snapshot of a model folder for resuming: (weights of `scope` or None, state or None, step).  The snapshot may
+    be a TF checkpoint or a kfnet_weights*.npz, with or without a kfnet_train_state-<step>.npz beside it."""
     from .tools.io import get_snapshot
     from .weights import load_snapshot
     snapshot, step = get_snapshot(model_folder) if model_folder and os.path.isdir(model_folder) else (None, 0)
     if snapshot is None:
         return None, None, 0
-    W = load_snapshot(snapshot, scopes=(SCOPE,), verbose=verbose)
-    W = {k: v for k, v in W.items() if k.startswith(SCOPE + '/')}
+    W = load_snapshot(snapshot, scopes=(scope,), verbose=verbose)
+    W = {k: v for k, v in W.items() if k.startswith(scope + '/')}
     sp = snapshot_paths(model_folder, step)[1]
     state = None
     if os.path.exists(sp):

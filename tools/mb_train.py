@@ -4,6 +4,7 @@ launch as fractions of the fp32 MFMA peak.
 
     python tools/mb_train.py [--height 480 --width 640 --batch 4 --steps 10 --warmup 3] [--layers] [--augment] [--depth]
     python tools/mb_train.py --kfnet [--groups 1]
+    python tools/mb_train.py --oflownet [--pairs 4]
 
 --augment times the step with the augmentation of DESIGN.md 6c on: full-resolution labels, the parameters of
 kfnet_amd.augment.draw(0, step) in turn (its kernels are channel_sums_kernel and augment_kernel in a kernel trace).
@@ -12,6 +13,10 @@ or stride 1 with --augment; depth_labels_grid_kernel / depth_labels_full_kernel 
 --kfnet times kfnet_amd.train_kfnet.KFNetTrainer instead: ms per step on --groups groups of four frames, and
 the launches it adds to stage 1's step -- the OFlowNet forward, the measurement map and the scan, the three-term loss, the
 reverse scan -- each alone and as a share of the step.
+--oflownet times kfnet_amd.train_flow.OFlowNetTrainer (stage 2): ms per step on --pairs pairs of frames, its
+forward, loss + backward, Adam and packs, and the launches stage 2 adds, each alone: the cost volume's transpose with the bytes
+that have to cross HBM (d_vol once, two feature maps) over its time as a share of 8 TB/s, the flow head's and the L2
+normalisation's backward, and the loss.
 
 Under `rocprofv3 --kernel-trace --stats -- python tools/mb_train.py --steps 5` the kernel table gives the same split per
 kernel name (wgrad_mfma_kernel, conv_mfma_kernel, ...)."""
@@ -77,6 +82,66 @@ def kfnet(a):
     return 0
 
 
+def oflownet(a):
+    import ctypes as C
+    import torch
+    from kfnet_amd import _lib
+    lib = _lib.load()
+    P, h, w, Cc = a.pairs, a.height // 8, a.width // 8, 32
+    N = P * h * w
+    stream = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator(device='cuda').manual_seed(0)
+
+    def rand(*shape):
+        return torch.randn(*shape, device='cuda', generator=g)
+    d_vol, d_f2, d_f1 = rand(N, 8, 8, Cc), torch.empty(N, Cc, device='cuda'), torch.empty(N, Cc, device='cuda')
+    d_flow, prob = rand(N, 2), torch.softmax(rand(N, 64), -1)
+    d_sigma, sigma = rand(N), 1e-2 * torch.exp(rand(N))
+    d_logits, d_pre = torch.empty(N * 64, 16, device='cuda'), torch.empty(N, 16, device='cuda')
+    x, gy, dx = rand(2 * N, Cc), rand(2 * N, Cc), torch.empty(2 * N, Cc, device='cuda')
+    labels = rand(2 * P, h, w, 4)
+    labels[..., 3] = (labels[..., 3] > -1.3).float()
+    flow, stats = 2.0 * torch.rand(N, 2, device='cuda', generator=g) - 1.0, torch.zeros(16, device='cuda')
+    desc = _lib.FlowLossDesc(P=P, h=h, w=w, label_stride=1, dist_threshold=0.05, min_uncertainty=1e-5)
+    launches = [
+        ('kfn_cost_volume_backward', lambda: lib.kfn_cost_volume_backward(d_vol.data_ptr(), d_f2.data_ptr(), d_f1.data_ptr(), P, h, w,
+                                                                          Cc, stream)),
+        ('kfn_flow_head_backward', lambda: lib.kfn_flow_head_backward(d_flow.data_ptr(), prob.data_ptr(), d_sigma.data_ptr(),
+                                                                      sigma.data_ptr(), d_logits.data_ptr(), 16, d_pre.data_ptr(), 16,
+                                                                      N, stream)),
+        ('kfn_l2norm_backward', lambda: lib.kfn_l2norm_backward(x.data_ptr(), Cc, gy.data_ptr(), Cc, dx.data_ptr(), Cc, 2 * N, Cc,
+                                                                stream)),
+        ('kfn_flow_loss_grad', lambda: lib.kfn_flow_loss_grad(C.byref(desc), flow.data_ptr(), sigma.data_ptr(), labels.data_ptr(),
+                                                              d_flow.data_ptr(), d_sigma.data_ptr(), stats.data_ptr(), stream)),
+    ]
+    print('%dx%d, %d pair(s): grid %dx%d, %d windows' % (a.height, a.width, P, h, w, N))
+    from kfnet_amd.synth import synthetic_sequence
+    from kfnet_amd.train import synthetic_labels
+    from kfnet_amd.train_flow import OFlowNetTrainer
+    from kfnet_amd.weights import synthetic_weights
+    tr = OFlowNetTrainer(synthetic_weights(1234), image_size=(a.height, a.width), pairs=P)
+    frames = torch.from_numpy(synthetic_sequence(2 * P, a.height, a.width)).cuda()
+    labs = torch.from_numpy(synthetic_labels(2 * P, tr.grid)).cuda()
+    for _ in range(a.warmup):
+        tr.step(frames, labs)
+    ms = timed(torch, lambda: tr.step(frames, labs), a.steps)
+    tr.stage(frames, labs)
+    parts = [('forward', tr.forward), ('loss + backward', lambda: (tr.loss(), tr.backward())),
+             ('adam', lambda: tr.apply_gradients()), ('packs', lambda: tr._repack(stream))]
+    print('%.2f ms per step (%.1f pairs/s), %.2f M parameters; %s' % (
+        ms, 1e3 * P / ms, tr.num_floats / 1e6, ', '.join('%s %.2f ms' % (n, timed(torch, f, a.steps)) for n, f in parts)))
+    for name, fn in launches:
+        _lib.check(fn(), name)
+        ms = timed(torch, fn, max(a.steps, 20))
+        line = '%-26s %8.3f ms' % (name, ms)
+        if name == 'kfn_cost_volume_backward':
+            need = 4.0 * (d_vol.numel() + 2 * N * Cc)
+            line += '   %.1f MB have to cross HBM: %.2f TB/s = %.1f%% of 8 TB/s (the launch reads d_vol twice)' % (
+                need / 1e6, need / (ms * 1e-3) / 1e12, 100 * need / (ms * 1e-3) / 8e12)
+        print(line)
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--height', type=int, default=480)
@@ -89,9 +154,13 @@ def main(argv=None):
     ap.add_argument('--depth', action='store_true', help='make the labels of every step from depth maps and poses')
     ap.add_argument('--kfnet', action='store_true', help='time the step of KFNetTrainer (SCoordNet through the filter)')
     ap.add_argument('--groups', type=int, default=1, help='--kfnet: groups of four frames per step')
+    ap.add_argument('--oflownet', action='store_true', help='time the step of OFlowNetTrainer (stage 2) and the launches it adds')
+    ap.add_argument('--pairs', type=int, default=4, help='--oflownet: pairs of frames per step')
     a = ap.parse_args(argv)
     if a.kfnet:
         return kfnet(a)
+    if a.oflownet:
+        return oflownet(a)
     import torch
     from kfnet_amd import _lib
     from kfnet_amd.synth import synthetic_sequence, synthetic_transform
