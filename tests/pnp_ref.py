@@ -323,3 +323,77 @@ def synthetic_records(rng, h, w, R, t, fx=525.0, fy=525.0, u=320.0, v=240.0, cel
     rec[..., :3] = Xw
     rec[..., 3] = confidence
     return rec
+
+
+# ---- helpers of tests/test_gpu_pnp_stages.py: one stage of the device at a time against fp64 ----------------------------
+
+def synthetic_frames(seed, B, h, w, outliers=0.0, noise=0.0, fx=525.0, fy=525.0, u=320.0, v=240.0, cell_stride=8):
+    """(records [B,h,w,4] float32, camera-to-world ground truth [B,4,4]): random poses, Gaussian `noise` (m) on every
+    scene coordinate, a share `outliers` of the cells replaced by points uniform in +-5 m."""
+    rng = np.random.default_rng(seed)
+    recs, gts = [], []
+    for _ in range(B):
+        R, t = random_pose(rng)
+        rec = synthetic_records(rng, h, w, R, t, fx, fy, u, v, cell_stride)
+        if noise:
+            rec[..., :3] += rng.normal(scale=noise, size=rec[..., :3].shape).astype(np.float32)
+        out = rng.random((h, w)) < outliers
+        rec[..., :3][out] = rng.uniform(-5, 5, size=(int(out.sum()), 3)).astype(np.float32)
+        recs.append(rec)
+        gts.append(cam_to_world(R, t))
+    return np.stack(recs), np.stack(gts)
+
+
+def first_max(counts):
+    """The selection rule: index of the first maximum of the counts, -1 if no hypothesis is valid."""
+    k = int(np.argmax(counts))
+    return k if counts[k] >= 0 else -1
+
+
+def widen(hyp):
+    """A device hypothesis [12] = [R | t] in fp32 -> (R, t) in fp64, as pnp_refine_kernel reads it."""
+    M = np.asarray(hyp, np.float32).astype(np.float64).reshape(3, 4)
+    return M[:, :3].copy(), M[:, 3].copy()
+
+
+def threshold_margin(R, t, X, pix, fx, fy, u, v, thr):
+    """Smallest relative distance |err / thr - 1| of a candidate in front of the camera from the inlier threshold."""
+    e2, Z = project_error2(R, t, X, pix, fx, fy, u, v)
+    front = Z > 0.0
+    if not front.any():
+        return np.inf
+    return float(np.abs(np.sqrt(e2[front]) / thr - 1.0).min())
+
+
+def score_brackets(hyps, X, pix, fx, fy, u, v, thr, delta=1e-3, zmin=1e-3, chunk=64):
+    """hyps [H,12] fp32 -> (lo [H], hi [H]): lo counts the candidates that are inliers of the widened pose beyond doubt,
+    hi adds the undecided ones (|Zc| < zmin, or a pixel error within a relative delta of thr)."""
+    hyps = np.asarray(hyps, np.float32).astype(np.float64).reshape(-1, 3, 4)
+    H = hyps.shape[0]
+    lo = np.zeros(H, np.int64)
+    hi = np.zeros(H, np.int64)
+    dx, dy = pix[:, 0] - u, pix[:, 1] - v
+    for k0 in range(0, H, chunk):
+        M = hyps[k0:k0 + chunk]
+        Xc = np.einsum('hrc,nc->hnr', M[:, :, :3], X) + M[:, None, :, 3]
+        Z = Xc[..., 2]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            err = np.sqrt((fx * Xc[..., 0] / Z - dx) ** 2 + (fy * Xc[..., 1] / Z - dy) ** 2)
+        undecided = (np.abs(Z) < zmin) | (np.abs(err - thr) <= delta * thr)
+        inl = (Z > 0.0) & (err < thr) & ~undecided
+        lo[k0:k0 + chunk] = inl.sum(1)
+        hi[k0:k0 + chunk] = inl.sum(1) + undecided.sum(1)
+    return lo, hi
+
+
+def refine_permutation_spread(R, t, X, pix, fx, fy, u, v, thr, iters, perms=5, seed=0):
+    """d_perm: the largest change of an entry of cam_to_world(refine(...)) when the candidates are listed in another
+    order (other summation order; at convergence possibly another last accept/reject decision)."""
+    base = cam_to_world(*refine(R, t, X, pix, fx, fy, u, v, thr, iters))
+    rng = np.random.default_rng(seed)
+    d = 0.0
+    for _ in range(perms):
+        p = rng.permutation(X.shape[0])
+        T = cam_to_world(*refine(R, t, X[p], pix[p], fx, fy, u, v, thr, iters))
+        d = max(d, float(np.abs(T - base).max()))
+    return d
