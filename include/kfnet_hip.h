@@ -53,7 +53,8 @@ extern "C" {
  * batch), added exports that leave every ABI-13 host working, so the number stays; likewise kfn_decode_png_gray16,
  * kfn_depth_labels and kfn_label_moments (training labels from depth maps and poses), and kfn_measurement_map,
  * kfn_filter_loss_grad, kfn_filter_backward_scratch_bytes and kfn_filter_backward (fine-tuning SCoordNet through the filter),
- * and kfn_cost_volume_backward, kfn_flow_head_backward, kfn_l2norm_backward and kfn_flow_loss_grad (training OFlowNet). */
+ * and kfn_cost_volume_backward, kfn_flow_head_backward, kfn_l2norm_backward and kfn_flow_loss_grad (training OFlowNet),
+ * and kfn_filter_backward_joint (joint stage 3: both networks trained through the filter). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -875,6 +876,26 @@ int kfn_filter_backward_scratch_bytes(const kfn_filter_backward_desc* desc, size
 int kfn_filter_backward(const kfn_filter_backward_desc* desc, const float* flow_xy, const float* meas, const float* temp,
                         const float* kf, const float* d_temp, float* d_kf, float* dpred, float* stats, void* scratch,
                         void* stream);
+
+/* kfn_filter_backward_joint -- kfn_filter_backward for joint stage 3, where OFlowNet is trained too (KFNet/train.py:282-303):
+ * the same descriptor, scratch size and launches, and on dpred, d_kf and stats word 11 the same bits.  Beside them it emits the
+ * gradients with respect to the process model's two inputs (KFNet/KFNet.py:361-403 with tools/util.py:36-94), per frame
+ * t >= 1 and cell q, from values the reverse scan holds already:
+ *   av     [4]  the gradient with respect to the value (x^-, s_l) sampled from KF_{t-1} (s_l's is 0 where s_l^2 <= eps2)
+ *   v_xy   [4]  KF_{t-1} at the forward's clamped corner (x = 0|1, y = 0|1); w_x0 = x1s - px, w_x1 = px - x0s, likewise in y
+ *   d_flow[q] = (dL/du, dL/dv):  the weights' derivatives by px are -1 and +1, corner indices, floor and the clamps are
+ *               piecewise constant (tools/util.py:36-59), so
+ *               dL/du = sum_c av_c (w_y0 (v10_c - v00_c) + w_y1 (v11_c - v01_c))
+ *               dL/dv = sum_c av_c (w_x0 (v01_c - v00_c) + w_x1 (v11_c - v10_c))
+ *               two corners that clamp to one cell give 0 by themselves
+ *   d_sigma_trans[q] = [sigma_trans^2 > eps2] d_lvar 2 sigma_trans, d_lvar the gradient with respect to sigma^-^2 and
+ *               eps2 = float(min_uncertainty^2), the floor of kfn_kalman_scan_ex
+ * Frame 0 of every group receives zeros in both.  ORDER: unfused fp32; inside the brackets the w_.0 product first; the sum over
+ * c runs c = 0, 1, 2, 3 (x, y, z, sigma), ((t0 + t1) + t2) + t3.  No floating-point atomics: two launches give the same bits.
+ *   sigma_trans [S,T,HW] in;  d_flow [S,T,HW,2] out, 8-byte aligned;  d_sigma_trans [S,T,HW] out;  the rest as above */
+int kfn_filter_backward_joint(const kfn_filter_backward_desc* desc, const float* flow_xy, const float* sigma_trans,
+                              const float* meas, const float* temp, const float* kf, const float* d_temp, float* d_kf,
+                              float* dpred, float* d_flow, float* d_sigma_trans, float* stats, void* scratch, void* stream);
 
 /* ---- training OFlowNet: stage 2 of the reference's procedure (added exports; the ABI number stays 13) -------------------
  * The backward pass of the Temporal scope (cnn_wrapper/OFlowNet.py:17-57, KFNet/KFNet.py:315-403) outside its convolutions,

@@ -1,12 +1,15 @@
-"""Stage 3 of the reference README's "Training" with OFlowNet frozen: fine-tune SCoordNet through the Kalman filter.
+"""Stage 3 of the reference README's "Training": fine-tune SCoordNet through the Kalman filter with OFlowNet frozen
+(--fix_flownet), or train both networks through it (--joint).
 
     python -m kfnet_amd.KFNet.train --input_folder I --model_folder M --scene S --fix_flownet --scoordnet A --oflownet B
+    python -m kfnet_amd.KFNet.train --input_folder I --model_folder M --scene S --joint --scoordnet A --oflownet B
 
 I is the folder of `python -m kfnet_amd.SCoordNet.train` (image_list.txt, label_list.txt, transform.txt; or, with --depth,
 depth_list.txt and pose_list.txt).  A step trains --groups groups of four consecutive frames, forward or reversed
 (get_indexes, KFNet/train.py:60-147), on 0.2 L_measure + 0.2 L_temporal + 0.6 L_KF (:293-295); the gradients reach ScoreNet/*
-through the Kalman update, the variance chain and the warp of the previous estimate.  Temporal/* is used as it
-is restored and written back unchanged.
+through the Kalman update, the variance chain and the warp of the previous estimate.  With --fix_flownet
+Temporal/* is used as it is restored and written back unchanged; with --joint the same loss reaches Temporal/* through the
+flow and the process noise, and both scopes are trained and regularised with one schedule.
 
 Restoring follows KFNet/train.py:398-408: first the newest snapshot of M (all scopes, with its Adam slots), then ScoreNet/*
 from the newest snapshot of --scoordnet, then Temporal/* from that of --oflownet; a scope that nothing restores starts from an
@@ -14,8 +17,9 @@ untrained graph's values.  With both --scoordnet and --oflownet the step starts 
 Snapshots go to M as kfnet_weights-<step>.npz (both scopes: `python -m kfnet_amd.KFNet.eval --model_folder M` reads it as it
 is) and kfnet_train_state-<step>.npz.
 
-The flags are the reference's (KFNet/train.py:14-47) and stage 1's.  Without --fix_flownet the program stops: training
-OFlowNet is not built.  --augment is refused: the reference's stage 3 has none.  --loss_clip is off by default, as in stage 1.
+The flags are the reference's (KFNet/train.py:14-47) and stage 1's, and --joint.  A stated deviation: the reference trains
+both networks unless told --fix_flownet; here the plain command line stops and asks for one of the two flags.  --augment is
+refused: the reference's stage 3 has none.  --loss_clip is off by default, as in stage 1.
 """
 import argparse
 import sys
@@ -40,7 +44,8 @@ def build_parser():
     ap.description = __doc__
     ap.add_argument('--scoordnet', default='', help='model folder whose newest snapshot gives ScoreNet/*')
     ap.add_argument('--oflownet', default='', help='model folder whose newest snapshot gives Temporal/*')
-    ap.add_argument('--fix_flownet', action='store_true', help='keep OFlowNet as restored (required)')
+    ap.add_argument('--fix_flownet', action='store_true', help='keep OFlowNet as restored (this or --joint is required)')
+    ap.add_argument('--joint', action='store_true', help='train OFlowNet too: the joint stage 3 of the reference')
     ap.add_argument('--groups', type=int, default=1, help='groups of four frames per step')
     ap.add_argument('--sequence_length', type=int, default=None, help='frames per range of get_indexes (500 for stairs, else 1000)')
     return ap
@@ -51,8 +56,12 @@ def main(argv=None):
     if a.scene not in modes.SCENES:
         print('Invalid scene:', a.scene)
         return 1
-    if not a.fix_flownet:
-        print('training OFlowNet is not built: run with --fix_flownet (OFlowNet stays as restored)', file=sys.stderr)
+    if a.joint and a.fix_flownet:
+        print('--joint trains OFlowNet and --fix_flownet keeps it as restored: pass one of them', file=sys.stderr)
+        return 1
+    if not a.fix_flownet and not a.joint:
+        print('training OFlowNet is not built into the plain command line: pass --joint to train both networks, or '
+              '--fix_flownet to keep OFlowNet as restored', file=sys.stderr)
         return 1
     if a.augment:
         print('--augment is refused: stage 3 of the reference trains without augmentation', file=sys.stderr)
@@ -96,7 +105,7 @@ def main(argv=None):
     torch.cuda.set_device(a.gpu)
     tr = KFNetTrainer(W, image_size=(a.height, a.width), groups=a.groups, transform=source.transform, base_lr=a.base_lr,
                       gamma=a.gamma, stepvalue=stepvalue, weight_decay=a.weight_decay, loss_clip=a.loss_clip,
-                      smooth_weight=a.smooth_weight, device='cuda:%d' % a.gpu)
+                      smooth_weight=a.smooth_weight, device='cuda:%d' % a.gpu, train_flownet=a.joint)
     if state is not None:
         tr.load_state(state)
     tr.global_step = start_step(step, stepvalue, a.reset_step, a.scoordnet, a.oflownet)

@@ -223,6 +223,8 @@ SYMBOLS = {
     'kfn_flow_head_backward': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, C.c_long, _vp]),
     'kfn_l2norm_backward': (_i, [_vp, _i, _vp, _i, _vp, _i, C.c_long, _i, _vp]),
     'kfn_flow_loss_grad': (_i, [C.POINTER(FlowLossDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # joint stage 3: both networks through the Kalman filter (added export, ABI 13)
+    'kfn_filter_backward_joint': (_i, [C.POINTER(FilterBackwardDesc)] + [_vp] * 13),
 }
 
 _lib = None

@@ -7,8 +7,12 @@
 //                         + 50 SmoothLoss (:430-467), with the gradients with respect to the three outputs
 //   kfn_filter_backward   the reverse scan t = T-1 .. 0: BuildKFCoord (:148-162), the variance chain (:393-401) and the
 //                         transpose of tools.util.bilinear_sampler (tools/util.py:36-93) as a gather in a fixed order
+//   kfn_filter_backward_joint  the same scan for joint stage 3 (OFlowNet trained too, KFNet/train.py:282-303): beside the above
+//                         the gradients with respect to the flow (through the sampler's weights) and to sigma_trans
 // The forward filter itself is kfn_kalman_scan_ex (kfn_kalman.hip): training and eval run the same launch.
 #include "kfn_common.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -209,6 +213,13 @@ struct BackArgs {
   float eps2;
 };
 
+// What kfn_filter_backward_joint adds: the process noise it differentiates by, and its two outputs.
+struct JointBackArgs : BackArgs {
+  const float* sigma_trans;   // [S,T,hw]
+  f32x2* d_flow;              // [S,T,hw] out
+  float* d_sigma_trans;       // [S,T,hw] out
+};
+
 // The clamped corners and their weights of the target cell (x, y), exactly fuse_pixel's arithmetic (kfn_kalman.hip).
 struct Taps {
   int ix0, ix1, iy0, iy1;
@@ -235,7 +246,10 @@ __device__ __forceinline__ Taps taps_of(int x, int y, f32x2 flow, float xmax, fl
 //   fuse     (t >= 1) d_temp[t], d_kf[t] -> the measurement's gradient (into dpred) and the gradient with respect to the
 //            value sampled from KF_{t-1} (a_out, which the next launch gathers)
 //   t == 0   d_temp[0] + d_kf[0] fall on the measurement
-__global__ __launch_bounds__(BT) void filter_backward_kernel(BackArgs a) {
+// JOINT (kfn_filter_backward_joint) adds, per cell of a frame t >= 1, the gradients with respect to the flow and to sigma_trans
+// from values the fuse step holds already; frame 0 writes zeros to both.  The other instantiation is kfn_filter_backward's.
+template <bool JOINT>
+__global__ __launch_bounds__(BT) void filter_backward_kernel(std::conditional_t<JOINT, JointBackArgs, BackArgs> a) {
   const int HW = a.H * a.W;
   const int q = blockIdx.x * BT + threadIdx.x;
   const int s = blockIdx.y;
@@ -277,6 +291,11 @@ __global__ __launch_bounds__(BT) void filter_backward_kernel(BackArgs a) {
   if (t == 0) {   // KFNet/KFNet.py:122-126: both estimates of frame 1 ARE the measurement
     const f32x4 gz = G + Gt;
     dp[0] += gz.x; dp[1] += gz.y; dp[2] += gz.z; dp[3] += gz.w * z.w;
+    if constexpr (JOINT) {   // no pair ends on a group's first frame
+      const f32x2 none = {0.f, 0.f};
+      a.d_flow[off + q] = none;
+      a.d_sigma_trans[off + q] = 0.0f;
+    }
     return;
   }
   const f32x2 fl = a.flow[off + q];
@@ -311,6 +330,22 @@ __global__ __launch_bounds__(BT) void filter_backward_kernel(BackArgs a) {
   av.x = G.x * om + Gt.x; av.y = G.y * om + Gt.y; av.z = G.z * om + Gt.z;
   av.w = s_l * s_l > a.eps2 ? d_lvar * (2.0f * s_l) : 0.0f;     // below the floor the maximum passes nothing
   a.a_out[(size_t)s * HW + q] = av;
+  if constexpr (JOINT) {
+    // The sampler's weights are wx0 = x1s - px, wx1 = px - x0s (and likewise in y): their derivatives by (u, v) are -1 and +1,
+    // the corner indices are piecewise constant (tools/util.py:36-59).  v_xy = corner (ix_x, iy_y) of KF_{t-1}.  Two corners
+    // clamped to one cell hold the same value, so their difference is 0 by itself.  ORDER: channels 0..3 ascending.
+    const f32x4 v00 = prev[k.iy0 * a.W + k.ix0], v01 = prev[k.iy1 * a.W + k.ix0];
+    const f32x4 v10 = prev[k.iy0 * a.W + k.ix1], v11 = prev[k.iy1 * a.W + k.ix1];
+    const f32x4 gu = k.wy0 * (v10 - v00) + k.wy1 * (v11 - v01);
+    const f32x4 gv = k.wx0 * (v01 - v00) + k.wx1 * (v11 - v10);
+    f32x2 df;
+    df.x = ((av.x * gu.x + av.y * gu.y) + av.z * gu.z) + av.w * gu.w;
+    df.y = ((av.x * gv.x + av.y * gv.y) + av.z * gv.z) + av.w * gv.w;
+    a.d_flow[off + q] = df;
+    // sigma^-^2 = max(s_l^2, eps^2) + max(sigma_trans^2, eps^2): the second maximum passes nothing below the floor
+    const float st = a.sigma_trans[off + q];
+    a.d_sigma_trans[off + q] = st * st > a.eps2 ? d_lvar * (2.0f * st) : 0.0f;
+  }
 }
 
 }  // namespace
@@ -398,8 +433,55 @@ extern "C" int kfn_filter_backward(const kfn_filter_backward_desc* d, const floa
     a.t = t;
     a.a_out = buf[t & 1];
     a.a_in = buf[(t + 1) & 1];
-    hipLaunchKernelGGL(filter_backward_kernel, grid, dim3(BT), 0, s, a);
+    hipLaunchKernelGGL(filter_backward_kernel<false>, grid, dim3(BT), 0, s, a);
     KFN_LAUNCH_CHECK("filter_backward_kernel");
+  }
+  return KFN_OK;
+}
+
+extern "C" int kfn_filter_backward_joint(const kfn_filter_backward_desc* d, const float* flow_xy, const float* sigma_trans,
+                                         const float* meas, const float* temp, const float* kf, const float* d_temp, float* d_kf,
+                                         float* dpred, float* d_flow, float* d_sigma_trans, float* stats, void* scratch,
+                                         void* stream) {
+  KFN_REQUIRE(d && flow_xy && sigma_trans && meas && temp && kf && d_temp && d_kf && dpred && d_flow && d_sigma_trans && stats &&
+              scratch, "kfn_filter_backward_joint: null argument");
+  KFN_REQUIRE(d->struct_size == (int32_t)sizeof(kfn_filter_backward_desc), "kfn_filter_backward_joint: struct_size %d, expected %d",
+              (int)d->struct_size, (int)sizeof(kfn_filter_backward_desc));
+  KFN_REQUIRE(d->S > 0 && d->S < 65536 && d->T > 0 && d->H > 1 && d->W > 1 && (long)d->S * d->T * d->H * d->W < (1L << 27),
+              "kfn_filter_backward_joint: bad shape S=%d T=%d H=%d W=%d", d->S, d->T, d->H, d->W);
+  KFN_REQUIRE(d->radius >= 4 && d->radius <= 64, "kfn_filter_backward_joint: radius %d outside 4..64", d->radius);
+  KFN_REQUIRE(d->ld_dpred >= 4 && d->min_uncertainty > 0.0, "kfn_filter_backward_joint: bad ld_dpred %d or min_uncertainty",
+              d->ld_dpred);
+  KFN_REQUIRE((((reinterpret_cast<uintptr_t>(flow_xy) | reinterpret_cast<uintptr_t>(d_flow)) & 7) |
+               ((reinterpret_cast<uintptr_t>(sigma_trans) | reinterpret_cast<uintptr_t>(d_sigma_trans)) & 3) |
+               ((reinterpret_cast<uintptr_t>(meas) | reinterpret_cast<uintptr_t>(temp) | reinterpret_cast<uintptr_t>(kf) |
+                 reinterpret_cast<uintptr_t>(d_temp) | reinterpret_cast<uintptr_t>(d_kf) | reinterpret_cast<uintptr_t>(scratch)) & 15)) == 0,
+              "kfn_filter_backward_joint: misaligned buffer");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int HW = d->H * d->W;
+  JointBackArgs a;
+  a.flow = reinterpret_cast<const f32x2*>(flow_xy);
+  a.meas = reinterpret_cast<const f32x4*>(meas);
+  a.temp = reinterpret_cast<const f32x4*>(temp);
+  a.kf = reinterpret_cast<const f32x4*>(kf);
+  a.d_temp = reinterpret_cast<const f32x4*>(d_temp);
+  a.d_kf = reinterpret_cast<f32x4*>(d_kf);
+  a.dpred = dpred;
+  a.exceed = reinterpret_cast<unsigned*>(stats + 11);
+  a.S = d->S; a.T = d->T; a.H = d->H; a.W = d->W; a.ld_dpred = d->ld_dpred; a.radius = d->radius;
+  a.eps2 = (float)(d->min_uncertainty * d->min_uncertainty);
+  a.sigma_trans = sigma_trans;
+  a.d_flow = reinterpret_cast<f32x2*>(d_flow);
+  a.d_sigma_trans = d_sigma_trans;
+  f32x4* buf[2] = {reinterpret_cast<f32x4*>(scratch), reinterpret_cast<f32x4*>(scratch) + (size_t)d->S * HW};
+  KFN_HIP(hipMemsetAsync(a.exceed, 0, sizeof(unsigned), s));
+  const dim3 grid((unsigned)((HW + BT - 1) / BT), (unsigned)d->S);
+  for (int t = d->T - 1; t >= 0; --t) {   // the launches of kfn_filter_backward, frame for frame
+    a.t = t;
+    a.a_out = buf[t & 1];
+    a.a_in = buf[(t + 1) & 1];
+    hipLaunchKernelGGL(filter_backward_kernel<true>, grid, dim3(BT), 0, s, a);
+    KFN_LAUNCH_CHECK("filter_backward_kernel<joint>");
   }
   return KFN_OK;
 }

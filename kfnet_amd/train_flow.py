@@ -18,6 +18,10 @@ A transposed layer y = deconv(x, w[k,k,Cout,Cin]) is the input gradient of the s
 gradient is V itself (KFN_PACK_FORWARD), and its weight gradient is V's, with the layer's output gradient as input and the
 layer's input as dZ.  Its bias gradient, the pixel sum of the output gradient, is the bias row of a 1x1 weight-gradient launch.
 
+With `frames` and `pair_index` the pairs share frames (joint stage 3, DESIGN.md 6g: a group of T frames holds T - 1 overlapping
+pairs): the tower runs once per frame, f_a and f_b are gathers of its normalised output, and the backward pass writes d_fb to
+the rows of the b frames and adds d_fa at the rows of the a frames.
+
 There is no fallback: a missing entry point or an unsupported shape raises.
 """
 import ctypes as C
@@ -38,6 +42,20 @@ WINDOW = 8
 
 def _pad16(c):
     return -(-c // 16) * 16
+
+
+def check_pair_index(pair_index, pairs, frames):
+    """(a_idx, b_idx) as int64 arrays of length `pairs`: frame numbers below `frames`, no number twice within a list -- so the
+    scatter of the backward pass meets every row of d_feat at most once per list and repeats bit for bit."""
+    a, b = (np.asarray(x, dtype=np.int64).reshape(-1) for x in pair_index)
+    for name, idx in (('a', a), ('b', b)):
+        if len(idx) != pairs:
+            raise ValueError('pair_index: %d %s frames for %d pairs' % (len(idx), name, pairs))
+        if idx.min() < 0 or idx.max() >= frames:
+            raise ValueError('pair_index: an %s frame outside 0..%d' % (name, frames - 1))
+        if len(np.unique(idx)) != len(idx):
+            raise ValueError('pair_index: an %s frame is listed twice' % name)
+    return a, b
 
 
 class View(object):
@@ -86,9 +104,11 @@ class StepStats(object):
 
 class OFlowNetTrainer(object):
     def __init__(self, weights, image_size=(480, 640), pairs=4, base_lr=1e-4, gamma=0.5, stepvalue=100000, weight_decay=1e-4,
-                 loss_clip=None, device='cuda:0'):
+                 loss_clip=None, device='cuda:0', frames=None, pair_index=None):
         """weights: {TF name: array} holding at least Temporal/*.  pairs = P: a batch is 2P frames, pair p = frames (2p, 2p + 1).
-        loss_clip: None (no clip) or a float."""
+        loss_clip: None (no clip) or a float.  frames = B with pair_index = (a_idx, b_idx): a batch is B frames instead and
+        pair p = frames (a_idx[p], b_idx[p]), each list without repeats; the gradients then come from the caller
+        (backward(d_flow, d_sigma)), the loss of stage 2 knows the default layout only."""
         import torch
         H, Wd = image_size
         staging.check_size(H, Wd, 'the height and width of a training batch')
@@ -101,6 +121,10 @@ class OFlowNetTrainer(object):
         self.loss_clip = None if loss_clip is None else float(loss_clip)
         self.global_step = self.adam_t = 0
         P, (h, w) = self.pairs, self.grid
+        if (frames is None) != (pair_index is None):
+            raise ValueError('frames and pair_index go together')
+        self.nframes = F = 2 * P if frames is None else int(frames)
+        self.pair_index = None if pair_index is None else check_pair_index(pair_index, P, F)
         self.windows = N = P * h * w
 
         specs = {n.split('/', 1)[1]: (kind, shape) for n, kind, shape in variable_specs() if n.startswith(SCOPE + '/')}
@@ -118,14 +142,16 @@ class OFlowNetTrainer(object):
             self.params, self.grads = torch.zeros(off, **f32), torch.zeros(off, **f32)
             self.m, self.v = torch.zeros(off, **f32), torch.zeros(off, **f32)
             self._fill(self.params, weights)
-            self.frames = torch.zeros((2 * P, H, Wd, 3), dtype=torch.uint8, device=self.device)
+            self.frames = torch.zeros((F, H, Wd, 3), dtype=torch.uint8, device=self.device)
+            if self.pair_index is not None:
+                self.a_idx, self.b_idx = (torch.from_numpy(x).to(self.device) for x in self.pair_index)
             self.labels = None
             self.label_stride = 1
 
             def buf(rows, ld):
                 return torch.zeros((rows, ld), **f32)
 
-            # ---- the tower on 2P frames: every output kept, feat7 both plain and normalised
+            # ---- the tower on the F frames (2P unless the pairs share them): every output kept, feat7 both plain and normalised
             self.layers = []
             hh, ww, ci = H, Wd, 3
             prev = None
@@ -134,16 +160,16 @@ class OFlowNetTrainer(object):
                 hh, ww = -(-hh // s), -(-ww // s)
                 L = Layer(name, 'conv', 3, ci, co, s, relu)
                 L.x = prev
-                L.y = View(buf(2 * P * hh * ww, co), 0, co, 2 * P, hh, ww)
-                L.dy = View(buf(2 * P * hh * ww, _pad16(co)), 0, co, 2 * P, hh, ww)
+                L.y = View(buf(F * hh * ww, co), 0, co, F, hh, ww)
+                L.dy = View(buf(F * hh * ww, _pad16(co)), 0, co, F, hh, ww)
                 L.dx = None if prev is None else self.layers[-1].dy
                 self.layers.append(L)
                 prev, ci = L.y, co
             self.tower = list(self.layers)
             assert (hh, ww) == (h, w) and ci == 32
-            self.feat = buf(2 * P * h * w, 32)                       # l2_normalize(feat7), all frames
+            self.feat = buf(F * h * w, 32)                           # l2_normalize(feat7), all frames
             self.f_a, self.f_b = buf(N, 32), buf(N, 32)
-            self.d_feat = buf(2 * P * h * w, 32)
+            self.d_feat = buf(F * h * w, 32)
             self.d_fa, self.d_fb = buf(N, 32), buf(N, 32)
             self.vol = View(buf(N * 64, 32), 0, 32, N, WINDOW, WINDOW)
             self.d_vol = View(buf(N * 64, 32), 0, 32, N, WINDOW, WINDOW)
@@ -208,7 +234,7 @@ class OFlowNetTrainer(object):
             self.d_flow, self.d_sigma = buf(N, 2), buf(N, 1)
             self.stats = torch.zeros(16, **f32)
 
-            ws_bytes = self._size(self.lib.kfn_first_conv_u8_grad_weights_workspace_bytes, 2 * P, H, Wd, self.tower[0].co)
+            ws_bytes = self._size(self.lib.kfn_first_conv_u8_grad_weights_workspace_bytes, F, H, Wd, self.tower[0].co)
             for L in self.layers[1:]:
                 k, ci, co = L.k, L.ci, L.co
                 if L.kind == 'deconv':                              # the stride-2 convolution V: Cout -> Cin
@@ -302,11 +328,20 @@ class OFlowNetTrainer(object):
                            'kfn_pack_conv_weights[%s]' % L.name)
         self._packs_stale = False
 
-    def stage(self, frames_u8, labels):
-        """Brings 2P frames (uint8 [2P,H,W,3]) and their labels (float32 [2P,H,W,4] or grid-sized) to the device."""
+    def stage(self, frames_u8, labels=None):
+        """Brings the batch's frames (uint8 [2P,H,W,3]; [B,H,W,3] with `frames` = B) and their labels (float32 [2P,H,W,4] or
+        grid-sized) to the device.  With `pair_index` the labels may be None (the caller owns the loss), and a uint8 tensor
+        of the batch's shape that lies on the device already is read where it is: stage 3 stages its frames once."""
         torch = self.torch
-        B, (H, Wd), (h, w) = 2 * self.pairs, self.image_size, self.grid
-        staging.stage(self.frames, frames_u8, torch.uint8, (B, H, Wd, 3), 'frames')
+        B, (H, Wd), (h, w) = self.nframes, self.image_size, self.grid
+        if self.pair_index is not None and torch.is_tensor(frames_u8) and frames_u8.device == self.device:
+            if tuple(frames_u8.shape) != (B, H, Wd, 3) or frames_u8.dtype != torch.uint8 or not frames_u8.is_contiguous():
+                raise ValueError('frames on the device must be contiguous uint8 %s' % [B, H, Wd, 3])
+            self.frames = frames_u8
+        else:
+            staging.stage(self.frames, frames_u8, torch.uint8, (B, H, Wd, 3), 'frames')
+        if labels is None and self.pair_index is not None:
+            return None
         lb = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.float32))
         if tuple(lb.shape) not in ((B, H, Wd, 4), (B, h, w, 4)):
             raise ValueError('labels must be float32 [%d,%d,%d,4] or grid-sized [%d,%d,%d,4], got %s'
@@ -336,18 +371,23 @@ class OFlowNetTrainer(object):
         stream = staging.current_stream(self.device) if stream is None else stream
         if self._packs_stale:
             self._repack(stream)
-        P, (H, Wd), (h, w), N = self.pairs, self.image_size, self.grid, self.windows
+        P, F, (H, Wd), (h, w), N = self.pairs, self.nframes, self.image_size, self.grid, self.windows
         first = self.tower[0]
-        _lib.check(self.lib.kfn_first_conv_u8(self.frames.data_ptr(), 2 * P, H, Wd, self._ptr(self.params, first, 'kernel'),
+        _lib.check(self.lib.kfn_first_conv_u8(self.frames.data_ptr(), F, H, Wd, self._ptr(self.params, first, 'kernel'),
                                               self._ptr(self.params, first, 'bias'), first.y.ptr, first.co, None, None, None, 0,
                                               stream), 'kfn_first_conv_u8')
         for L in self.tower[1:]:
             self._forward_layer(L, stream)
         last = self.tower[-1]
-        self._forward_layer(last, stream, y=View(self.feat, 0, 32, 2 * P, h, w), epilogue=_lib.EPI_L2NORM)
-        f = self.feat.view(P, 2, h * w, 32)
-        self.f_a.view(P, h * w, 32).copy_(f[:, 0])
-        self.f_b.view(P, h * w, 32).copy_(f[:, 1])
+        self._forward_layer(last, stream, y=View(self.feat, 0, 32, F, h, w), epilogue=_lib.EPI_L2NORM)
+        if self.pair_index is None:
+            f = self.feat.view(P, 2, h * w, 32)
+            self.f_a.view(P, h * w, 32).copy_(f[:, 0])
+            self.f_b.view(P, h * w, 32).copy_(f[:, 1])
+        else:
+            f = self.feat.view(F, h * w, 32)
+            self.torch.index_select(f, 0, self.a_idx, out=self.f_a.view(P, h * w, 32))
+            self.torch.index_select(f, 0, self.b_idx, out=self.f_b.view(P, h * w, 32))
         _lib.check(self.lib.kfn_cost_volume(self.f_a.data_ptr(), self.f_b.data_ptr(), self.vol.ptr, P, h, w, 32, WINDOW, stream),
                    'kfn_cost_volume')
         for L in self.unet + self.fc:
@@ -359,6 +399,8 @@ class OFlowNetTrainer(object):
         """The loss launch: self.stats, self.d_flow and self.d_sigma."""
         stream = staging.current_stream(self.device) if stream is None else stream
         P, (h, w) = self.pairs, self.grid
+        if self.pair_index is not None:
+            raise ValueError('the loss of stage 2 reads pairs of frames (2p, 2p + 1): with pair_index the gradients are the caller\'s')
         d = _lib.FlowLossDesc(P=P, h=h, w=w, label_stride=self.label_stride, has_loss_clip=int(self.loss_clip is not None),
                               loss_clip=self.loss_clip or 0.0, dist_threshold=0.05, min_uncertainty=1e-5)
         _lib.check(self.lib.kfn_flow_loss_grad(C.byref(d), self.flow.data_ptr(), self.sigma.data_ptr(), self.labels.data_ptr(),
@@ -400,7 +442,7 @@ class OFlowNetTrainer(object):
         """The backward pass into self.grads from the gradients with respect to flow [N,2] and sigma_trans [N] -- the loss's
         by default; explicit device tensors are the seam of joint stage 3."""
         stream = staging.current_stream(self.device) if stream is None else stream
-        P, (H, Wd), (h, w), N = self.pairs, self.image_size, self.grid, self.windows
+        P, F, (H, Wd), (h, w), N = self.pairs, self.nframes, self.image_size, self.grid, self.windows
         d_flow = self.d_flow if d_flow is None else d_flow
         d_sigma = self.d_sigma if d_sigma is None else d_sigma
         lg, un = self.logits_layer, self.fc[-1]
@@ -419,12 +461,19 @@ class OFlowNetTrainer(object):
             self._input_gradient(L, stream)
         _lib.check(self.lib.kfn_cost_volume_backward(self.d_vol.ptr, self.d_fb.data_ptr(), self.d_fa.data_ptr(), P, h, w, 32, stream),
                    'kfn_cost_volume_backward')
-        g = self.d_feat.view(P, 2, h * w, 32)
-        g[:, 0].copy_(self.d_fa.view(P, h * w, 32))
-        g[:, 1].copy_(self.d_fb.view(P, h * w, 32))
+        if self.pair_index is None:
+            g = self.d_feat.view(P, 2, h * w, 32)
+            g[:, 0].copy_(self.d_fa.view(P, h * w, 32))
+            g[:, 1].copy_(self.d_fb.view(P, h * w, 32))
+        else:
+            # a frame is at most once a b and once an a: its row is zero, then d_fb, then d_fb + d_fa -- one add per address
+            g = self.d_feat.view(F, h * w, 32)
+            g.zero_()
+            g.index_copy_(0, self.b_idx, self.d_fb.view(P, h * w, 32))
+            g.index_add_(0, self.a_idx, self.d_fa.view(P, h * w, 32))
         last = self.tower[-1]
         _lib.check(self.lib.kfn_l2norm_backward(last.y.ptr, last.y.ld, self.d_feat.data_ptr(), 32, last.dy.ptr, last.dy.ld,
-                                                2 * P * h * w, 32, stream), 'kfn_l2norm_backward')
+                                                F * h * w, 32, stream), 'kfn_l2norm_backward')
         for L in reversed(self.tower[1:]):
             if L.relu:
                 self._relu_mask(L.y, L.dy, stream)
@@ -432,7 +481,7 @@ class OFlowNetTrainer(object):
             self._input_gradient(L, stream)
         first = self.tower[0]
         self._relu_mask(first.y, first.dy, stream)
-        _lib.check(self.lib.kfn_first_conv_u8_grad_weights(self.frames.data_ptr(), 2 * P, H, Wd, first.dy.ptr, first.co,
+        _lib.check(self.lib.kfn_first_conv_u8_grad_weights(self.frames.data_ptr(), F, H, Wd, first.dy.ptr, first.co,
                                                            self._ptr(self.grads, first, 'kernel'), self._ptr(self.grads, first, 'bias'),
                                                            self.workspace.data_ptr(), stream), 'kfn_first_conv_u8_grad_weights')
 

@@ -1,5 +1,6 @@
-"""Fine-tuning SCoordNet through the Kalman filter with OFlowNet frozen: stage 3 of the reference's procedure ("Train KFNet")
-under --fix_flownet (KFNet/train.py:268-298 with KFNet.GetKFCoordBatch, KFNet/KFNet.py:102-162).
+"""Stage 3 of the reference's procedure ("Train KFNet"): fine-tuning SCoordNet through the Kalman filter with OFlowNet frozen
+(--fix_flownet; KFNet/train.py:268-298 with KFNet.GetKFCoordBatch, KFNet/KFNet.py:102-162), or training both
+networks through it (train_flownet=True, the reference's default; KFNet/train.py:282-303).
 
 A step sees S groups of T consecutive frames (T = 4 on the command line).  Its launches, on top of kfnet_amd.train's:
 
@@ -12,8 +13,14 @@ A step sees S groups of T consecutive frames (T = 4 on the command line).  Its l
     backward    kfn_filter_backward: the reverse scan, whose measurement gradients join d(loss)/d(prediction);
                 then SCoordNetTrainer.backward, Adam and the packs as in stage 1
 
-Only ScoreNet/* is trained and regularised; Temporal/* is handed through unchanged.  There is no fallback: a missing entry
-point raises, and so does a flow outside the radius the reverse scan gathers over.
+Only ScoreNet/* is trained and regularised; Temporal/* is handed through unchanged.
+
+With train_flownet=True an OFlowNetTrainer stands where the frozen engine stood: the S (T - 1) pairs (t - 1, t) of the groups
+share the staged frames, its forward pass (activations kept) gives flow and sigma_trans, kfn_filter_backward_joint emits their
+gradients beside the measurement's, OFlowNetTrainer.backward takes them down to feat1 on the flow stream beside SCoordNet's
+backward pass, and both scopes take an Adam step with one global_step, learning rate and weight decay.
+
+There is no fallback: a missing entry point raises, and so does a flow outside the radius the reverse scan gathers over.
 """
 import ctypes as C
 import os
@@ -60,6 +67,18 @@ def group_indices(step, S, groups, shuffle=False, seed=0):
     return out
 
 
+def pair_table(S, T):
+    """The pairs of a joint step over S groups of T frames: (a_idx, b_idx), pair s (T - 1) + t - 1 = frames (s T + t - 1, s T + t)
+    for t = 1 .. T - 1.  OFlowNet sees frame b = t from frame a = t - 1, as the eval engine does."""
+    b = np.array([s * T + t for s in range(S) for t in range(1, T)], dtype=np.int64)
+    return b - 1, b
+
+
+def split_state(st, scopes=(SCOPE, FLOW_SCOPE)):
+    """Which of `scopes` a train-state file carries Adam slots for: {scope: bool}."""
+    return {scope: any(k.startswith('adam_m/%s/' % scope) for k in st) for scope in scopes}
+
+
 def start_step(snapshot_step, stepvalue, reset_step, scoordnet, oflownet):
     """set_stepvalue's rule (KFNet/train.py:348-350, :364-365): with both --scoordnet and --oflownet the step is reset to 4
     stepvalue; otherwise an explicit --reset_step wins over the snapshot's step."""
@@ -99,9 +118,10 @@ def check_flow_count(stats_host, radius):
 class KFNetTrainer(object):
     def __init__(self, weights, image_size=(480, 640), groups=1, group=GROUP, transform=None, base_lr=1e-4, gamma=0.5,
                  stepvalue=80000, weight_decay=1e-4, loss_clip=None, smooth_weight=50.0, loss_weights=LOSS_WEIGHTS,
-                 radius=RADIUS, device='cuda:0'):
+                 radius=RADIUS, device='cuda:0', train_flownet=False, overlap=True):
         """weights: {TF name: array} holding ScoreNet/* and Temporal/*.  groups = S, group = T.  The other arguments are
-        SCoordNetTrainer's; loss_weights = (measure, temporal, KF)."""
+        SCoordNetTrainer's; loss_weights = (measure, temporal, KF).  train_flownet: train Temporal/* too, with the same
+        schedule and weight decay; overlap: run its backward pass on the flow stream beside SCoordNet's (else behind it)."""
         import torch
         from .engine import OFlowNetEngine
         if groups < 1 or group < 2:
@@ -115,16 +135,28 @@ class KFNetTrainer(object):
         self.torch, self.lib, self.device = torch, sc.lib, sc.device
         self.loss_weights = tuple(float(x) for x in loss_weights)
         self.radius = int(radius)
+        self.train_flownet, self.overlap = bool(train_flownet), bool(overlap)
         self.flow_weights = {k: np.asarray(v, dtype=np.float32).copy() for k, v in weights.items()
                              if k.startswith(FLOW_SCOPE + '/')}
         h, w = sc.grid
         with torch.cuda.device(self.device):
             self.flow_stream = torch.cuda.Stream(device=self.device)
             self.ev_frames, self.ev_flow = torch.cuda.Event(), torch.cuda.Event()
-            with torch.cuda.stream(self.flow_stream):
-                self.engine = OFlowNetEngine(self.flow_weights, image_size=image_size, batch=self.T, max_chunk=B, device=device)
-            self.flow_stream.synchronize()
             f32 = dict(dtype=torch.float32, device=self.device)
+            if self.train_flownet:
+                from .train_flow import OFlowNetTrainer
+                self.engine = None
+                self.ft = OFlowNetTrainer(self.flow_weights, image_size=image_size, pairs=self.S * (self.T - 1), base_lr=base_lr,
+                                          gamma=gamma, stepvalue=stepvalue, weight_decay=weight_decay, device=device, frames=B,
+                                          pair_index=pair_table(self.S, self.T))
+                self.ev_back, self.ev_flow_done = torch.cuda.Event(), torch.cuda.Event()
+                # flow and sigma_trans in the scan's [S,T,hw] layout (slot 0 of a group is never read) and their gradients
+                self.c_flow, self.c_sigma = torch.zeros((B, h, w, 2), **f32), torch.zeros((B, h, w), **f32)
+                self.d_flow, self.d_sigma = torch.zeros((B, h, w, 2), **f32), torch.zeros((B, h, w), **f32)
+            else:
+                with torch.cuda.stream(self.flow_stream):
+                    self.engine = OFlowNetEngine(self.flow_weights, image_size=image_size, batch=self.T, max_chunk=B, device=device)
+                self.flow_stream.synchronize()
             self.meas = torch.zeros((B, h, w, 4), **f32)
             self.temp = torch.zeros((B, h, w, 4), **f32)
             self.kf = torch.zeros((B, h, w, 4), **f32)
@@ -153,19 +185,42 @@ class KFNetTrainer(object):
     adam_t = property(lambda self: self.sc.adam_t)
 
     def weights(self):
-        """Both scopes: ScoreNet/* as trained, Temporal/* as given -- what KFNet.eval --model_folder reads."""
+        """Both scopes: ScoreNet/* as trained, Temporal/* as given (as trained with train_flownet) -- what KFNet.eval
+        --model_folder reads."""
         W = self.sc.weights()
-        W.update({k: v.copy() for k, v in self.flow_weights.items()})
+        W.update(self.ft.weights() if self.train_flownet else {k: v.copy() for k, v in self.flow_weights.items()})
         return W
 
     def gradients(self):
-        return self.sc.gradients()
+        g = self.sc.gradients()
+        if self.train_flownet:
+            g.update(self.ft.gradients())
+        return g
 
     def state(self):
-        return self.sc.state()
+        """One file's content: the counters and ScoreNet/*'s Adam slots, with train_flownet Temporal/*'s beside them."""
+        st = self.sc.state()
+        if self.train_flownet:
+            st.update({k: v for k, v in self.ft.state().items() if k.startswith('adam_')})
+        return st
 
-    def load_state(self, st):
-        self.sc.load_state(st)
+    def load_state(self, st, verbose=True):
+        """With train_flownet a state of an --fix_flownet run, of stage 1 or of stage 2 loads too: the slots of the scope it
+        lacks start at zero."""
+        if not self.train_flownet:
+            self.sc.load_state(st)
+            return
+        for scope, held in split_state(st).items():
+            tr = self.sc if scope == SCOPE else self.ft
+            if held:
+                tr._fill(tr.m, st, 'adam_m/')
+                tr._fill(tr.v, st, 'adam_v/')
+            else:
+                tr.m.zero_()
+                tr.v.zero_()
+                if verbose:
+                    print('the train state holds no Adam slots of %s/*: they start at zero' % scope)
+        self.sc.global_step, self.sc.adam_t = int(st['global_step']), int(st['adam_t'])
 
     def save(self, folder, step=None):
         """Writes kfnet_weights-<step>.npz (both scopes) and kfnet_train_state-<step>.npz; returns the two paths."""
@@ -174,7 +229,7 @@ class KFNetTrainer(object):
         os.makedirs(folder, exist_ok=True)
         wp, sp = snapshot_paths(folder, step)
         save_npz(wp, self.weights())
-        np.savez(sp, **self.sc.state())
+        np.savez(sp, **self.state())
         return wp, sp
 
     # ---- one step ----------------------------------------------------------------------------------------------------
@@ -184,8 +239,38 @@ class KFNetTrainer(object):
         self.ev_frames.record(main)
         self.flow_stream.wait_event(self.ev_frames)
         with self.torch.cuda.stream(self.flow_stream):
-            self.engine.heavy(self.sc.frames, self.S * self.T)
+            if self.train_flownet:
+                self.flow_forward()
+            else:
+                self.engine.heavy(self.sc.frames, self.S * self.T)
             self.ev_flow.record(self.flow_stream)
+
+    def flow_forward(self):
+        """OFlowNetTrainer's forward pass on the frames SCoordNet staged, on torch's current stream; then its flow [P hw,2] and
+        sigma_trans [P hw] into slots 1 .. T-1 of every group of the scan's layout."""
+        ft, (S, T) = self.ft, (self.S, self.T)
+        ft.stage(self.sc.frames)
+        ft.forward()
+        self.c_flow.view(S, T, -1, 2)[:, 1:].copy_(ft.flow.view(S, T - 1, -1, 2))
+        self.c_sigma.view(S, T, -1)[:, 1:].copy_(ft.sigma.view(S, T - 1, -1))
+
+    def flow_backward(self, main):
+        """The gradients of the reverse scan back in the pair layout, then OFlowNetTrainer.backward: on the flow stream behind
+        an event (overlap), so that it runs beside SCoordNet's backward pass, or on `main`."""
+        ft, (S, T) = self.ft, (self.S, self.T)
+        side = self.flow_stream if self.overlap else main
+        if self.overlap:
+            self.ev_back.record(main)
+            side.wait_event(self.ev_back)
+        with self.torch.cuda.stream(side):
+            ft.d_flow.view(S, T - 1, -1, 2).copy_(self.d_flow.view(S, T, -1, 2)[:, 1:])
+            ft.d_sigma.view(S, T - 1, -1).copy_(self.d_sigma.view(S, T, -1)[:, 1:])
+            ft.backward(stream=side.cuda_stream)
+
+    def _scan_inputs(self):
+        if self.train_flownet:
+            return self.c_flow.data_ptr(), self.c_sigma.data_ptr()
+        return self.engine.c_flow.ptr, self.engine.c_sigma.ptr
 
     def forward(self, stream=None):
         """SCoordNet, the measurement map and the filter: self.meas, self.temp, self.kf.  The flow must have been launched
@@ -200,8 +285,8 @@ class KFNetTrainer(object):
         main.wait_event(self.ev_flow)
         _lib.check(self.lib.kfn_memset(self.filter_state.data_ptr(), 0, self.filter_state.numel() * 4, stream),
                    'kfn_memset state')
-        eng = self.engine
-        _lib.check(self.lib.kfn_kalman_scan_ex(C.byref(self.scan_desc), eng.c_flow.ptr, eng.c_sigma.ptr, self.meas.data_ptr(),
+        c_flow, c_sigma = self._scan_inputs()
+        _lib.check(self.lib.kfn_kalman_scan_ex(C.byref(self.scan_desc), c_flow, c_sigma, self.meas.data_ptr(),
                                                self.filter_state.data_ptr(), self.records.data_ptr(), self.temp.data_ptr(), None,
                                                self.kf.data_ptr(), 0,
                                                self.scan_scratch.data_ptr() if self.scan_scratch is not None else None, stream),
@@ -226,8 +311,15 @@ class KFNetTrainer(object):
 
     def filter_backward(self, stream=None):
         stream = staging.current_stream(self.device) if stream is None else stream
-        eng = self.engine
-        _lib.check(self.lib.kfn_filter_backward(C.byref(self.back_desc), eng.c_flow.ptr, self.meas.data_ptr(),
+        c_flow, c_sigma = self._scan_inputs()
+        if self.train_flownet:
+            _lib.check(self.lib.kfn_filter_backward_joint(C.byref(self.back_desc), c_flow, c_sigma, self.meas.data_ptr(),
+                                                          self.temp.data_ptr(), self.kf.data_ptr(), self.d_temp.data_ptr(),
+                                                          self.d_kf.data_ptr(), self.sc.dact[-1].data_ptr(), self.d_flow.data_ptr(),
+                                                          self.d_sigma.data_ptr(), self.stats.data_ptr(),
+                                                          self.back_scratch.data_ptr(), stream), 'kfn_filter_backward_joint')
+            return
+        _lib.check(self.lib.kfn_filter_backward(C.byref(self.back_desc), c_flow, self.meas.data_ptr(),
                                                 self.temp.data_ptr(), self.kf.data_ptr(), self.d_temp.data_ptr(),
                                                 self.d_kf.data_ptr(), self.sc.dact[-1].data_ptr(), self.stats.data_ptr(),
                                                 self.back_scratch.data_ptr(), stream), 'kfn_filter_backward')
@@ -247,15 +339,32 @@ class KFNetTrainer(object):
             self.filter_backward(stream)
             self._flow_count.copy_(self.stats.view(torch.int32)[11:12], non_blocking=True)
             self.ev_count.record(main)
+            if self.train_flownet:
+                self.flow_backward(main)
             sc.backward(stream)
             stats = self.stats.clone()
             # the one wait of a step: for the reverse scan's counter, while the backward pass is still queued
             self.ev_count.synchronize()
             if int(self._flow_count[0]):
                 raise _lib.KfnError(FLOW_MESSAGE % (int(self._flow_count[0]), self.radius))
+            if self.train_flownet:
+                self.flow_update(main)
             lr = sc.apply_gradients(stream)
             sc._repack(stream)
         return StepStats(stats, lr, self.radius)
+
+    def flow_update(self, main):
+        """Temporal/*'s Adam step and packs with SCoordNet's counters, where its backward pass ran; `main` then waits for the
+        flow stream, so that the next step may overwrite the frames."""
+        ft = self.ft
+        ft.global_step, ft.adam_t = self.sc.global_step, self.sc.adam_t
+        side = self.flow_stream if self.overlap else main
+        with self.torch.cuda.stream(side):
+            ft.apply_gradients(side.cuda_stream)
+            ft._repack(side.cuda_stream)
+        if self.overlap:
+            self.ev_flow_done.record(side)
+            main.wait_event(self.ev_flow_done)
 
 
 def restore(model_folder, scoordnet='', oflownet='', verbose=True):

@@ -5,6 +5,7 @@ launch as fractions of the fp32 MFMA peak.
     python tools/mb_train.py [--height 480 --width 640 --batch 4 --steps 10 --warmup 3] [--layers] [--augment] [--depth]
     python tools/mb_train.py --kfnet [--groups 1]
     python tools/mb_train.py --oflownet [--pairs 4]
+    python tools/mb_train.py --joint [--groups 1]
 
 --augment times the step with the augmentation of DESIGN.md 6c on: full-resolution labels, the parameters of
 kfnet_amd.augment.draw(0, step) in turn (its kernels are channel_sums_kernel and augment_kernel in a kernel trace).
@@ -17,6 +18,9 @@ reverse scan -- each alone and as a share of the step.
 forward, loss + backward, Adam and packs, and the launches stage 2 adds, each alone: the cost volume's transpose with the bytes
 that have to cross HBM (d_vol once, two feature maps) over its time as a share of 8 TB/s, the flow head's and the L2
 normalisation's backward, and the loss.
+--joint times the joint step of KFNetTrainer (train_flownet): ms per step with OFlowNet's backward pass on the
+flow stream beside SCoordNet's and on one stream, the share of the launches the joint step adds to the fixed one (the reverse
+scan's joint form beside the fixed form, the copies between the pair and the scan layout), and the OFlowNet backward alone.
 
 Under `rocprofv3 --kernel-trace --stats -- python tools/mb_train.py --steps 5` the kernel table gives the same split per
 kernel name (wgrad_mfma_kernel, conv_mfma_kernel, ...)."""
@@ -79,6 +83,60 @@ def kfnet(a):
         print('%-72s %7.3f ms  %5.1f%% of the step' % (name, v, 100 * v / ms))
     print('the new launches together %.3f ms = %.1f%% of the step; SCoordNet forward %.2f ms, backward %.2f ms' %
           (new, 100 * new / ms, t['SCoordNet forward'], t['SCoordNet backward']))
+    return 0
+
+
+def joint(a):
+    import torch
+    from kfnet_amd.synth import synthetic_sequence, synthetic_transform
+    from kfnet_amd.train import synthetic_labels
+    from kfnet_amd.train_kfnet import GROUP, KFNetTrainer
+    from kfnet_amd.weights import initial_weights, synthetic_weights
+    W = initial_weights(0)
+    W.update({k: v for k, v in synthetic_weights(1234).items() if k.startswith('Temporal/')})
+    B = a.groups * GROUP
+    frames = torch.from_numpy(synthetic_sequence(B, a.height, a.width)).cuda()
+    ms = {}
+    for overlap in (True, False):
+        tr = KFNetTrainer(W, image_size=(a.height, a.width), groups=a.groups, transform=synthetic_transform(), train_flownet=True,
+                          overlap=overlap)
+        labels = torch.from_numpy(synthetic_labels(B, tr.sc.grid)).cuda()
+        for _ in range(a.warmup):
+            tr.step(frames, labels)
+        ms[overlap] = timed(torch, lambda: tr.step(frames, labels), a.steps)
+        print('%dx%d, %d group(s) of %d, joint, OFlowNet backward %s: %.2f ms per step (%.1f frames/s)' % (
+            a.height, a.width, a.groups, GROUP, 'on the flow stream' if overlap else 'on the main stream', ms[overlap],
+            1e3 * B / ms[overlap]))
+    step = ms[False]
+    main = torch.cuda.current_stream()
+    stride = tr.sc.stage(frames, labels, None, main.cuda_stream)
+    tr.flow(main)
+    tr.forward()
+    tr.loss(stride)
+    fixed = tr.lib.kfn_filter_backward
+    c_flow = tr.c_flow.data_ptr()
+
+    def fixed_scan():
+        fixed(tr.back_desc, c_flow, tr.meas.data_ptr(), tr.temp.data_ptr(), tr.kf.data_ptr(), tr.d_temp.data_ptr(),
+              tr.d_kf.data_ptr(), tr.sc.dact[-1].data_ptr(), tr.stats.data_ptr(), tr.back_scratch.data_ptr(), main.cuda_stream)
+
+    def copies():
+        S, T, ft = tr.S, tr.T, tr.ft
+        tr.c_flow.view(S, T, -1, 2)[:, 1:].copy_(ft.flow.view(S, T - 1, -1, 2))
+        tr.c_sigma.view(S, T, -1)[:, 1:].copy_(ft.sigma.view(S, T - 1, -1))
+        ft.d_flow.view(S, T - 1, -1, 2).copy_(tr.d_flow.view(S, T, -1, 2)[:, 1:])
+        ft.d_sigma.view(S, T - 1, -1).copy_(tr.d_sigma.view(S, T, -1)[:, 1:])
+    parts = [('reverse scan, joint form', tr.filter_backward), ('reverse scan, fixed form', fixed_scan),
+             ('copies between the pair and the scan layout', copies), ('OFlowNet forward, activations kept', tr.ft.forward),
+             ('OFlowNet backward', lambda: tr.ft.backward()), ('OFlowNet Adam + packs', lambda: (tr.ft.apply_gradients(),
+                                                                                                 tr.ft._repack(main.cuda_stream))),
+             ('SCoordNet backward', tr.sc.backward)]
+    t = {name: timed(torch, fn, a.steps) for name, fn in parts}
+    for name, _ in parts:
+        print('%-48s %7.3f ms  %5.1f%% of the one-stream step' % (name, t[name], 100 * t[name] / step))
+    new = t['reverse scan, joint form'] - t['reverse scan, fixed form'] + t['copies between the pair and the scan layout']
+    print('the new launches (the scan\'s extra work and the copies) %.3f ms = %.2f%% of the step; the flow stream hides %.2f ms' %
+          (new, 100 * new / step, ms[False] - ms[True]))
     return 0
 
 
@@ -153,10 +211,13 @@ def main(argv=None):
     ap.add_argument('--augment', action='store_true', help='time the step with augmentation on')
     ap.add_argument('--depth', action='store_true', help='make the labels of every step from depth maps and poses')
     ap.add_argument('--kfnet', action='store_true', help='time the step of KFNetTrainer (SCoordNet through the filter)')
-    ap.add_argument('--groups', type=int, default=1, help='--kfnet: groups of four frames per step')
+    ap.add_argument('--groups', type=int, default=1, help='--kfnet, --joint: groups of four frames per step')
+    ap.add_argument('--joint', action='store_true', help='time the joint step of KFNetTrainer (both networks trained)')
     ap.add_argument('--oflownet', action='store_true', help='time the step of OFlowNetTrainer (stage 2) and the launches it adds')
     ap.add_argument('--pairs', type=int, default=4, help='--oflownet: pairs of frames per step')
     a = ap.parse_args(argv)
+    if a.joint:
+        return joint(a)
     if a.kfnet:
         return kfnet(a)
     if a.oflownet:
