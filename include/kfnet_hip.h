@@ -642,7 +642,8 @@ int kfn_recv_state(kfn_comm* comm, int peer, float* state /* [H,W,4] */, int H, 
  * (KFNet/train.py:300-315) over the ScoreNet variables.  TensorFlow derives the backward graph; here it is the entry points
  * below plus the EXISTING forward kernels: the input gradient of a stride-1 convolution is kfn_conv2d_nhwc on the kernel
  * rotated by 180 degrees with its channel axes swapped, that of a stride-2 convolution of an even-sized image is the
- * transposed convolution (kfn_conv_desc.transposed = 1) with the kernel as it is.  fp32 only.  DESIGN.md "Training".
+ * transposed convolution (kfn_conv_desc.transposed = 1) with the kernel as it is.  fp32 here; fp16 operands: the section
+ * "mixed-precision training" below.  DESIGN.md "Training".
  *
  * kfn_conv2d_grad_weights -- the gradient of tf.layers.conv2d (cnn_wrapper/network.py:116-135) with respect to its kernel
  * and bias.  `desc` is the FORWARD convolution's descriptor (N, H, W, Cin, ldx of its input x; Cout; kh = kw = 3 or 1;
@@ -718,6 +719,48 @@ int kfn_coord_loss_grad(const kfn_coord_loss_desc* desc, const float* pred, cons
  * evaluated in fp64 from the fp32 variables, each stored value rounded once. */
 int kfn_adam_step(float* w, float* m, float* v, const float* g, long n, double lr_t, double beta1, double beta2,
                   double epsilon, double weight_decay, void* stream);
+
+/* ---- mixed-precision training of SCoordNet (added exports; the ABI number stays 13) ----------------------------------
+ * Tensors, master weights and Adam's slots stay fp32 in memory; the convolutions' operands are rounded to IEEE halfs (RNE)
+ * while they are staged and multiplied on v_mfma_f32_32x32x16_f16 with fp32 accumulation.  Forward passes and input
+ * gradients are kfn_conv2d_nhwc with operand_dtype = KFN_OPERAND_F16 and half packs.  DESIGN.md 6h.
+ *
+ * kfn_conv2d_grad_weights with desc.operand_dtype = KFN_OPERAND_F16: the contract above (x, dz, dw, db, workspace fp32;
+ * runs of pixels fixed by the shapes; planes added in ascending order; no atomics; bit-identical launches), the products
+ * being those of x and dz rounded to halfs.  Needs Cin % 32 == 0, Cout % 32 == 0, desc.ldy % 4 == 0 and a 16-byte aligned
+ * dz: KFN_ERR_ARG otherwise, and nothing launched.  kfn_conv2d_grad_weights_workspace_bytes follows operand_dtype:
+ * a run is a multiple of 32 pixels instead of 16.
+ *
+ * kfn_pack_conv_weights_f16 -- kfn_pack_conv_weights with every value rounded once (RNE) to an IEEE half: the layout of
+ * the fp32 pack, kfn_pack_conv_weights_floats elements of 2 bytes, what kfnet_amd.graph.as_f16(pack_conv_kernel) makes on
+ * the host and kfn_conv2d_nhwc reads under KFN_OPERAND_F16. */
+int kfn_pack_conv_weights_f16(const float* w_hwio, int kh, int kw, int Cin, int Cout, int kind, void* out_halfs, void* stream);
+
+/* Dynamic loss scaling without a read-back.  One record in DEVICE memory, written by the host once (scale a power of two,
+ * both powers 1.0, every counter 0) and from then on by the launches below:
+ *   kfn_loss_scale_apply          buf[i] *= scale (the gradient of the loss with respect to the prediction, after
+ *                                 kfn_coord_loss_grad); exact, the scale being a power of two
+ *   kfn_loss_scale_unscale_check  grads[i] *= 1 / scale; overflow |= 1 if any element was inf or NaN (an integer OR)
+ *   kfn_adam_step_guarded         kfn_adam_step's arithmetic when overflow == 0, with lr_t = lr sqrt(1 - beta2_power beta2) /
+ *                                 (1 - beta1_power beta1) from the record (fp64); w, m, v untouched otherwise.  Then one
+ *                                 thread of a second launch: on overflow scale = max(scale / 2, 1), good_steps = 0,
+ *                                 skipped += 1, overflow = 0; otherwise beta1_power *= beta1, beta2_power *= beta2,
+ *                                 adam_t += 1, good_steps += 1, and after growth_interval such steps scale = min(2 scale,
+ *                                 2^24), good_steps = 0.
+ * The powers are products accumulated once per APPLIED step, as TensorFlow's beta1_power / beta2_power variables. */
+typedef struct kfn_loss_scale_state {
+  double beta1_power, beta2_power;
+  float scale;
+  int32_t good_steps;       /* applied steps since the scale last changed */
+  int32_t overflow;         /* raised by kfn_loss_scale_unscale_check, cleared by kfn_adam_step_guarded */
+  int32_t skipped;          /* steps dropped because of an overflow */
+  int32_t adam_t;           /* applied steps */
+  int32_t reserved;         /* 0 */
+} kfn_loss_scale_state;
+int kfn_loss_scale_apply(float* buf, long n, const kfn_loss_scale_state* state, void* stream);
+int kfn_loss_scale_unscale_check(float* grads, long n, kfn_loss_scale_state* state, void* stream);
+int kfn_adam_step_guarded(float* w, float* m, float* v, const float* g, long n, double lr, double beta1, double beta2,
+                          double epsilon, double weight_decay, int growth_interval, kfn_loss_scale_state* state, void* stream);
 
 /* ---- augmenting a training batch (added exports; the ABI number stays 13) --------------------------------------------
  * data_augmentation of the reference (KFNet/train.py:168-193): tf.image.random_brightness / random_contrast on the frames,

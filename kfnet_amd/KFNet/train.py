@@ -19,7 +19,8 @@ is) and kfnet_train_state-<step>.npz.
 
 The flags are the reference's (KFNet/train.py:14-47) and stage 1's, and --joint.  A stated deviation: the reference trains
 both networks unless told --fix_flownet; here the plain command line stops and asks for one of the two flags.  --augment is
-refused: the reference's stage 3 has none.  --loss_clip is off by default, as in stage 1.
+refused: the reference's stage 3 has none, and so is --fp16: mixed precision is built for stage 1 only.  --loss_clip is off by
+default, as in stage 1.
 """
 import argparse
 import sys
@@ -65,6 +66,9 @@ def main(argv=None):
         return 1
     if a.augment:
         print('--augment is refused: stage 3 of the reference trains without augmentation', file=sys.stderr)
+        return 1
+    if a.fp16 or a.loss_scale is not None:
+        print('--fp16 is refused: mixed precision is built for stage 1 (SCoordNet.train) only', file=sys.stderr)
         return 1
     if not a.model_folder:
         print('--model_folder is required: the snapshots go there', file=sys.stderr)

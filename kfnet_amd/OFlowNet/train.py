@@ -57,6 +57,7 @@ def build_parser():
     ap.add_argument('--loss_clip', type=float, default=None)
     ap.add_argument('--synthetic', type=int, default=0, help='train on this many seeded synthetic frames and labels')
     ap.add_argument('--augment', action='store_true', help='refused: not built for pairs')
+    ap.add_argument('--fp16', action='store_true', help='refused: mixed precision is built for SCoordNet.train only')
     ap.add_argument('--depth', action='store_true', help='make the labels on the device from depth_list.txt and pose_list.txt')
     from ..labels import add_camera_flags
     add_camera_flags(ap)
@@ -67,6 +68,9 @@ def main(argv=None):
     a = build_parser().parse_args(argv)
     if a.augment:
         print('--augment is not built for OFlowNet.train: both frames of a pair would need one draw', file=sys.stderr)
+        return 1
+    if a.fp16:
+        print('--fp16 is refused: mixed precision is built for stage 1 (SCoordNet.train) only', file=sys.stderr)
         return 1
     if not a.model_folder:
         print('--model_folder is required: the snapshots go there', file=sys.stderr)

@@ -18,6 +18,9 @@ pixels the loss uses.
 kfnet_amd.labels make --no_labels` writes), and every batch's labels are made on the device from its 16-bit depth maps and
 poses -- at the pixels the loss reads, or at full resolution with --augment.  The camera flags are those of
 `labels make`.
+`--fp16` trains in mixed precision: conv1b .. conv7 on fp16 MFMA operands with fp32 accumulation, tensors and
+master weights in fp32, under dynamic loss scaling that starts at --loss_scale (a power of two, default 32768).  The printed
+line then ends with the scale and the number of steps skipped because of an overflow; `step` counts attempted steps.
 """
 import argparse
 import sys
@@ -32,10 +35,17 @@ FORMAT = ('[%s] epoch %d, step %d/%d, loss=%.3f, l_measure=%.3f, l_smooth=%.3f, 
           '(%.3f sec/step)')
 
 
+FORMAT_FP16 = ', loss_scale=%d, skipped=%d'
+
+
 def format_line(now, epoch, step, max_steps, s, duration):
-    """KFNet/train.py:427-432 reduced to the measurement fields."""
-    return FORMAT % (now, epoch, step, max_steps, s['loss'], s['l_measure'], s['l_smooth'], s['a_measure'], s['pixels'],
+    """KFNet/train.py:427-432 reduced to the measurement fields; under --fp16 (s holds 'loss_scale') the scale and the
+    skipped steps behind them."""
+    line = FORMAT % (now, epoch, step, max_steps, s['loss'], s['l_measure'], s['l_smooth'], s['a_measure'], s['pixels'],
                      s['lr'], duration)
+    if 'loss_scale' in s:
+        line += FORMAT_FP16 % (s['loss_scale'], s['skipped'])
+    return line
 
 
 def schedule(scene, stepvalue=None, max_steps=None):
@@ -69,6 +79,8 @@ def build_parser():
     ap.add_argument('--augment', action='store_true', help='brightness, contrast, rotation and zoom / shrink per batch')
     ap.add_argument('--augment_seed', type=int, default=None, help='seed of the augmentation draws (default: --seed)')
     ap.add_argument('--depth', action='store_true', help='make the labels on the device from depth_list.txt and pose_list.txt')
+    ap.add_argument('--fp16', action='store_true', help='mixed precision: fp16 MFMA operands under dynamic loss scaling')
+    ap.add_argument('--loss_scale', type=int, default=None, help='initial loss scale of --fp16, a power of two (default 32768)')
     from ..labels import add_camera_flags
     add_camera_flags(ap)
     return ap
@@ -84,6 +96,13 @@ def main(argv=None):
         return 1
     if a.display < 1 or a.snapshot < 1 or a.batch < 1:
         print('--display, --snapshot and --batch must be >= 1', file=sys.stderr)
+        return 1
+    if a.loss_scale is not None and not a.fp16:
+        print('--loss_scale belongs to --fp16', file=sys.stderr)
+        return 1
+    loss_scale = 2 ** 15 if a.loss_scale is None else a.loss_scale
+    if loss_scale < 1 or loss_scale > 2 ** 24 or loss_scale & (loss_scale - 1):
+        print('--loss_scale must be a power of two in 1 .. 2^24', file=sys.stderr)
         return 1
     stepvalue, max_steps = schedule(a.scene, a.stepvalue, a.max_steps)
     from ..batches import open_source
@@ -104,7 +123,8 @@ def main(argv=None):
     torch.cuda.set_device(a.gpu)
     tr = SCoordNetTrainer(W, image_size=(a.height, a.width), batch=a.batch, transform=source.transform, base_lr=a.base_lr,
                           gamma=a.gamma, stepvalue=stepvalue, weight_decay=a.weight_decay, loss_clip=a.loss_clip,
-                          smooth_weight=a.smooth_weight, device='cuda:%d' % a.gpu)
+                          smooth_weight=a.smooth_weight, device='cuda:%d' % a.gpu, precision='fp16' if a.fp16 else 'fp32',
+                          loss_scale=loss_scale)
     if state is not None:
         tr.load_state(state)
     tr.global_step = step if a.reset_step < 0 else a.reset_step

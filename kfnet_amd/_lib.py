@@ -120,6 +120,12 @@ class FlowLossDesc(SizedStructure):
                 ('dist_threshold', C.c_double), ('min_uncertainty', C.c_double)]
 
 
+class LossScaleState(C.Structure):
+    """kfn_loss_scale_state (include/kfnet_hip.h): the record in device memory that drives dynamic loss scaling."""
+    _fields_ = [('beta1_power', C.c_double), ('beta2_power', C.c_double), ('scale', C.c_float), ('good_steps', C.c_int32),
+                ('overflow', C.c_int32), ('skipped', C.c_int32), ('adam_t', C.c_int32), ('reserved', C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/kfnet_hip.h
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 SYMBOLS = {
@@ -225,6 +231,12 @@ SYMBOLS = {
     'kfn_flow_loss_grad': (_i, [C.POINTER(FlowLossDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # joint stage 3: both networks through the Kalman filter (added export, ABI 13)
     'kfn_filter_backward_joint': (_i, [C.POINTER(FilterBackwardDesc)] + [_vp] * 13),
+    # mixed-precision training of SCoordNet (added exports, ABI 13)
+    'kfn_pack_conv_weights_f16': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'kfn_loss_scale_apply': (_i, [_vp, C.c_long, _vp, _vp]),
+    'kfn_loss_scale_unscale_check': (_i, [_vp, C.c_long, _vp, _vp]),
+    'kfn_adam_step_guarded': (_i, [_vp, _vp, _vp, _vp, C.c_long, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i,
+                               _vp, _vp]),
 }
 
 _lib = None

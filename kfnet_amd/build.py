@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(CSRC, 'build')
 LIB = os.path.join(HERE, 'libkfnet_hip.so')
-HEADERS = [os.path.join(CSRC, 'kfn_common.h'),
+HEADERS = [os.path.join(CSRC, 'kfn_common.h'), os.path.join(CSRC, 'kfn_train_shared.h'),
            os.path.join(os.path.dirname(HERE), 'include', 'kfnet_hip.h')]
 
 ARCH = 'gfx950'
@@ -39,6 +39,8 @@ EXTRA = {
     'kfn_train_filter.hip': ['-ffp-contract=off'],
     # training OFlowNet: the loss's per-cell terms as the filter's, and gather sums that a sequential fp32 restatement repeats
     'kfn_train_flow.hip': ['-ffp-contract=off'],
+    # the guarded Adam step repeats kfn_train_loss.hip's fp64 arithmetic, which a numpy restatement follows bit for bit
+    'kfn_loss_scale.hip': ['-ffp-contract=off'],
 }
 
 

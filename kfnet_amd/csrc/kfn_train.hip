@@ -3,10 +3,16 @@
 // weight packs of the forward and input-gradient launches.  Replaces what tf.gradients derives from tf.layers.conv2d
 // (cnn_wrapper/network.py:116-135) under AdamOptimizer.minimize (KFNet/train.py:313-314).  DESIGN.md "Training".
 //
-// Input gradients are NOT here: they run on the forward kernels (kfn_conv2d_nhwc) with the packs made below.
-#include "kfn_common.h"
+// Input gradients are NOT here: they run on the forward kernels (kfn_conv2d_nhwc) with the packs made below.  The fp16-operand
+// weight gradient is in kfn_train_f16.hip; kfn_train_shared.h holds what the two files share.
+#include "kfn_train_shared.h"
 
 namespace {
+
+using kfn::WG_BM;
+using kfn::WG_BP;
+using kfn::WgradArgs;
+using kfn::WgradPlan;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -23,23 +29,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // Every split writes its partial tile into its own plane of the workspace; wgrad_reduce_kernel adds the planes in the
 // order 0 .. splits-1.  No atomics: the result is a fixed function of the shapes.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int WG_BM = 128;        // k rows per workgroup
-constexpr int WG_BP = 16;         // pixels per stage
 constexpr int WG_TARGET = 1024;   // workgroups a launch aims for (4 per CU of an MI355X); a constant, so that the split --
                                   // and with it the summation order -- depends on the shapes alone, not on the device
 constexpr int WG_MIN_CHUNK = 512; // fewest pixels per split
-
-struct WgradArgs {
-  const float* x;
-  const float* dz;
-  float* ws;
-  int H, W, Cin, ldx, Cout, ldz, kw, stride, Ho, Wo, pad_t, pad_l;
-  int Ktot;       // kh*kw*Cin; row Ktot is the bias row
-  long P;         // N*Ho*Wo
-  long chunk;     // pixels per split (multiple of WG_BP)
-  int tiles_n;
-  int vec_b;      // dZ rows can be read as float4 (ldz % 4 == 0, 16-byte aligned base)
-};
 
 template <int TN>
 __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(WgradArgs p) {
@@ -178,11 +170,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   }
 }
 
-struct WgradPlan {
-  int Ho, Wo, pad_t, pad_l, Ktot, tn, tiles_m, tiles_n, splits;
-  long P, chunk;
-};
-
 int wgrad_plan(const kfn_conv_desc* d, WgradPlan* pl, const char* who) {
   KFN_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0, "%s: bad shape %dx%dx%d", who, d->N, d->H, d->W);
   KFN_REQUIRE(d->Cin > 0 && d->Cin % 16 == 0, "%s: Cin=%d must be a multiple of 16", who, d->Cin);
@@ -191,8 +178,14 @@ int wgrad_plan(const kfn_conv_desc* d, WgradPlan* pl, const char* who) {
   KFN_REQUIRE((d->kh == 3 && d->kw == 3) || (d->kh == 1 && d->kw == 1), "%s: kernel %dx%d (3x3 and 1x1 only)", who, d->kh, d->kw);
   KFN_REQUIRE(d->stride == 1 || d->stride == 2, "%s: stride %d unsupported", who, d->stride);
   KFN_REQUIRE(!d->transposed, "%s: the descriptor is the FORWARD convolution's (transposed = 0)", who);
-  KFN_REQUIRE(d->operand_dtype == KFN_OPERAND_F32 && d->x_dtype == KFN_ACT_F32 && d->y_dtype == KFN_ACT_F32,
-              "%s: fp32 only", who);
+  KFN_REQUIRE(d->operand_dtype == KFN_OPERAND_F32 || d->operand_dtype == KFN_OPERAND_F16, "%s: operand_dtype %d (fp32 or fp16 operands)",
+              who, d->operand_dtype);
+  KFN_REQUIRE(d->x_dtype == KFN_ACT_F32 && d->y_dtype == KFN_ACT_F32, "%s: fp32 activations in memory only", who);
+  const bool f16 = d->operand_dtype == KFN_OPERAND_F16;
+  // the fp16 kernel stages whole float4 of dZ and 32-column MFMA tiles: nothing ragged in the channels
+  KFN_REQUIRE(!f16 || (d->Cin % 32 == 0 && d->Cout % 32 == 0), "%s: fp16 operands need Cin %% 32 == 0 and Cout %% 32 == 0 (Cin=%d, Cout=%d)",
+              who, d->Cin, d->Cout);
+  KFN_REQUIRE(!f16 || d->ldy % 4 == 0, "%s: fp16 operands need dZ's pixel stride ldy %% 4 == 0 (ldy=%d)", who, d->ldy);
   kfn::same_pad(d->H, d->kh, d->stride, &pl->Ho, &pl->pad_t);
   kfn::same_pad(d->W, d->kw, d->stride, &pl->Wo, &pl->pad_l);
   pl->Ktot = d->kh * d->kw * d->Cin;
@@ -206,7 +199,8 @@ int wgrad_plan(const kfn_conv_desc* d, WgradPlan* pl, const char* who) {
   if (splits > most) splits = most;
   if (splits < 1) splits = 1;
   long chunk = (pl->P + splits - 1) / splits;
-  chunk = (chunk + WG_BP - 1) / WG_BP * WG_BP;
+  const int stage = f16 ? kfn::WG_BP_F16 : WG_BP;
+  chunk = (chunk + stage - 1) / stage * stage;
   pl->chunk = chunk;
   pl->splits = (int)((pl->P + chunk - 1) / chunk);
   KFN_REQUIRE(pl->splits <= 65535, "%s: too many splits", who);
@@ -282,9 +276,11 @@ __global__ __launch_bounds__(256) void relu_grad_kernel(const float* __restrict_
   }
 }
 
-// out[r][(a, b, c)], r < rows_pad, c < cols_pad: the matrix kfn_conv2d_nhwc multiplies by (K contiguous per output channel)
+// out[r][(a, b, c)], r < rows_pad, c < cols_pad: the matrix kfn_conv2d_nhwc multiplies by (K contiguous per output channel);
+// T = float, or _Float16 for the fp16-operand launches (the value rounded once, to nearest even)
+template <typename T>
 __global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restrict__ w, int kh, int kw, int Cin, int Cout,
-                                                           int kind, int rows_pad, int cols_pad, float* __restrict__ out) {
+                                                           int kind, int rows_pad, int cols_pad, T* __restrict__ out) {
   const long n = (long)rows_pad * kh * kw * cols_pad;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const int c = (int)(i % cols_pad);
@@ -301,7 +297,7 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restri
     } else {
       if (r < Cin && c < Cout) v = w[(((long)a * kw + b) * Cin + r) * Cout + c];
     }
-    out[i] = v;
+    out[i] = (T)v;
   }
 }
 
@@ -349,10 +345,16 @@ extern "C" int kfn_conv2d_grad_weights(const kfn_conv_desc* d, const float* x, c
   a.Ktot = pl.Ktot; a.P = pl.P; a.chunk = pl.chunk; a.tiles_n = pl.tiles_n;
   a.vec_b = (d->ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(dz) & 15) == 0) ? 1 : 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)(pl.tiles_m * pl.tiles_n), (unsigned)pl.splits);
-  if (pl.tn == 1) hipLaunchKernelGGL(wgrad_mfma_kernel<1>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(wgrad_mfma_kernel<2>, grid, dim3(256), 0, s, a);
-  KFN_LAUNCH_CHECK("wgrad_mfma_kernel");
+  if (d->operand_dtype == KFN_OPERAND_F16) {
+    KFN_REQUIRE(a.vec_b, "kfn_conv2d_grad_weights: fp16 operands need a 16-byte aligned dz");
+    rc = kfn::wgrad_f16_launch(a, pl, s);
+    if (rc != KFN_OK) return rc;
+  } else {
+    const dim3 grid((unsigned)(pl.tiles_m * pl.tiles_n), (unsigned)pl.splits);
+    if (pl.tn == 1) hipLaunchKernelGGL(wgrad_mfma_kernel<1>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(wgrad_mfma_kernel<2>, grid, dim3(256), 0, s, a);
+    KFN_LAUNCH_CHECK("wgrad_mfma_kernel");
+  }
   const long n = (long)(pl.Ktot + 1) * d->Cout;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(n)), dim3(256), 0, s, workspace, pl.splits, (long)pl.Ktot, d->Cout, dw, db);
   KFN_LAUNCH_CHECK("wgrad_reduce_kernel");
@@ -416,8 +418,21 @@ extern "C" int kfn_pack_conv_weights(const float* w_hwio, int kh, int kw, int Ci
   int rc = pack_dims(kh, kw, Cin, Cout, kind, &rp, &cp);
   if (rc != KFN_OK) return rc;
   const long n = (long)rp * kh * kw * cp;
-  hipLaunchKernelGGL(pack_weights_kernel, dim3(grid_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_hwio, kh,
-                     kw, Cin, Cout, kind, rp, cp, out);
+  hipLaunchKernelGGL(pack_weights_kernel<float>, dim3(grid_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_hwio,
+                     kh, kw, Cin, Cout, kind, rp, cp, out);
   KFN_LAUNCH_CHECK("pack_weights_kernel");
+  return KFN_OK;
+}
+
+extern "C" int kfn_pack_conv_weights_f16(const float* w_hwio, int kh, int kw, int Cin, int Cout, int kind, void* out_halfs,
+                                         void* stream) {
+  KFN_REQUIRE(w_hwio && out_halfs, "kfn_pack_conv_weights_f16: null argument");
+  int rp, cp;
+  int rc = pack_dims(kh, kw, Cin, Cout, kind, &rp, &cp);
+  if (rc != KFN_OK) return rc;
+  const long n = (long)rp * kh * kw * cp;
+  hipLaunchKernelGGL(pack_weights_kernel<_Float16>, dim3(grid_for(n)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), w_hwio,
+                     kh, kw, Cin, Cout, kind, rp, cp, reinterpret_cast<_Float16*>(out_halfs));
+  KFN_LAUNCH_CHECK("pack_weights_kernel<_Float16>");
   return KFN_OK;
 }

@@ -18,6 +18,12 @@ fallback: a missing entry point or an unsupported shape raises.
 Definitions that are this module's own (the reference's SCoordNet training branch is not in the snapshot):
 `global_step` counts applied updates, the learning rate of update number global_step + 1 is base_lr * gamma ** (global_step /
 stepvalue), and Adam's t is the number of updates applied since the slots were zero, + 1.
+
+precision='fp16'  runs the layers of f16_layer() on fp16 MFMA operands -- forward, weight gradient and input
+gradient; tensors, master weights and Adam's slots stay fp32 -- under dynamic loss scaling whose state lives on the device:
+the loss gradient is multiplied by the scale, the weight gradients are divided by it and checked, and kfn_adam_step_guarded
+applies the update only if every gradient is finite.  `global_step` then counts ATTEMPTED steps (it drives the learning
+rate and the batch stream; the host cannot know whether a step was applied), Adam's t counts applied ones on the device.
 """
 import ctypes as C
 import os
@@ -32,6 +38,22 @@ SCOPE = 'ScoreNet'
 BETA1, BETA2, EPSILON = 0.9, 0.999, 1e-8          # tf.train.AdamOptimizer defaults (KFNet/train.py:313)
 WEIGHTS_NAME = 'kfnet_weights-%d.npz'             # tools.io.get_snapshot's kind: SCoordNet.eval --model_folder reads it
 STATE_NAME = 'kfnet_train_state-%d.npz'           # NOT matched by get_snapshot's kfnet_weights*.npz
+PRECISIONS = ('fp32', 'fp16')
+MAX_LOSS_SCALE = 2 ** 24
+
+
+def f16_layer(kernel, cin, cout):
+    """The one statement of which layers precision='fp16' runs on fp16 operands: those whose three launches all take them.
+    kfn_conv2d_nhwc needs Cin % 32 == 0 of what it reads -- the layer's input going forward, its dZ (Cout channels) going
+    back -- and kfn_conv2d_grad_weights needs both.  That leaves out conv1a (3 input channels, its own entry points) and
+    'prediction' (4 output channels), the head that carries the log-uncertainty.  Every eligible layer's fp16 weight
+    gradient is faster than its fp32 launch, so none is routed back."""
+    return cin % 32 == 0 and cout % 32 == 0
+
+
+def power_of_two(x):
+    m, _ = np.frexp(float(x))
+    return float(x) > 0 and m == 0.5
 
 
 def learning_rate(base_lr, gamma, stepvalue, global_step):
@@ -83,6 +105,14 @@ def synthetic_labels(count, grid_hw, seed=3, start=0):
     return out
 
 
+def beta_powers(t):
+    """(beta1^t, beta2^t) as the device accumulates them: one fp64 multiplication per applied step."""
+    p1 = p2 = 1.0
+    for _ in range(int(t)):
+        p1, p2 = p1 * BETA1, p2 * BETA2
+    return p1, p2
+
+
 def snapshot_paths(folder, step):
     return os.path.join(folder, WEIGHTS_NAME % step), os.path.join(folder, STATE_NAME % step)
 
@@ -91,12 +121,13 @@ class StepStats(object):
     """What a step reports, read from the device on first access (so that steps queue): loss, l_measure, l_smooth,
     a_measure, pixels, lr.  dict(stats) gives plain floats."""
     KEYS = ('loss', 'l_measure', 'l_smooth', 'a_measure', 'pixels', 'lr')
+    SCALE_KEYS = ('loss_scale', 'skipped')      # precision='fp16' only: the scale after this step, the steps skipped so far
 
-    def __init__(self, stats_dev, lr):
-        self._dev, self._lr, self._host = stats_dev, lr, None
+    def __init__(self, stats_dev, lr, scale_dev=None):
+        self._dev, self._lr, self._host, self._scale_dev = stats_dev, lr, None, scale_dev
 
     def keys(self):
-        return list(self.KEYS)
+        return list(self.KEYS) + (list(self.SCALE_KEYS) if self._scale_dev is not None else [])
 
     def __getitem__(self, k):
         if self._host is None:
@@ -104,19 +135,33 @@ class StepStats(object):
             # kfn_coord_loss_grad's stats; valid = sum(mask) + 1, the reference logs np.sum(masks)
             self._host = dict(loss=float(s[4]), l_measure=float(s[0]), l_smooth=float(s[1]), a_measure=float(s[2]),
                               pixels=float(s[3]) - 1.0, lr=self._lr)
+            if self._scale_dev is not None:
+                st = _lib.LossScaleState.from_buffer_copy(self._scale_dev.cpu().numpy().tobytes())
+                self._host.update(loss_scale=float(st.scale), skipped=int(st.skipped))
         return self._host[k]
 
 
 class SCoordNetTrainer(object):
     def __init__(self, weights, image_size=(480, 640), batch=4, transform=None, base_lr=1e-4, gamma=0.5, stepvalue=80000,
-                 weight_decay=1e-4, loss_clip=None, smooth_weight=50.0, device='cuda:0'):
+                 weight_decay=1e-4, loss_clip=None, smooth_weight=50.0, device='cuda:0', precision='fp32', loss_scale=2 ** 15,
+                 growth_interval=2000):
         """weights: {TF name: array} holding at least ScoreNet/*.  transform: the 4x4 of transform.txt ITSELF (labels are
-        mapped by it, KFNet/train.py:279-280), None = identity.  loss_clip: None (no clip) or the reference's -2.0."""
+        mapped by it, KFNet/train.py:279-280), None = identity.  loss_clip: None (no clip) or the reference's -2.0.
+        precision: 'fp32', or 'fp16' = fp16 MFMA operands in the layers of f16_layer() under dynamic loss scaling that starts
+        at loss_scale (a power of two in 1 .. 2^24) and doubles after growth_interval applied steps without an overflow."""
         import torch
         H, Wd = image_size
         staging.check_size(H, Wd, 'the height and width of a training batch')
         if batch < 1:
             raise ValueError('batch must be >= 1')
+        if precision not in PRECISIONS:
+            raise ValueError('precision must be one of %s' % (PRECISIONS,))
+        if not (power_of_two(loss_scale) and 1 <= loss_scale <= MAX_LOSS_SCALE):
+            raise ValueError('loss_scale must be a power of two in 1 .. 2^24')
+        if growth_interval < 1:
+            raise ValueError('growth_interval must be >= 1')
+        self.precision, self.loss_scale, self.growth_interval = precision, float(loss_scale), int(growth_interval)
+        self.f16 = [precision == 'fp16' and f16_layer(k, ci, co) for _, k, ci, co, _, _ in LAYERS]
         self.lib = _lib.load()
         self.torch = torch
         self.device = torch.device(device)
@@ -163,9 +208,10 @@ class SCoordNetTrainer(object):
                 if li == 0:
                     self.packs.append(None)
                     continue
-                fwd = torch.zeros(self._pack_floats(k, ci, co, _lib.PACK_FORWARD), **f32)
+                pk = dict(f32, dtype=torch.float16) if self.f16[li] else f32     # the same layout, halfs under fp16 operands
+                fwd = torch.zeros(self._pack_floats(k, ci, co, _lib.PACK_FORWARD), **pk)
                 kind = _lib.PACK_INPUT_GRAD_S2 if s == 2 else _lib.PACK_INPUT_GRAD_S1
-                back = torch.zeros(self._pack_floats(k, ci, co, kind), **f32)
+                back = torch.zeros(self._pack_floats(k, ci, co, kind), **pk)
                 self.packs.append((fwd, back, kind))
                 d = self._fwd_desc(li)
                 nbytes = C.c_size_t()
@@ -175,6 +221,10 @@ class SCoordNetTrainer(object):
             self.workspace = torch.zeros(-(-ws_bytes // 4), **f32)
             self.stats = torch.zeros(8, **f32)
             self._packs_stale = True
+            self.scale_state = None           # kfn_loss_scale_state on the device
+            if precision == 'fp16':
+                self.scale_state = torch.zeros(C.sizeof(_lib.LossScaleState), dtype=torch.uint8, device=self.device)
+                self._write_scale_state(self.loss_scale, 0, 0, 0, 1.0, 1.0)
 
     # ---- sizes and descriptors ------------------------------------------------------------------------------------
     def _first_ws_bytes(self, n, h, w, c1):
@@ -193,7 +243,10 @@ class SCoordNetTrainer(object):
         name, k, ci, co, s, relu = LAYERS[li]
         hin, win, _, _ = self.shapes[li]
         return _lib.ConvDesc(N=self.batch, H=hin, W=win, Cin=ci, ldx=ci, Cout=co, cout_pad=-(-co // 32) * 32, ldy=co,
-                             kh=k, kw=k, stride=s, transposed=0, relu=int(relu))
+                             kh=k, kw=k, stride=s, transposed=0, relu=int(relu), operand_dtype=self._operands(li))
+
+    def _operands(self, li):
+        return _lib.OPERAND_F16 if self.f16[li] else _lib.OPERAND_F32
 
     @staticmethod
     def variable(li, kind):
@@ -231,18 +284,46 @@ class SCoordNetTrainer(object):
         layout under the variables' names."""
         return self._named(self.grads)
 
+    def _write_scale_state(self, scale, good_steps, skipped, adam_t, beta1_power, beta2_power):
+        rec = _lib.LossScaleState(beta1_power=beta1_power, beta2_power=beta2_power, scale=scale, good_steps=good_steps,
+                                  overflow=0, skipped=skipped, adam_t=adam_t)
+        self.scale_state.copy_(self.torch.from_numpy(np.frombuffer(bytes(rec), dtype=np.uint8).copy()))
+
+    def loss_scale_state(self):
+        """precision='fp16': the device's record, read back -- dict(scale, good_steps, skipped, adam_t, beta1_power,
+        beta2_power)."""
+        rec = _lib.LossScaleState.from_buffer_copy(self.scale_state.cpu().numpy().tobytes())
+        return dict(scale=float(rec.scale), good_steps=int(rec.good_steps), skipped=int(rec.skipped), adam_t=int(rec.adam_t),
+                    beta1_power=float(rec.beta1_power), beta2_power=float(rec.beta2_power))
+
     def state(self):
-        """The Adam slots and the counters, as numpy arrays (an .npz's content)."""
+        """The Adam slots and the counters, as numpy arrays (an .npz's content); with precision='fp16' the loss-scale record
+        too, whose adam_t counts the APPLIED steps."""
+        if self.precision == 'fp16':
+            ls = self.loss_scale_state()
+            self.adam_t = ls['adam_t']
         st = dict(global_step=np.int64(self.global_step), adam_t=np.int64(self.adam_t))
+        if self.precision == 'fp16':
+            st.update(loss_scale=np.float32(ls['scale']), loss_scale_good_steps=np.int64(ls['good_steps']),
+                      loss_scale_skipped=np.int64(ls['skipped']), adam_beta1_power=np.float64(ls['beta1_power']),
+                      adam_beta2_power=np.float64(ls['beta2_power']))
         st.update(self._named(self.m, 'adam_m/'))
         st.update(self._named(self.v, 'adam_v/'))
         return st
 
     def load_state(self, st):
+        """A state file written without the loss-scale record (before it existed, or by an fp32 run) loads with the
+        constructor's scale, zero counters and the powers of beta that adam_t applied steps accumulate."""
         self._fill(self.m, st, 'adam_m/')
         self._fill(self.v, st, 'adam_v/')
         self.global_step = int(st['global_step'])
         self.adam_t = int(st['adam_t'])
+        if self.precision == 'fp16':
+            if 'loss_scale' in st:
+                self._write_scale_state(float(st['loss_scale']), int(st['loss_scale_good_steps']), int(st['loss_scale_skipped']),
+                                        self.adam_t, float(st['adam_beta1_power']), float(st['adam_beta2_power']))
+            else:
+                self._write_scale_state(self.loss_scale, 0, 0, self.adam_t, *beta_powers(self.adam_t))
 
     def save(self, folder, step=None):
         """Writes kfnet_weights-<step>.npz (ScoreNet/* only) and kfnet_train_state-<step>.npz; returns the two paths."""
@@ -272,10 +353,9 @@ class SCoordNetTrainer(object):
                 continue          # conv1a's forward matrix [27][C] is the master copy
             fwd, back, kind = self.packs[li]
             w = self._ptr(self.params, li, 'kernel')
-            _lib.check(self.lib.kfn_pack_conv_weights(w, k, k, ci, co, _lib.PACK_FORWARD, fwd.data_ptr(), stream),
-                       'kfn_pack_conv_weights[%s]' % name)
-            _lib.check(self.lib.kfn_pack_conv_weights(w, k, k, ci, co, kind, back.data_ptr(), stream),
-                       'kfn_pack_conv_weights[%s, input gradient]' % name)
+            pack = self.lib.kfn_pack_conv_weights_f16 if self.f16[li] else self.lib.kfn_pack_conv_weights
+            _lib.check(pack(w, k, k, ci, co, _lib.PACK_FORWARD, fwd.data_ptr(), stream), 'kfn_pack_conv_weights[%s]' % name)
+            _lib.check(pack(w, k, k, ci, co, kind, back.data_ptr(), stream), 'kfn_pack_conv_weights[%s, input gradient]' % name)
         self._packs_stale = False
 
     def stage(self, frames_u8, labels, augment=None, stream=None):
@@ -344,7 +424,7 @@ class SCoordNetTrainer(object):
         hin, win, ho, wo = self.shapes[li]
         dz, ldz = self.dact[li], self.dact[li].shape[3]
         bd = _lib.ConvDesc(N=self.batch, H=ho, W=wo, Cin=ldz, ldx=ldz, Cout=ci, cout_pad=-(-ci // 32) * 32, ldy=ci, kh=k,
-                           kw=k, stride=s, transposed=int(s == 2), relu=0)
+                           kw=k, stride=s, transposed=int(s == 2), relu=0, operand_dtype=self._operands(li))
         _lib.check(self.lib.kfn_conv2d_nhwc(C.byref(bd), dz.data_ptr(), self.packs[li][1].data_ptr(), None,
                                             self.dact[li - 1].data_ptr(), stream), 'kfn_conv2d_nhwc[%s, input gradient]' % name)
         _lib.check(self.lib.kfn_relu_grad(self.act[li - 1].data_ptr(), ci, self.dact[li - 1].data_ptr(), ci,
@@ -372,15 +452,23 @@ class SCoordNetTrainer(object):
         _lib.check(self.lib.kfn_coord_loss_grad(C.byref(d), self.act[last].data_ptr(), self.labels.data_ptr(),
                                                 self.frames.data_ptr(), self.dact[last].data_ptr(), self.stats.data_ptr(),
                                                 stream), 'kfn_coord_loss_grad')
+        if self.precision == 'fp16':          # everything behind this point of the backward pass carries the scale
+            _lib.check(self.lib.kfn_loss_scale_apply(self.dact[last].data_ptr(), self.dact[last].numel(),
+                                                     self.scale_state.data_ptr(), stream), 'kfn_loss_scale_apply')
 
     def backward(self, stream=None):
-        """The backward pass from self.dact[-1] (the gradient with respect to the prediction) into self.grads."""
+        """The backward pass from self.dact[-1] (the gradient with respect to the prediction) into self.grads.  With
+        precision='fp16' self.dact[-1] carries the loss scale; self.grads is divided by it here and the overflow flag set, so
+        that gradients() returns plain gradients either way."""
         stream = staging.current_stream(self.device) if stream is None else stream
         last = len(LAYERS) - 1
         for li in range(last, 0, -1):
             self.weight_gradient(li, stream)
             self.input_gradient(li, stream)
         self.weight_gradient(0, stream)
+        if self.precision == 'fp16':
+            _lib.check(self.lib.kfn_loss_scale_unscale_check(self.grads.data_ptr(), self.num_floats, self.scale_state.data_ptr(),
+                                                             stream), 'kfn_loss_scale_unscale_check')
 
     def loss_and_gradients(self, label_stride, stream=None):
         """Loss on self.act[-1], then the backward pass into self.grads."""
@@ -391,6 +479,15 @@ class SCoordNetTrainer(object):
         """TensorFlow's Adam on the flat buffer, with the regulariser's weight_decay * w folded into the gradient."""
         stream = staging.current_stream(self.device) if stream is None else stream
         lr = learning_rate(self.base_lr, self.gamma, self.stepvalue, self.global_step)
+        if self.precision == 'fp16':
+            # applied or skipped, the device decides; its record supplies Adam's bias correction
+            _lib.check(self.lib.kfn_adam_step_guarded(self.params.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                                      self.grads.data_ptr(), self.num_floats, lr, BETA1, BETA2, EPSILON,
+                                                      self.weight_decay, self.growth_interval, self.scale_state.data_ptr(),
+                                                      stream), 'kfn_adam_step_guarded')
+            self.global_step += 1
+            self._packs_stale = True
+            return lr
         t = self.adam_t + 1
         _lib.check(self.lib.kfn_adam_step(self.params.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.grads.data_ptr(),
                                           self.num_floats, adam_lr_t(lr, t), BETA1, BETA2, EPSILON, self.weight_decay, stream),
@@ -414,7 +511,8 @@ class SCoordNetTrainer(object):
             stats = self.stats.clone()
             lr = self.apply_gradients(stream)
             self._repack(stream)
-        return StepStats(stats, lr)
+            scale = self.scale_state.clone() if self.precision == 'fp16' else None
+        return StepStats(stats, lr, scale)
 
 
 def restore(model_folder, verbose=True, scope=SCOPE):

@@ -3,6 +3,7 @@ frames and labels, the split of a step over its phases, and per layer the weight
 launch as fractions of the fp32 MFMA peak.
 
     python tools/mb_train.py [--height 480 --width 640 --batch 4 --steps 10 --warmup 3] [--layers] [--augment] [--depth]
+    python tools/mb_train.py --fp16 [--layers] [--rounds 5]
     python tools/mb_train.py --kfnet [--groups 1]
     python tools/mb_train.py --oflownet [--pairs 4]
     python tools/mb_train.py --joint [--groups 1]
@@ -11,6 +12,9 @@ launch as fractions of the fp32 MFMA peak.
 kfnet_amd.augment.draw(0, step) in turn (its kernels are channel_sums_kernel and augment_kernel in a kernel trace).
 --depth makes every step's labels on the device from synthetic depth maps and poses that stay there (stride 8,
 or stride 1 with --augment; depth_labels_grid_kernel / depth_labels_full_kernel in a kernel trace).
+--fp16 times the mixed-precision step beside the fp32 step in ONE process: two trainers on the same batch, timed
+in alternating rounds (median and minimum of --rounds windows of --steps steps each), the phases of both, and with --layers
+every layer's weight gradient, forward and input-gradient launch of both, as ms and TFLOP/s of the layer's nominal FLOPs.
 --kfnet times kfnet_amd.train_kfnet.KFNetTrainer instead: ms per step on --groups groups of four frames, and
 the launches it adds to stage 1's step -- the OFlowNet forward, the measurement map and the scan, the three-term loss, the
 reverse scan -- each alone and as a share of the step.
@@ -200,6 +204,73 @@ def oflownet(a):
     return 0
 
 
+def fp16(a):
+    """The fp32 and the fp16 step side by side, in alternating rounds."""
+    import torch
+    from kfnet_amd.synth import synthetic_sequence, synthetic_transform
+    from kfnet_amd.train import LAYERS, SCoordNetTrainer, synthetic_labels
+    from kfnet_amd.weights import initial_weights
+    size = (a.height, a.width)
+    trs = {p: SCoordNetTrainer(initial_weights(0), image_size=size, batch=a.batch, transform=synthetic_transform(), precision=p)
+           for p in ('fp32', 'fp16')}
+    frames = torch.from_numpy(synthetic_sequence(a.batch, a.height, a.width)).cuda()
+    labels = torch.from_numpy(synthetic_labels(a.batch, trs['fp32'].grid)).cuda()
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def rounds(fns):
+        """{name: (median, minimum)} of --rounds windows per function, the functions taking turns."""
+        t = {n: [] for n in fns}
+        for _ in range(a.rounds):
+            for n, fn in fns.items():
+                t[n].append(timed(torch, fn, a.steps))
+        return {n: (float(np.median(v)), min(v)) for n, v in t.items()}
+    for tr in trs.values():
+        for _ in range(a.warmup):
+            tr.step(frames, labels)
+    ms = rounds({p: (lambda tr=tr: tr.step(frames, labels)) for p, tr in trs.items()})
+    for p in trs:
+        print('%dx%d batch %d, %s: %.2f ms per step (median of %d windows of %d steps; fastest %.2f), %.1f frames/s' %
+              (a.height, a.width, a.batch, p, ms[p][0], a.rounds, a.steps, ms[p][1], 1e3 * a.batch / ms[p][0]))
+    print('fp16 step / fp32 step = %.3f; loss scale state after the timed steps: %s' %
+          (ms['fp16'][0] / ms['fp32'][0], trs['fp16'].loss_scale_state()))
+    stride = {p: tr.stage(frames, labels) for p, tr in trs.items()}
+    parts = {}
+    for p, tr in trs.items():
+        parts['forward ' + p] = tr.forward
+        parts['loss + backward ' + p] = lambda tr=tr, p=p: tr.loss_and_gradients(stride[p])
+        parts['packs ' + p] = lambda tr=tr: tr._repack(stream)
+    t = rounds(parts)
+    for p in trs:
+        print('%s: forward %.2f ms, loss + backward %.2f ms, packs %.2f ms' %
+              (p, t['forward ' + p][0], t['loss + backward ' + p][0], t['packs ' + p][0]))
+    if not a.layers:
+        return 0
+    print('ms (median) and TFLOP/s of the nominal 2 P k k Cin Cout, fp32 | fp16; * = the layer stays on fp32 operands')
+    print('%-11s %23s %7s | %23s %7s | %23s %7s' % ('layer', 'wgrad ms / TFLOP/s', 'x', 'forward ms / TFLOP/s', 'x',
+                                                   'input grad ms / TFLOP/s', 'x'))
+    tot = {}
+    for li in range(1, len(LAYERS)):
+        name, k, ci, co, s, relu = LAYERS[li]
+        hin, win, ho, wo = trs['fp32'].shapes[li]
+        nominal = 2.0 * a.batch * ho * wo * k * k * ci * co
+        fns = {}
+        for p, tr in trs.items():
+            fns['w' + p] = lambda tr=tr: tr.weight_gradient(li, stream)
+            fns['f' + p] = lambda tr=tr: tr.forward_layer(li, stream)
+            fns['i' + p] = lambda tr=tr: tr.input_gradient(li, stream)       # with the ReLU gradient of the layer below
+        t = rounds(fns)
+        cols = []
+        for kind in 'wfi':
+            t32, t16 = t[kind + 'fp32'][0], t[kind + 'fp16'][0]
+            tot[kind + 'fp32'] = tot.get(kind + 'fp32', 0.0) + t32
+            tot[kind + 'fp16'] = tot.get(kind + 'fp16', 0.0) + t16
+            cols.append('%6.3f/%6.1f %6.3f/%6.1f %6.2fx' % (t32, nominal / t32 / 1e9, t16, nominal / t16 / 1e9, t32 / t16))
+        print('%-11s %s' % (name + ('' if trs['fp16'].f16[li] else '*'), ' | '.join(cols)))
+    print('sums: weight gradients %.2f -> %.2f ms, forward %.2f -> %.2f ms, input gradients %.2f -> %.2f ms (conv1a apart)' %
+          (tot['wfp32'], tot['wfp16'], tot['ffp32'], tot['ffp16'], tot['ifp32'], tot['ifp16']))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--height', type=int, default=480)
@@ -215,7 +286,11 @@ def main(argv=None):
     ap.add_argument('--joint', action='store_true', help='time the joint step of KFNetTrainer (both networks trained)')
     ap.add_argument('--oflownet', action='store_true', help='time the step of OFlowNetTrainer (stage 2) and the launches it adds')
     ap.add_argument('--pairs', type=int, default=4, help='--oflownet: pairs of frames per step')
+    ap.add_argument('--fp16', action='store_true', help='time the mixed-precision step beside the fp32 step')
+    ap.add_argument('--rounds', type=int, default=5, help='--fp16: timing windows per variant, taken in turns')
     a = ap.parse_args(argv)
+    if a.fp16:
+        return fp16(a)
     if a.joint:
         return joint(a)
     if a.kfnet:
