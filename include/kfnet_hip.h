@@ -54,7 +54,8 @@ extern "C" {
  * kfn_depth_labels and kfn_label_moments (training labels from depth maps and poses), and kfn_measurement_map,
  * kfn_filter_loss_grad, kfn_filter_backward_scratch_bytes and kfn_filter_backward (fine-tuning SCoordNet through the filter),
  * and kfn_cost_volume_backward, kfn_flow_head_backward, kfn_l2norm_backward and kfn_flow_loss_grad (training OFlowNet),
- * and kfn_filter_backward_joint (joint stage 3: both networks trained through the filter). */
+ * and kfn_filter_backward_joint (joint stage 3: both networks trained through the filter), and kfn_pnp_ransac_unc and
+ * kfn_pose_filter (uncertainty-aware poses: weighted refinement, pose covariance, pose filter). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -610,6 +611,65 @@ int kfn_pnp_ransac(const kfn_pnp_desc* desc, const float* records,
  * candidates), hyp_poses [B,H,12] = [R | t] world-to-camera in fp32 (NaN: invalid), counts [B,H] inliers (-1: invalid). */
 int kfn_pnp_hypotheses(const kfn_pnp_desc* desc, const float* records, int32_t* samples, float* hyp_poses, int32_t* counts,
                        void* stream);
+
+/* ---- uncertainty-aware poses (added exports, the ABI number stays 13) -------------------------------------------------
+ * kfn_pnp_ransac_unc is kfn_pnp_ransac with the records' sigma = 1 / record[3] carried into the last stage (DESIGN.md 5c,
+ * "Uncertainty").  Candidates, sampling, P3P, scoring and selection are kfn_pnp_ransac's launches.  With camera point
+ * (x, y, z) = R X + t, residual r and 2x6 Jacobian J of the refinement above:
+ *   S   = sigma^2 A A^T + pixel_sigma^2 I,  A = [[fx/z, 0, -fx x/z^2], [0, fy/z, -fy y/z^2]]     (2x2, inverted in fp64)
+ *   weighted = 1   every iteration forms H = sum J^T S^-1 J, g = sum J^T S^-1 r, cost = sum r^T S^-1 r over the inliers of
+ *                  the current pose (the unweighted rule: Z > 0, pixel error < inlier_px), S evaluated at the current pose
+ *                  and held fixed for the iteration; a step is kept only if no inlier goes behind the camera and the cost
+ *                  over the same inliers with the same S falls
+ *   weighted = 0   the refinement is kfn_pnp_ransac's: poses and info are the same bits
+ *   cov            [B,36] = (sum J^T S^-1 J)^-1 at the final pose over the final inliers (info[:,2]), 6x6 row-major and
+ *                  symmetric to the last bit, in the coordinates (omega, tau) of the left perturbation of the
+ *                  world-to-camera pose, R <- exp(omega) R, t <- exp(omega) t + tau.  To first order this is the covariance
+ *                  of the body-frame perturbation (dtheta, drho) = -(omega, tau) of the camera-to-world pose C that `poses`
+ *                  holds, C ~ C_hat [exp(dtheta) | drho]; the camera centre's covariance in the scene frame is
+ *                  R_c2w Sigma_tau,tau R_c2w^T.  NaN where status != KFN_PNP_OK, and where fewer than 3 inliers remain or
+ *                  the Cholesky factorisation fails (the pose is still reported then).
+ *   quality        [B,2] = (sum r^T S^-1 r at the final pose, 2 * inliers - 6); NaN where status != KFN_PNP_OK
+ * cov and quality may be NULL.  min_confidence must be >= 0 (sigma positive).  Same scratch as kfn_pnp_ransac; bit-identical
+ * from launch to launch. */
+typedef struct kfn_pnp_unc_desc {
+  int32_t struct_size;     /* = sizeof(kfn_pnp_unc_desc) as the caller compiled it */
+  int32_t weighted;        /* 0: kfn_pnp_ransac's refinement; 1: weighted by S^-1 */
+  float pixel_sigma;       /* > 0; the floor that keeps S invertible as sigma -> 0 (1.0 pixel) */
+} kfn_pnp_unc_desc;
+#define KFN_PNP_UNC_DESC_INIT {(int32_t)sizeof(kfn_pnp_unc_desc), 0, 1.0f}
+int kfn_pnp_ransac_unc(const kfn_pnp_desc* desc, const kfn_pnp_unc_desc* unc, const float* records, float* poses, float* cov,
+                       float* quality, int32_t* info, void* scratch, void* stream);
+
+/* Random-walk error-state filter over a sequence of such poses, one sequence per lane, fp64, serial over t.  State: (R, p)
+ * camera-to-world and P (6x6, the body-frame coordinates (dtheta, drho) above).  flags [S,T]:
+ *   KFN_POSE_UPDATED   0   the measurement passed the gate and was fused
+ *   KFN_POSE_MISSING   1   no valid measurement (a non-finite pose or covariance, or P + Sigma_z not positive definite): the
+ *                          output is the prediction; does not count towards a reset
+ *   KFN_POSE_REJECTED  2   NIS > gate: the output is the prediction
+ *   KFN_POSE_INIT      3   the state was (re-)initialised from this measurement: the first valid one, or the max_rejects-th
+ *                          consecutive rejection
+ *   KFN_POSE_NONE      4   no estimate yet: the outputs are NaN
+ * Per frame: P <- P + diag(rot_sigma^2 I, trans_sigma^2 I); y = (log_SO3(R^T R_z), R^T (p_z - p)), S = P + Sigma_z,
+ * NIS = y^T S^-1 y (the rotation between the state's and the measurement's body frames is neglected in S);
+ * K = P S^-1, delta = K y, p <- p + R drho, then R <- R exp(dtheta), P <- (I - K) P (I - K)^T + K Sigma_z K^T.
+ * poses / out_poses [S,T,16] row-major 4x4, cov / out_cov [S,T,36], nis [S,T] (NaN where no test was made). */
+#define KFN_POSE_UPDATED 0
+#define KFN_POSE_MISSING 1
+#define KFN_POSE_REJECTED 2
+#define KFN_POSE_INIT 3
+#define KFN_POSE_NONE 4
+typedef struct kfn_pose_filter_desc {
+  int32_t struct_size;     /* = sizeof(kfn_pose_filter_desc) as the caller compiled it */
+  int32_t S, T;            /* sequences, frames per sequence */
+  float rot_sigma;         /* rad per frame (0.02), >= 0 */
+  float trans_sigma;       /* metres per frame (0.02), >= 0 */
+  float gate;              /* on the NIS; 22.46 is the 99.9 % point of chi^2 with 6 degrees of freedom; > 0 */
+  int32_t max_rejects;     /* consecutive rejections that force a re-initialisation (3); >= 1 */
+} kfn_pose_filter_desc;
+#define KFN_POSE_FILTER_DESC_INIT {(int32_t)sizeof(kfn_pose_filter_desc), 0, 0, 0.02f, 0.02f, 22.46f, 3}
+int kfn_pose_filter(const kfn_pose_filter_desc* desc, const float* poses, const float* cov, float* out_poses, float* out_cov,
+                    int32_t* flags, float* nis, void* stream);
 
 /* ---- multi-GPU: rank -> rank hand-off of the recurrent state (RCCL point-to-point) ----
  * No reference counterpart (the reference is single-device: KFNet/train.py:375 is its only

@@ -23,6 +23,7 @@ raw (untransformed, ungated) KF state fed back, NIS gate on the output only.
 When label_list.txt is present the reference's per-frame log line (losses, accuracies, median
 distance errors in cm, NIS-in-band fraction) and the final summary are printed
 (kfnet_amd/KFNet/metrics.py).  Not reproduced: --show plotting.
+`--pose_weighted` is `--pose` with the refinement weighted by the records' uncertainty; it also writes `pose_cov_<i>.txt`.
 `--pose` also solves every frame's camera pose on the device (kfnet_amd/KFNet/pnp.py) and writes `pose_<i>.txt` next to
 each `coord_<i>.npy`.
 """
@@ -129,8 +130,9 @@ def main(argv=None):
     ap.add_argument('--sharding', choices=['contiguous', 'cyclic'], default='contiguous',
                     help='multi-process runs: contiguous chunks per rank, or blocks of --block frames dealt round-robin')
     ap.add_argument('--block', type=int, default=32, help='--sharding cyclic: frames per block')
-    ap.add_argument('--pose', action='store_true', help='also write pose_<i>.txt (RANSAC-PnP on the device)')
+    modes.add_pose_flags(ap)
     a = ap.parse_args(argv)
+    pose = modes.pose_argument(a)
     rank, world, local = modes.sharded_env()
     if a.scene not in SCENES:
         print('Invalid scene:', a.scene)   # KFNet/train.py:142-144
@@ -175,9 +177,9 @@ def main(argv=None):
         with modes.rank_group(rank, world, local, state_link=True) as (dist, link):
             if a.sharding == 'cyclic':
                 parts = eval_sharded_cyclic(frames_of, T, transform, W, a.output_folder, rank, world, link, a.block, a.NIS,
-                                            pose=a.pose, **kw)
+                                            pose=pose, **kw)
             else:
-                parts = [eval_sharded(frames_of, T, transform, W, a.output_folder, rank, world, link, a.NIS, pose=a.pose,
+                parts = [eval_sharded(frames_of, T, transform, W, a.output_folder, rank, world, link, a.NIS, pose=pose,
                                       **kw)]
             if label_paths is not None or a.pose:
                 modes.report_sharded(dist, parts, T, rank, M.format_line if label_paths is not None else None, pose=a.pose)
@@ -187,7 +189,7 @@ def main(argv=None):
     out = eval(image_paths, transform, W, a.output_folder, a.NIS, frames=frames_of(0, T) if image_paths is None else None,
                device='cuda:%d' % a.gpu, **kw)
     if a.pose:
-        modes.write_poses(out[0] if label_paths is not None else out, a.output_folder)
+        modes.write_poses(out[0] if label_paths is not None else out, a.output_folder, pose=pose)
     return 0
 
 

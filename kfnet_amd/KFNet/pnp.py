@@ -5,11 +5,20 @@ a git-lfs pointer; this module is that last stage, with the reference's command-
 
     python -m kfnet_amd.KFNet.pnp <coord_file_list> <output_folder> [--gt <pose_list>] [--thread_num N]
                                   [--focal_x F --focal_y F --u U --v V] [--hypotheses 256] [--batch 64]
+                                  [--weighted] [--pixel_sigma 1.0] [--covariance]
+                                  [--smooth [--rot_sigma 0.02 --trans_sigma 0.02 --gate 22.46 --max_rejects 3
+                                             --sequence_length N]]
 
 writes one `pose_<i>.txt` (4x4 camera-to-world, the 7-Scenes `frame-*.pose.txt` format; NaN where no pose was found)
 per listed map, i = the map's position in the list.  With --gt (one pose file per map) it prints every frame's rotation
 and translation error, their medians and the share of frames within 5 cm / 5 degrees.  The geometry (cell (r, c)
 observes pixel (8c, 8r)), the candidate rule and the sampling are fixed in DESIGN.md "Camera poses".
+
+--weighted weighs the refinement by the maps' own uncertainty (channel 3 = 1/sigma) propagated to the image plane;
+--covariance writes `pose_cov_<i>.txt` (6 rows of 6: the covariance of the pose's body-frame perturbation, rotation
+first) next to each pose; --smooth runs the listed frames, cut into sequences of --sequence_length (default: one
+sequence), through the pose filter and writes `pose_smooth_<i>.txt`.  Without these flags the program does and prints
+what it always did.
 """
 import argparse
 import ctypes as C
@@ -27,12 +36,17 @@ STATUS_NAMES = {_lib.PNP_OK: 'ok', _lib.PNP_TOO_FEW_POINTS: 'too few points', _l
 class PnPSolver(object):
     """RANSAC-PnP over [B,h,w,>=4] records (x, y, z, 1/sigma) of an h x w grid.  Intrinsics default to KFNetDataSpec
     (fx = fy = 525, u = 320, v = 240).  `solve` returns camera-to-world poses [B,4,4] (NaN on failure) and info [B,4] =
-    (status, candidates, final inliers, best hypothesis): numpy in, numpy out; a CUDA tensor in, tensors out (no sync)."""
+    (status, candidates, final inliers, best hypothesis): numpy in, numpy out; a CUDA tensor in, tensors out (no sync).
+    `solve_unc` (kfn_pnp_ransac_unc) also returns every pose's 6x6 covariance and (cost, degrees of freedom); `weighted`
+    and `pixel_sigma` act on it alone."""
 
     def __init__(self, h, w, fx=525., fy=525., u=320., v=240., hypotheses=256, refine_iters=10, min_points=16, seed=0,
-                 min_confidence=20., inlier_px=10., cell_stride=8):
+                 min_confidence=20., inlier_px=10., cell_stride=8, weighted=False, pixel_sigma=1.0):
         if not 1 <= int(hypotheses) <= _lib.PNP_MAX_HYPOTHESES:
             raise ValueError('hypotheses must be in 1..%d' % _lib.PNP_MAX_HYPOTHESES)
+        if not float(pixel_sigma) > 0.0:
+            raise ValueError('pixel_sigma must be > 0')
+        self.weighted, self.pixel_sigma = bool(weighted), float(pixel_sigma)
         self.h, self.w = int(h), int(w)
         self.fx, self.fy, self.u, self.v = float(fx), float(fy), float(u), float(v)
         self.hypotheses, self.refine_iters, self.min_points = int(hypotheses), int(refine_iters), int(min_points)
@@ -76,6 +90,33 @@ class PnPSolver(object):
         if host:
             return poses.cpu().numpy(), info.cpu().numpy()
         return poses, info
+
+    def solve_unc(self, records, t0=0):
+        """kfn_pnp_ransac_unc: (poses [B,4,4], cov [B,6,6], quality [B,2] = (weighted cost, 2 * inliers - 6), info [B,4]).
+        cov is the covariance of the body-frame perturbation (dtheta, drho) of the camera-to-world pose (see
+        pose_filter.position_covariance); NaN where there is no pose.  With weighted=False, poses and info are `solve`'s
+        bit for bit.  `solve`'s contract: numpy in, numpy out; tensors in, tensors out, no sync."""
+        import torch
+        lib = _lib.load()
+        rec, host = self._device_records(records)
+        B = rec.shape[0]
+        d = self.desc(B, t0, rec.shape[3])
+        q = _lib.PnPUncDesc(weighted=int(self.weighted), pixel_sigma=self.pixel_sigma)
+        nbytes = C.c_size_t()
+        _lib.check(lib.kfn_pnp_scratch_bytes(C.byref(d), C.byref(nbytes)), 'kfn_pnp_scratch_bytes')
+        if self._scratch is None or self._scratch.numel() < nbytes.value or self._scratch.device != rec.device:
+            self._scratch = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=rec.device)
+        poses = torch.empty((B, 4, 4), dtype=torch.float32, device=rec.device)
+        cov = torch.empty((B, 6, 6), dtype=torch.float32, device=rec.device)
+        quality = torch.empty((B, 2), dtype=torch.float32, device=rec.device)
+        info = torch.empty((B, 4), dtype=torch.int32, device=rec.device)
+        stream = torch.cuda.current_stream(rec.device).cuda_stream
+        _lib.check(lib.kfn_pnp_ransac_unc(C.byref(d), C.byref(q), rec.data_ptr(), poses.data_ptr(), cov.data_ptr(),
+                                          quality.data_ptr(), info.data_ptr(), self._scratch.data_ptr(), stream),
+                   'kfn_pnp_ransac_unc')
+        if host:
+            return poses.cpu().numpy(), cov.cpu().numpy(), quality.cpu().numpy(), info.cpu().numpy()
+        return poses, cov, quality, info
 
     def hypotheses_probe(self, records, t0=0):
         """kfn_pnp_hypotheses: (samples [B,H,4], hypothesis poses [B,H,12] = [R | t] world-to-camera, counts [B,H]) as
@@ -135,6 +176,47 @@ def solve_in_batches(solver, records, batch=64, t0=0):
     return poses, info
 
 
+def solve_unc_in_batches(solver, records, batch=64, t0=0):
+    """solve_in_batches for PnPSolver.solve_unc: (poses [T,4,4], cov [T,6,6], quality [T,2], info [T,4])."""
+    T = records.shape[0]
+    poses = np.full((T, 4, 4), np.nan, np.float32)
+    cov = np.full((T, 6, 6), np.nan, np.float32)
+    quality = np.full((T, 2), np.nan, np.float32)
+    info = np.zeros((T, 4), np.int32)
+    for lo in range(0, T, batch):
+        hi = lo + batch
+        poses[lo:hi], cov[lo:hi], quality[lo:hi], info[lo:hi] = solver.solve_unc(records[lo:hi], t0=t0 + lo)
+    return poses, cov, quality, info
+
+
+def write_covariance(path, cov):
+    cov = np.asarray(cov, dtype=np.float64).reshape(6, 6)
+    with open(path, 'w') as f:
+        for row in cov:
+            f.write('\t'.join('%.9e' % x for x in row) + '\t\n')
+
+
+def read_covariance(path):
+    """A `pose_cov_<i>.txt`: 6 rows of 6."""
+    M = np.loadtxt(path, dtype=np.float64)
+    if M.shape != (6, 6):
+        raise ValueError('%s: expected a 6x6 covariance, got %s' % (path, M.shape))
+    return M
+
+
+def smooth_in_sequences(filt, poses, cov, sequence_length=0):
+    """poses [T,4,4], cov [T,6,6] cut into sequences of `sequence_length` frames (0: one sequence; the last may be
+    shorter), each filtered from a fresh state -> (poses, cov, flags [T], nis [T])."""
+    T = poses.shape[0]
+    N = T if sequence_length <= 0 else min(sequence_length, T)
+    full = (T // N) * N
+    out = [filt.run(poses[:full].reshape(-1, N, 4, 4), cov[:full].reshape(-1, N, 6, 6))]
+    out = [[x.reshape((full,) + x.shape[2:]) for x in out[0]]]
+    if full < T:
+        out.append(filt.run(poses[full:], cov[full:]))
+    return tuple(np.concatenate([o[k] for o in out]) for k in range(4))
+
+
 def summarize(rot, trans):
     """Median rotation (deg) and translation (m) errors and the share of frames within 5 cm / 5 degrees (a failed frame
     counts as outside)."""
@@ -161,7 +243,34 @@ def main(argv=None):
     ap.add_argument('--inlier_px', type=float, default=10.)
     ap.add_argument('--min_confidence', type=float, default=20.)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--weighted', action='store_true', help='weigh the refinement by the propagated uncertainty')
+    ap.add_argument('--pixel_sigma', type=float, default=None, help='pixel floor of the measurement covariance (1.0)')
+    ap.add_argument('--covariance', action='store_true', help='write pose_cov_<i>.txt next to each pose')
+    ap.add_argument('--smooth', action='store_true', help='filter the poses in time; writes pose_smooth_<i>.txt')
+    ap.add_argument('--rot_sigma', type=float, default=None, help='--smooth: rotation random walk, rad per frame (0.02)')
+    ap.add_argument('--trans_sigma', type=float, default=None, help='--smooth: translation random walk, m per frame (0.02)')
+    ap.add_argument('--gate', type=float, default=None, help='--smooth: gate on the NIS (22.46: 99.9 %% of chi^2_6)')
+    ap.add_argument('--max_rejects', type=int, default=None, help='--smooth: consecutive rejections that reset (3)')
+    ap.add_argument('--sequence_length', type=int, default=None, help='--smooth: frames per sequence (all of them)')
     a = ap.parse_args(argv)
+    uncertain = a.weighted or a.covariance or a.smooth
+    if a.pixel_sigma is not None and not uncertain:
+        ap.error('--pixel_sigma needs --weighted, --covariance or --smooth')
+    if a.pixel_sigma is not None and not a.pixel_sigma > 0.0:
+        ap.error('--pixel_sigma must be > 0')
+    for name in ('rot_sigma', 'trans_sigma', 'gate', 'max_rejects', 'sequence_length'):
+        if getattr(a, name) is not None and not a.smooth:
+            ap.error('--%s needs --smooth' % name)
+    filt = None
+    if a.smooth:
+        from .pose_filter import PoseFilter
+        if a.sequence_length is not None and a.sequence_length < 1:
+            ap.error('--sequence_length must be >= 1')
+        try:
+            filt = PoseFilter(**{k: getattr(a, k) for k in ('rot_sigma', 'trans_sigma', 'gate', 'max_rejects')
+                                 if getattr(a, k) is not None})
+        except ValueError as e:
+            ap.error('--rot_sigma / --trans_sigma / --gate / --max_rejects: %s' % e)
     paths = read_lines(a.coord_file_list)
     paths = [p for p in paths if p]
     if not paths:
@@ -182,11 +291,21 @@ def main(argv=None):
             print('%s: expected a [%d,%d,4] map, got %s' % (p, h, w, r.shape))
             return 1
     solver = PnPSolver(h, w, a.focal_x, a.focal_y, a.u, a.v, hypotheses=a.hypotheses, refine_iters=a.refine_iters,
-                       seed=a.seed, min_confidence=a.min_confidence, inlier_px=a.inlier_px)
-    poses, info = solve_in_batches(solver, np.stack(records), max(1, a.batch))
+                       seed=a.seed, min_confidence=a.min_confidence, inlier_px=a.inlier_px, weighted=a.weighted,
+                       pixel_sigma=1.0 if a.pixel_sigma is None else a.pixel_sigma)
+    if uncertain:
+        poses, cov, _, info = solve_unc_in_batches(solver, np.stack(records), max(1, a.batch))
+    else:
+        poses, info = solve_in_batches(solver, np.stack(records), max(1, a.batch))
     os.makedirs(a.output_folder, exist_ok=True)
     for i in range(len(paths)):
         write_pose(os.path.join(a.output_folder, 'pose_%d.txt' % i), poses[i])
+        if a.covariance:
+            write_covariance(os.path.join(a.output_folder, 'pose_cov_%d.txt' % i), cov[i])
+    if filt is not None:
+        smooth, _, flags, _ = smooth_in_sequences(filt, poses, cov, a.sequence_length or 0)
+        for i in range(len(paths)):
+            write_pose(os.path.join(a.output_folder, 'pose_smooth_%d.txt' % i), smooth[i])
     failed = int((info[:, 0] != _lib.PNP_OK).sum())
     print('%d poses written to %s (%d frames without a pose)' % (len(paths), a.output_folder, failed))
     if gt_paths is not None:
@@ -198,6 +317,15 @@ def main(argv=None):
         mr, mt, within = summarize(rot, trans)
         print('median rotation error: %.4f deg, median translation error: %.4f m, within 5cm/5deg: %.1f %%'
               % (mr, mt, 100.0 * within))
+        if filt is not None:
+            from .pose_filter import FLAG_NAMES
+            rot, trans = pose_errors(smooth, gt)
+            for i in range(len(paths)):
+                print('smoothed frame %d: %s, rotation error %.4f deg, translation error %.4f m'
+                      % (i, FLAG_NAMES.get(int(flags[i]), '?'), rot[i], trans[i]))
+            mr, mt, within = summarize(rot, trans)
+            print('smoothed: median rotation error: %.4f deg, median translation error: %.4f m, within 5cm/5deg: %.1f %%'
+                  % (mr, mt, 100.0 * within))
     return 0
 
 

@@ -7,7 +7,8 @@ I holds image_list.txt (+ optional label_list.txt) and transform.txt; for every 
 the record KFNet writes on a reset frame (kfn_coord_records).  Only SCoordNet runs (kfnet_amd.engine.SCoordNetEngine); the
 model folder's newest snapshot (a TF checkpoint model.ckpt-<step> or a kfnet_weights*.npz) may hold just the ScoreNet/*
 scope.  `--synthetic T` / `--random_weights` replace the images / the checkpoint; `--pose` also writes pose_<i>.txt
-(modes.write_poses).
+(modes.write_poses); `--pose_weighted` is --pose with the refinement weighted by the records' uncertainty, and also writes
+pose_cov_<i>.txt.
 With label_list.txt every frame's median distance error d_m (cm) is printed, then the median / mean / stddev over d_m.
 
 Under `python -m torch.distributed.run --nproc-per-node N -m kfnet_amd.SCoordNet.eval ...` every rank processes a
@@ -66,12 +67,13 @@ def build_parser():
     ap.add_argument('--model_folder', default='')
     ap.add_argument('--scene', default='')
     modes.add_project_flags(ap)
-    ap.add_argument('--pose', action='store_true', help='also write pose_<i>.txt (RANSAC-PnP on the device)')
+    modes.add_pose_flags(ap)
     return ap
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
+    pose = modes.pose_argument(a)
     rank, world, local = modes.sharded_env()
     if a.scene not in modes.SCENES:
         print('Invalid scene:', a.scene)
@@ -103,16 +105,16 @@ def main(argv=None):
         if rank == 0:
             modes.print_banner(T, a.scene)
     if world > 1:
-        return _main_sharded(a, W, size, rank, world, local, T, transform, frames_of, label_paths)
+        return _main_sharded(a, W, size, rank, world, local, T, transform, frames_of, label_paths, pose)
     torch.cuda.set_device(a.gpu)
     out = eval(paths, transform, W, a.output_folder, image_size=size, batch=a.batch,
                frames=frames_of(0, T) if paths is None else None, label_paths=label_paths, device='cuda:%d' % a.gpu)
     if a.pose:
-        modes.write_poses(out[0] if label_paths is not None else out, a.output_folder)
+        modes.write_poses(out[0] if label_paths is not None else out, a.output_folder, pose=pose)
     return 0
 
 
-def _main_sharded(a, W, size, rank, world, local, T, transform, frames_of, label_paths):
+def _main_sharded(a, W, size, rank, world, local, T, transform, frames_of, label_paths, pose=False):
     """One rank of torch.distributed.run: its contiguous chunk through modes.run_shard.  No rank talks to another unless
     labels or --pose ask for the per-frame results on rank 0: only then is a process group started (modes.rank_group)."""
     import torch
@@ -121,7 +123,7 @@ def _main_sharded(a, W, size, rank, world, local, T, transform, frames_of, label
 
     def run():
         eng = _engine(W, transform, size, a.batch, max(hi - lo, 1), label_paths is not None, None)
-        outs = modes.chunk_outputs(eng, T, a.output_folder, label_paths, modes.diagonal_pairs, a.pose)
+        outs = modes.chunk_outputs(eng, T, a.output_folder, label_paths, modes.diagonal_pairs, pose)
         return modes.run_shard(eng, frames_of, T, rank, world, a.output_folder, 'coord', outputs=outs)
 
     if label_paths is None and not a.pose:

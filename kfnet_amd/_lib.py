@@ -25,6 +25,7 @@ WINO_FORM_S2_EIGHT_WAVE = 4                                # ... for kfn_conv2d_
 WINO_FORM_S2_F42 = 5                                       # ... its polyphase + F(4,2) form (wino_s2c_kernel)
 PNP_OK, PNP_TOO_FEW_POINTS, PNP_NO_HYPOTHESIS = 0, 1, 2      # kfn_pnp_ransac info[:, 0] (KFN_PNP_*)
 PNP_MAX_HYPOTHESES = 1024
+POSE_UPDATED, POSE_MISSING, POSE_REJECTED, POSE_INIT, POSE_NONE = 0, 1, 2, 3, 4     # kfn_pose_filter flags (KFN_POSE_*)
 PACK_FORWARD, PACK_INPUT_GRAD_S1, PACK_INPUT_GRAD_S2 = 0, 1, 2     # kfn_pack_conv_weights kind (KFN_PACK_*)
 CFG_AUTO, CFG_160x128, CFG_128x128, CFG_128x64, CFG_128x32, CFG_64x64, CFG_256x32, CFG_192x64 = 0, 1, 2, 3, 4, 5, 6, 7
 
@@ -66,6 +67,17 @@ class PnPDesc(SizedStructure):
                 ('t0', C.c_int32), ('seed', C.c_uint32), ('hypotheses', C.c_int32), ('refine_iters', C.c_int32),
                 ('min_points', C.c_int32), ('fx', C.c_float), ('fy', C.c_float), ('u', C.c_float), ('v', C.c_float),
                 ('cell_stride', C.c_int32), ('min_confidence', C.c_float), ('inlier_px', C.c_float)]
+
+
+class PnPUncDesc(SizedStructure):
+    """kfn_pnp_unc_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
+    _fields_ = [('struct_size', C.c_int32), ('weighted', C.c_int32), ('pixel_sigma', C.c_float)]
+
+
+class PoseFilterDesc(SizedStructure):
+    """kfn_pose_filter_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
+    _fields_ = [('struct_size', C.c_int32), ('S', C.c_int32), ('T', C.c_int32), ('rot_sigma', C.c_float),
+                ('trans_sigma', C.c_float), ('gate', C.c_float), ('max_rejects', C.c_int32)]
 
 
 class CoordLossDesc(SizedStructure):
@@ -237,6 +249,9 @@ SYMBOLS = {
     'kfn_loss_scale_unscale_check': (_i, [_vp, C.c_long, _vp, _vp]),
     'kfn_adam_step_guarded': (_i, [_vp, _vp, _vp, _vp, C.c_long, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _i,
                                _vp, _vp]),
+    # uncertainty-aware poses: weighted refinement, pose covariance, pose filter (added exports, ABI 13)
+    'kfn_pnp_ransac_unc': (_i, [C.POINTER(PnPDesc), C.POINTER(PnPUncDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'kfn_pose_filter': (_i, [C.POINTER(PoseFilterDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -41,6 +41,8 @@ EXTRA = {
     'kfn_train_flow.hip': ['-ffp-contract=off'],
     # the guarded Adam step repeats kfn_train_loss.hip's fp64 arithmetic, which a numpy restatement follows bit for bit
     'kfn_loss_scale.hip': ['-ffp-contract=off'],
+    # the pose filter: a serial fp64 recursion per sequence, rounded product by product as its numpy restatement, like the scan
+    'kfn_pose_filter.hip': ['-ffp-contract=off'],
 }
 
 

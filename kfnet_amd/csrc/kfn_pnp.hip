@@ -14,6 +14,8 @@
 //   3. pnp_refine_kernel  one workgroup per frame: the best hypothesis (ties to the lowest index), then Gauss-Newton on the
 //                         pixel error over the inliers of the current pose, normal equations in fp64 reduced in a fixed
 //                         order (per-lane strided sums, a butterfly per wave, the four waves in order).
+//      pnp_refine_unc_kernel   its sibling behind kfn_pnp_ransac_unc: optionally weighted by the records' sigma propagated
+//                         to the image plane; also writes the pose's 6x6 covariance and (cost, degrees of freedom).
 // No host round trip between the stages, no device RNG state, no float atomics: the result is the same bits on every launch.
 #include <cmath>
 
@@ -538,6 +540,298 @@ __global__ __launch_bounds__(NT) void pnp_refine_kernel(PnPArgs a, const float* 
   }
 }
 
+// ---- uncertainty (kfn_pnp_ransac_unc): the records' sigma propagated to the image plane ---------------------------------
+// S = sigma^2 A A^T + pixel_sigma^2 I with A = d(pixel)/d(camera point) at xc; W = S^-1 by the closed form of the symmetric
+// 2x2 inverse.  sig2 = sigma^2 = 1 / record[3]^2, ps2 = pixel_sigma^2.
+struct Weight2 { double w00, w01, w11; };
+
+__device__ __forceinline__ Weight2 measurement_weight(double fx, double fy, const double* xc, double sig2, double ps2) {
+  const double iz = 1.0 / xc[2];
+  const double a0 = fx * iz, a2 = -fx * xc[0] * iz * iz, b1 = fy * iz, b2 = -fy * xc[1] * iz * iz;
+  const double s00 = sig2 * (a0 * a0 + a2 * a2) + ps2, s01 = sig2 * (a2 * b2), s11 = sig2 * (b1 * b1 + b2 * b2) + ps2;
+  const double id = 1.0 / (s00 * s11 - s01 * s01);
+  return Weight2{s11 * id, -s01 * id, s00 * id};
+}
+
+__device__ __forceinline__ double sigma2_of(const PnPArgs& a, const float* r, int cell) {
+  const double c = (double)r[(size_t)cell * a.ld + 3];
+  return 1.0 / (c * c);
+}
+
+// One inlier's terms of the weighted normal equations at `pose` (Z > 0 there: the caller's inlier test):
+// acc[0..20] += upper triangle of J^T W J, acc[21..26] += J^T W r, acc[27] += r^T W r, acc[28] += 1.
+__device__ __forceinline__ void weighted_terms(const PnPArgs& a, const double* pose, const double* X, const double* px,
+                                               double sig2, double ps2, double* acc) {
+  const double fx = a.fx, fy = a.fy;
+  double xc[3];
+  to_camera(pose, pose + 9, X, xc);
+  const double iz = 1.0 / xc[2];
+  const double ru = fx * xc[0] * iz - (px[0] - a.u), rv = fy * xc[1] * iz - (px[1] - a.v);
+  const double a0 = fx * iz, a2 = -fx * xc[0] * iz * iz, b1 = fy * iz, b2 = -fy * xc[1] * iz * iz;
+  const double Ju[6] = {a2 * xc[1], a0 * xc[2] - a2 * xc[0], -a0 * xc[1], a0, 0.0, a2};
+  const double Jv[6] = {-b1 * xc[2] + b2 * xc[1], -b2 * xc[0], b1 * xc[0], 0.0, b1, b2};
+  const Weight2 W = measurement_weight(fx, fy, xc, sig2, ps2);
+  double Wu[6], Wv[6];   // rows of W J
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    Wu[i] = W.w00 * Ju[i] + W.w01 * Jv[i];
+    Wv[i] = W.w01 * Ju[i] + W.w11 * Jv[i];
+  }
+  int q = 0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int k = i; k < 6; ++k) acc[q++] += Wu[i] * Ju[k] + Wv[i] * Jv[k];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) acc[21 + i] += Wu[i] * ru + Wv[i] * rv;
+  acc[27] += (W.w00 * ru * ru + 2.0 * W.w01 * ru * rv) + W.w11 * rv * rv;
+  acc[28] += 1.0;
+}
+
+// Sigma = H^-1 from the Cholesky factor of the 6x6 H whose upper triangle is h[0..20] (row by row): L^-1 by forward
+// substitution, Sigma = L^-T L^-1 with the upper triangle computed and mirrored, so Sigma is symmetric to the last bit.
+// Returns false (Sigma untouched) if H is not positive definite.
+__device__ bool inverse_spd6(const double* h, double (*Sg)[6]) {
+  double L[6][6], Li[6][6];
+  int q = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int k = i; k < 6; ++k) { L[k][i] = h[q]; L[i][k] = h[q]; ++q; }
+  for (int j = 0; j < 6; ++j) {
+    double s = L[j][j];
+    for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
+    if (!(s > 0.0)) return false;
+    L[j][j] = sqrt(s);
+    for (int i = j + 1; i < 6; ++i) {
+      double t = L[i][j];
+      for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k];
+      L[i][j] = t / L[j][j];
+    }
+  }
+  for (int j = 0; j < 6; ++j) {
+    Li[j][j] = 1.0 / L[j][j];
+    for (int i = j + 1; i < 6; ++i) {
+      double s = 0.0;
+      for (int k = j; k < i; ++k) s -= L[i][k] * Li[k][j];
+      Li[i][j] = s / L[i][i];
+    }
+  }
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) {
+      double s = 0.0;
+      for (int k = j; k < 6; ++k) s += Li[k][i] * Li[k][j];
+      Sg[i][j] = s;
+      Sg[j][i] = s;
+    }
+  return true;
+}
+
+// pnp_refine_kernel's sibling behind kfn_pnp_ransac_unc: the same grid, LDS, selection and loop; it also writes cov [B,36]
+// and quality [B,2] (either may be null), and WEIGHTED weighs every inlier's residual by S^-1 (above) in the normal
+// equations and in both costs.  <false> repeats pnp_refine_kernel's arithmetic statement for statement: the same bits in
+// poses and info.  A sibling, not a template over both: pnp_refine_kernel is left as it was compiled before.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(NT) void pnp_refine_unc_kernel(PnPArgs a, double ps2, const float* __restrict__ hp,
+                                                            const int* __restrict__ counts, float* __restrict__ poses,
+                                                            float* __restrict__ cov, float* __restrict__ quality,
+                                                            int* __restrict__ info) {
+  extern __shared__ unsigned short list[];
+  __shared__ int wave_tot[NT / 64];
+  __shared__ int best_c[NT / 64], best_k[NT / 64];
+  __shared__ double red[4 * NV];
+  __shared__ double sums[NV];
+  __shared__ double pose[12], cand[12];   // R row-major, t
+  __shared__ int stop;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int b = blockIdx.x;
+  const float* r = a.rec + (size_t)b * a.h * a.w * a.ld;
+  const int n = build_candidates(a, r, list, wave_tot);
+  const double fx = a.fx, fy = a.fy, thr2 = (double)a.thr * (double)a.thr;
+
+  // selection: most inliers, ties to the lowest index
+  int bc = -1, bk = -1;
+  for (int k = tid; k < a.H; k += NT) {
+    const int c = counts[(size_t)b * a.H + k];
+    if (c > bc) { bc = c; bk = k; }            // k ascends: a later equal count never wins
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const int oc = __shfl_xor(bc, o), ok = __shfl_xor(bk, o);
+    if (oc > bc || (oc == bc && ok >= 0 && (bk < 0 || ok < bk))) { bc = oc; bk = ok; }
+  }
+  if (lane == 0) { best_c[wv] = bc; best_k[wv] = bk; }
+  __syncthreads();
+  if (tid == 0) {
+    int c = best_c[0], k = best_k[0];
+    for (int w = 1; w < NT / 64; ++w)
+      if (best_c[w] > c || (best_c[w] == c && best_k[w] >= 0 && (k < 0 || best_k[w] < k))) { c = best_c[w]; k = best_k[w]; }
+    best_c[0] = c;
+    best_k[0] = k;
+  }
+  __syncthreads();
+  const int best = best_k[0], best_count = best_c[0];
+  const int status = n < a.min_points ? KFN_PNP_TOO_FEW_POINTS : (best_count < 0 ? KFN_PNP_NO_HYPOTHESIS : KFN_PNP_OK);
+  if (status != KFN_PNP_OK) {
+    if (tid < 16) poses[(size_t)b * 16 + tid] = __builtin_nanf("");
+    if (tid == 0) {
+      info[b * 4 + 0] = status; info[b * 4 + 1] = n; info[b * 4 + 2] = 0; info[b * 4 + 3] = -1;
+    }
+    if (cov && tid < 36) cov[(size_t)b * 36 + tid] = __builtin_nanf("");
+    if (quality && tid < 2) quality[(size_t)b * 2 + tid] = __builtin_nanf("");
+    return;
+  }
+  if (tid < 12) {
+    const float* o = hp + ((size_t)b * a.H + best) * 12;
+    pose[tid] = (double)o[(tid < 9) ? (tid / 3) * 4 + tid % 3 : (tid - 9) * 4 + 3];
+  }
+  if (tid == 0) stop = 0;
+  __syncthreads();
+
+  for (int it = 0; it < a.iters; ++it) {
+    // normal equations over the inliers of the current pose
+    double acc[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) acc[i] = 0.0;
+    for (int j = tid; j < n; j += NT) {
+      double X[3], px[2], xc[3];
+      load_point(a, r, list[j], X, px);
+      to_camera(pose, pose + 9, X, xc);
+      if (!(xc[2] > 0.0)) continue;
+      const double iz = 1.0 / xc[2];
+      const double ru = fx * xc[0] * iz - (px[0] - a.u), rv = fy * xc[1] * iz - (px[1] - a.v);
+      if (!(ru * ru + rv * rv < thr2)) continue;
+      if constexpr (WEIGHTED) {
+        weighted_terms(a, pose, X, px, sigma2_of(a, r, list[j]), ps2, acc);
+        continue;
+      }
+      const double a0 = fx * iz, a2 = -fx * xc[0] * iz * iz, b1 = fy * iz, b2 = -fy * xc[1] * iz * iz;
+      const double Ju[6] = {a2 * xc[1], a0 * xc[2] - a2 * xc[0], -a0 * xc[1], a0, 0.0, a2};
+      const double Jv[6] = {-b1 * xc[2] + b2 * xc[1], -b2 * xc[0], b1 * xc[0], 0.0, b1, b2};
+      int q = 0;
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int k = i; k < 6; ++k) acc[q++] += Ju[i] * Ju[k] + Jv[i] * Jv[k];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) acc[21 + i] += Ju[i] * ru + Jv[i] * rv;
+      acc[27] += ru * ru + rv * rv;
+      acc[28] += 1.0;
+    }
+    block_sum(acc, red, sums);
+    if (tid == 0) {
+      // Cholesky of the 6x6 system, solve H d = -g, candidate pose exp(w) R, exp(w) t + tau
+      double L[6][6], g[6], d[6];
+      int q = 0;
+      for (int i = 0; i < 6; ++i)
+        for (int k = i; k < 6; ++k) { L[k][i] = sums[q]; L[i][k] = sums[q]; ++q; }
+      for (int i = 0; i < 6; ++i) g[i] = sums[21 + i];
+      bool pd = sums[28] >= 3.0;
+      for (int j = 0; j < 6 && pd; ++j) {
+        double s = L[j][j];
+        for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
+        if (!(s > 0.0)) { pd = false; break; }
+        L[j][j] = sqrt(s);
+        for (int i = j + 1; i < 6; ++i) {
+          double t = L[i][j];
+          for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k];
+          L[i][j] = t / L[j][j];
+        }
+      }
+      if (!pd) {
+        stop = 1;
+      } else {
+        double y[6];
+        for (int i = 0; i < 6; ++i) {
+          double s = -g[i];
+          for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
+          y[i] = s / L[i][i];
+        }
+        for (int i = 5; i >= 0; --i) {
+          double s = y[i];
+          for (int k = i + 1; k < 6; ++k) s -= L[k][i] * d[k];
+          d[i] = s / L[i][i];
+        }
+        const double th = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        const double K[9] = {0.0, -d[2], d[1], d[2], 0.0, -d[0], -d[1], d[0], 0.0};
+        double KK[9], E[9];
+        for (int rr = 0; rr < 3; ++rr)
+          for (int c = 0; c < 3; ++c)
+            KK[rr * 3 + c] = K[rr * 3 + 0] * K[0 * 3 + c] + K[rr * 3 + 1] * K[1 * 3 + c] + K[rr * 3 + 2] * K[2 * 3 + c];
+        const double s1 = th < 1e-12 ? 1.0 : sin(th) / th;
+        const double s2 = th < 1e-12 ? 0.0 : (1.0 - cos(th)) / (th * th);
+        for (int i = 0; i < 9; ++i) E[i] = ((i % 4 == 0) ? 1.0 : 0.0) + s1 * K[i] + s2 * KK[i];
+        for (int rr = 0; rr < 3; ++rr) {
+          for (int c = 0; c < 3; ++c)
+            cand[rr * 3 + c] = E[rr * 3 + 0] * pose[0 * 3 + c] + E[rr * 3 + 1] * pose[1 * 3 + c] + E[rr * 3 + 2] * pose[2 * 3 + c];
+          cand[9 + rr] = (E[rr * 3 + 0] * pose[9] + E[rr * 3 + 1] * pose[10] + E[rr * 3 + 2] * pose[11]) + d[3 + rr];
+        }
+      }
+    }
+    __syncthreads();
+    if (stop) break;
+    // cost of the candidate over the same inlier set
+    double c2[2] = {0.0, 0.0};   // cost, points behind the camera
+    for (int j = tid; j < n; j += NT) {
+      double X[3], px[2], xc[3];
+      load_point(a, r, list[j], X, px);
+      if (!inlier_of(a, pose, pose + 9, X, px, thr2)) continue;
+      to_camera(cand, cand + 9, X, xc);
+      if (!(xc[2] > 0.0)) { c2[1] += 1.0; continue; }
+      const double ru = fx * xc[0] / xc[2] - (px[0] - a.u), rv = fy * xc[1] / xc[2] - (px[1] - a.v);
+      if constexpr (WEIGHTED) {   // S stays the one of the current pose
+        double xp[3];
+        to_camera(pose, pose + 9, X, xp);
+        const Weight2 W = measurement_weight(fx, fy, xp, sigma2_of(a, r, list[j]), ps2);
+        c2[0] += (W.w00 * ru * ru + 2.0 * W.w01 * ru * rv) + W.w11 * rv * rv;
+        continue;
+      }
+      c2[0] += ru * ru + rv * rv;
+    }
+    block_sum(c2, red, sums + 21);   // (sums[21..22]: g is no longer needed; sums[27] still holds the cost)
+    if (tid == 0) {
+      if (sums[22] == 0.0 && sums[21] < sums[27]) {
+        for (int i = 0; i < 12; ++i) pose[i] = cand[i];
+      } else {
+        stop = 1;
+      }
+    }
+    __syncthreads();
+    if (stop) break;
+  }
+
+  // final inliers (pnp_refine_kernel's count, by its rule) and their weighted normal equations at the final pose:
+  // Sigma = H^-1, quality = (cost, 2 * inliers - 6); camera-to-world [R^T | -R^T t]
+  double acc[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) acc[i] = 0.0;
+  for (int j = tid; j < n; j += NT) {
+    double X[3], px[2];
+    load_point(a, r, list[j], X, px);
+    if (inlier_of(a, pose, pose + 9, X, px, thr2)) weighted_terms(a, pose, X, px, sigma2_of(a, r, list[j]), ps2, acc);
+  }
+  block_sum(acc, red, sums);
+  const int inliers = (int)sums[28];
+  if (tid == 0) {
+    double Sg[6][6];
+    const bool pd = inliers >= 3 && inverse_spd6(sums, Sg);
+    if (cov)
+      for (int i = 0; i < 36; ++i) cov[(size_t)b * 36 + i] = pd ? (float)Sg[i / 6][i % 6] : __builtin_nanf("");
+    if (quality) {
+      quality[(size_t)b * 2 + 0] = (float)sums[27];
+      quality[(size_t)b * 2 + 1] = (float)(2 * inliers - 6);
+    }
+  }
+  if (tid < 16) {
+    const int rr = tid / 4, c = tid % 4;
+    double val;
+    if (rr == 3) val = (c == 3) ? 1.0 : 0.0;
+    else if (c < 3) val = pose[c * 3 + rr];
+    else val = -(pose[0 * 3 + rr] * pose[9] + pose[1 * 3 + rr] * pose[10] + pose[2 * 3 + rr] * pose[11]);
+    poses[(size_t)b * 16 + tid] = (float)val;
+  }
+  if (tid == 0) {
+    info[b * 4 + 0] = KFN_PNP_OK; info[b * 4 + 1] = n; info[b * 4 + 2] = inliers; info[b * 4 + 3] = best;
+  }
+}
+
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Copy of the caller's descriptor (struct_size bytes, the rest 0) and the argument checks shared by the entry points.
@@ -621,6 +915,45 @@ extern "C" int kfn_pnp_ransac(const kfn_pnp_desc* desc, const float* records, fl
   hipLaunchKernelGGL(pnp_refine_kernel, dim3((unsigned)d.B), dim3(NT), 2 * d.h * d.w, st, a, (const float*)hp,
                      (const int*)counts, poses, info);
   KFN_LAUNCH_CHECK("pnp_refine_kernel");
+  return KFN_OK;
+}
+
+extern "C" int kfn_pnp_ransac_unc(const kfn_pnp_desc* desc, const kfn_pnp_unc_desc* unc, const float* records, float* poses,
+                                  float* cov, float* quality, int32_t* info, void* scratch, void* stream) {
+  kfn_pnp_desc d;
+  int rc = pnp_desc_in(desc, &d, "kfn_pnp_ransac_unc");
+  if (rc != KFN_OK) return rc;
+  if (unc == nullptr) return kfn::fail(KFN_ERR_ARG, "kfn_pnp_ransac_unc: null kfn_pnp_unc_desc");
+  if (unc->struct_size < (int32_t)sizeof(kfn_pnp_unc_desc) || (unc->struct_size & 3) != 0)
+    return kfn::fail(KFN_ERR_ARG, "kfn_pnp_ransac_unc: kfn_pnp_unc_desc.struct_size = %d (this library: %d bytes) -- use "
+                     "KFN_PNP_UNC_DESC_INIT", (int)unc->struct_size, (int)sizeof(kfn_pnp_unc_desc));
+  const kfn_pnp_unc_desc q = *unc;
+  KFN_REQUIRE(q.weighted == 0 || q.weighted == 1, "kfn_pnp_ransac_unc: weighted = %d (0 or 1)", q.weighted);
+  KFN_REQUIRE(q.pixel_sigma > 0.f && std::isfinite(q.pixel_sigma), "kfn_pnp_ransac_unc: pixel_sigma = %g, must be > 0",
+              (double)q.pixel_sigma);
+  KFN_REQUIRE(d.min_confidence >= 0.f, "kfn_pnp_ransac_unc: min_confidence = %g < 0 (sigma = 1 / confidence must be positive)",
+              (double)d.min_confidence);
+  KFN_REQUIRE(records && poses && info && scratch, "kfn_pnp_ransac_unc: null argument");
+  KFN_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "kfn_pnp_ransac_unc: scratch not 16-byte aligned");
+  const PnPArgs a = pnp_args(&d, records);
+  const size_t bh = (size_t)d.B * d.hypotheses;
+  float* hp = static_cast<float*>(scratch);
+  int* counts = reinterpret_cast<int*>(static_cast<char*>(scratch) + align256(bh * 12 * sizeof(float)));
+  const hipStream_t st = (hipStream_t)stream;
+  rc = launch_hyp_and_score(a, nullptr, hp, counts, st);
+  if (rc != KFN_OK) return rc;
+  static std::atomic<uint64_t> lds_done[2];
+  const void* kernel = q.weighted ? (const void*)pnp_refine_unc_kernel<true> : (const void*)pnp_refine_unc_kernel<false>;
+  rc = kfn::set_max_dynamic_lds(kernel, 2 * MAX_CELLS, lds_done[q.weighted]);
+  if (rc != KFN_OK) return rc;
+  const double ps2 = (double)q.pixel_sigma * (double)q.pixel_sigma;
+  if (q.weighted)
+    hipLaunchKernelGGL(pnp_refine_unc_kernel<true>, dim3((unsigned)d.B), dim3(NT), 2 * d.h * d.w, st, a, ps2, (const float*)hp,
+                       (const int*)counts, poses, cov, quality, info);
+  else
+    hipLaunchKernelGGL(pnp_refine_unc_kernel<false>, dim3((unsigned)d.B), dim3(NT), 2 * d.h * d.w, st, a, ps2,
+                       (const float*)hp, (const int*)counts, poses, cov, quality, info);
+  KFN_LAUNCH_CHECK("pnp_refine_unc_kernel");
   return KFN_OK;
 }
 

@@ -6,6 +6,9 @@ warm-up) and prints one JSON line with frames/s per engine and batch.
 Every engine is built with random weights and max_chunk = --frames; a timed repetition is one process() of the whole
 resident chunk (KFNetEngine: heavy phase on two streams + the Kalman scan; the single-network engines: their network +
 the record launch).  Several --batch values show where an engine stops scaling with the batch.
+
+`--engines pose` times the pose stage instead: ms per PnPSolver.solve of --frames records on a 60x80 grid (20 % outliers,
+per-cell sigma 0.5-4 cm) against solve_unc unweighted and weighted, in the same JSON line under "pose_ms".
 """
 import argparse
 import json
@@ -13,6 +16,38 @@ import os
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+
+
+def time_pose_stage(frames, reps, warmup, h=60, w=80):
+    """ms per call of solve / solve_unc (weighted 0, 1) on `frames` synthetic 60x80 records resident on the device."""
+    import numpy as np
+    import torch
+    from kfnet_amd.KFNet.pnp import PnPSolver
+    rng = np.random.default_rng(0)
+    rr, cc = np.meshgrid(np.arange(h), np.arange(w), indexing='ij')
+    z = rng.uniform(0.5, 5.0, size=(frames, h, w))
+    rec = np.stack([(cc * 8 - 320.) / 525. * z, (rr * 8 - 240.) / 525. * z, z, z], axis=-1)     # camera = scene frame
+    sigma = np.exp(rng.uniform(np.log(0.005), np.log(0.04), size=(frames, h, w)))
+    rec[..., :3] += rng.normal(size=rec[..., :3].shape) * sigma[..., None]
+    out = rng.random((frames, h, w)) < 0.2
+    rec[..., :3][out] = rng.uniform(-5, 5, size=(int(out.sum()), 3))
+    rec[..., 3] = 1.0 / sigma
+    dev = torch.from_numpy(rec.astype(np.float32)).cuda()
+    calls = {'solve': PnPSolver(h, w).solve, 'solve_unc': PnPSolver(h, w).solve_unc,
+             'solve_unc_weighted': PnPSolver(h, w, weighted=True).solve_unc}
+    ms = {}
+    for name, call in calls.items():
+        for _ in range(max(warmup, 1)):
+            call(dev)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            call(dev)
+        e1.record()
+        e1.synchronize()
+        ms[name] = round(e0.elapsed_time(e1) / reps, 3)
+    return ms
 
 
 def main():
@@ -40,6 +75,9 @@ def main():
         'kfnet': lambda B: KFNetEngine(W, image_size=size, batch=B, transform=T4, max_chunk=a.frames),
     }
     out = {'frames': a.frames, 'image': list(size), 'reps': a.reps, 'fps': {}}
+    if 'pose' in a.engines:
+        a.engines.remove('pose')
+        out['pose_ms'] = time_pose_stage(a.frames, a.reps, a.warmup)
     for name in a.engines:
         out['fps'][name] = {}
         for B in a.batch:
