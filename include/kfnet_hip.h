@@ -55,7 +55,8 @@ extern "C" {
  * kfn_filter_loss_grad, kfn_filter_backward_scratch_bytes and kfn_filter_backward (fine-tuning SCoordNet through the filter),
  * and kfn_cost_volume_backward, kfn_flow_head_backward, kfn_l2norm_backward and kfn_flow_loss_grad (training OFlowNet),
  * and kfn_filter_backward_joint (joint stage 3: both networks trained through the filter), and kfn_pnp_ransac_unc and
- * kfn_pose_filter (uncertainty-aware poses: weighted refinement, pose covariance, pose filter). */
+ * kfn_pose_filter (uncertainty-aware poses: weighted refinement, pose covariance, pose filter), and kfn_reproj_loss_grad
+ * and kfn_augment_pixel_map (the reprojection loss of KFNet/KFNet.py:405-428 for stages 1 and 3). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -863,6 +864,57 @@ typedef struct kfn_augment_desc {
 } kfn_augment_desc;
 int kfn_augment_batch(const kfn_augment_desc* desc, const uint8_t* frames_in, const float* labels_in, uint8_t* frames_out,
                       float* labels_out, uint32_t* sums, void* stream);
+/* kfn_augment_pixel_map -- channels 7-8 of the reference's 9-channel bundle (KFNet/train.py:181-187): the normalised pixel
+ * map of get_pixel_map (:150-166) carried through the same rotation and zoom, out [H/label_stride,W/label_stride,2] at output
+ * pixels (label_stride r, label_stride c).  One parameter set serves the batch, so one map serves every frame (desc->B is
+ * only checked).  It is the label path above with the gathered value replaced by the analytic one: a tap at source pixel
+ * (sx, sy) has the value ((float(sx) - u) inv_fx, (float(sy) - v) inv_fy), a tap outside the image (0, 0); the same three-step
+ * interpolation in the same order; mode 0 gives the plain map.  inv_fx = float(1 / fx), rounded once by the host.  out 8-byte
+ * aligned.  KFN_ERR_ARG, and nothing launched: kfn_augment_batch's conditions on the descriptor, a NULL buffer. */
+int kfn_augment_pixel_map(const kfn_augment_desc* desc, float u, float v, float inv_fx, float inv_fy, float* out, void* stream);
+
+/* ---- the reprojection loss (added export; the ABI number stays 13) --------------------------------------------------------
+ * KFNet.ReprojectionLoss (KFNet/KFNet.py:405-428) in its masked form, which the reference adds to the three terms of its
+ * loss: 50 R in MeasureCoordLoss (:246-248), 10 R in TemporalCoordLoss (:270-272), 10 R in KFCoordLoss (:292-294).  DESIGN.md
+ * 6i.  For cell (r, c) of frame b and a prediction x (channels 0..2 of out[o].x):
+ *   cam = M_b [x; 1], M [B,12] = the first three rows of P_b G^-1 (P_b: world to camera of frame b, G: the 4x4 by which the
+ *         loss launches map the labels), formed by the host in fp64 and rounded once
+ *   q   = (pixel_map[r][c][0], pixel_map[r][c][1], 1), or ((float(8 c) - u) inv_fx, (float(8 r) - v) inv_fy, 1) when pixel_map
+ *         is NULL
+ *   n(a) = a / sqrt(max(sum a^2, 1e-12)) (tf.nn.l2_normalize), e = n(cam) - n(q), rho = sum_c e_c^2
+ *   m   = (labels[b][label_stride r][label_stride c][3] == 1), labels [B,h label_stride,w label_stride,4]
+ *   R   = sum(m rho) / (valid + 1), valid = nll_stats[valid_index] = sum(m) + 1 as kfn_coord_loss_grad (word 3) and
+ *         kfn_filter_loss_grad (word 10) report it: the reference divides by valid_pixel + 1 where valid_pixel already
+ *         carries a + 1 (:422, :427), and so does this launch.  The unmasked form (mask = None) is not built.
+ *   d(rho)/d(cam) = (2 / sqrt(s)) (n(cam) (n(cam) . n(q)) - n(q)) with s = sum cam^2 above the floor, 2e6 e at or below it;
+ *   out[o].dx[..][0..2] += out[o].weight m M_b[:, :3]^T d(rho)/d(cam) / (valid + 1).  Channel 3 and any padding channel keep
+ *   their bits, and so does every channel of a cell with m = 0.
+ *   stats_out[8] = (R of out[0], out[1], out[2] (0 for an absent one), sum_o weight_o R_o, valid + 1, 0, 0, 0)
+ * The launch ADDS, so it goes behind kfn_coord_loss_grad / kfn_filter_loss_grad on the same stream and in front of
+ * kfn_loss_scale_apply / kfn_filter_backward*.  One workgroup; per-cell terms in unfused fp32, the sums in fp64 over a fixed
+ * tree, no atomics: two launches give the same bits.  x and dx with ld % 4 == 0 and a 16-byte aligned base move as 16-byte
+ * words.  KFN_ERR_ARG, and nothing launched: a wrong struct_size, outputs outside 1..3, a NULL required buffer (pixel_map may
+ * be NULL), ld_x < 3 or ld_dx < 3, a label stride other than 1 or 8, a non-positive size or B h w >= 2^24, M not 16-byte
+ * aligned. */
+#define KFN_REPROJ_MAX_OUTPUTS 3
+typedef struct kfn_reproj_output {
+  const float* x;           /* [B,h,w,ld_x] */
+  float* dx;                /* [B,h,w,ld_dx] */
+  float weight;             /* multiplies dR/dx and R in stats_out[3] */
+  int32_t ld_x, ld_dx;      /* floats per cell, >= 3 */
+  int32_t reserved;         /* 0 */
+} kfn_reproj_output;
+typedef struct kfn_reproj_desc {
+  int32_t struct_size;      /* = sizeof(kfn_reproj_desc) */
+  int32_t B, h, w;
+  int32_t label_stride;     /* 1 or 8 */
+  int32_t outputs;          /* 1..3 */
+  float u, v;               /* principal point */
+  float inv_fx, inv_fy;     /* float(1 / fx), float(1 / fy) */
+  kfn_reproj_output out[KFN_REPROJ_MAX_OUTPUTS];
+} kfn_reproj_desc;
+int kfn_reproj_loss_grad(const kfn_reproj_desc* desc, const float* M, const float* labels, const float* pixel_map,
+                         const float* nll_stats, int valid_index, float* stats_out, void* stream);
 
 /* ---- training labels from depth maps and poses (added exports; the ABI number stays 13) -----------------------------
  * A label is a function of a depth map and a camera-to-world pose.  The device evaluates the list below in

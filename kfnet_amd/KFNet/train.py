@@ -21,6 +21,10 @@ The flags are the reference's (KFNet/train.py:14-47) and stage 1's, and --joint.
 both networks unless told --fix_flownet; here the plain command line stops and asks for one of the two flags.  --augment is
 refused: the reference's stage 3 has none, and so is --fp16: mixed precision is built for stage 1 only.  --loss_clip is off by
 default, as in stage 1.
+`--reproj` adds the reference's reprojection loss (KFNet.ReprojectionLoss, KFNet/KFNet.py:405-428) to the three terms with
+its weights: 50 in L_measure (:246-248), 10 in L_temporal (:270-272), 10 in L_KF (:292-294); `--reproj_weights a b c` sets
+other ones.  It reads the poses that pose_list.txt of I names and the intrinsics of the camera flags; the
+printed line then ends with the three values of `l_reproj` (measure~temporal~KF).
 """
 import argparse
 import sys
@@ -28,6 +32,7 @@ import time
 from datetime import datetime
 
 from .. import modes
+from ..reproj import STAGE3_WEIGHTS as REPROJ_WEIGHTS
 from ..SCoordNet.train import build_parser as stage1_parser, schedule
 
 FORMAT = ('[%s] epoch %d, step %d/%d, %5d~%5d~%5d~%5d, loss=%.3f, l_measure=%.3f, l_temp=%.3f, l_KF= %.3f, '
@@ -35,13 +40,22 @@ FORMAT = ('[%s] epoch %d, step %d/%d, %5d~%5d~%5d~%5d, loss=%.3f, l_measure=%.3f
 
 
 def format_line(now, epoch, step, max_steps, group, s, duration):
-    """KFNet/train.py:427-432."""
-    return FORMAT % (now, epoch, step, max_steps, group[0], group[1], group[2], group[3], s['loss'], s['l_measure'], s['l_temp'],
+    """KFNet/train.py:427-432; under --reproj (s holds 'l_reproj_measure') the three reprojection losses at the end."""
+    line = FORMAT % (now, epoch, step, max_steps, group[0], group[1], group[2], group[3], s['loss'], s['l_measure'], s['l_temp'],
                      s['l_KF'], s['a_measure'], s['a_temp'], s['a_KF'], s['pixels'], s['lr'], duration)
+    if 'l_reproj_measure' in s:
+        line += FORMAT_REPROJ % (s['l_reproj_measure'], s['l_reproj_temp'], s['l_reproj_kf'])
+    return line
+
+
+FORMAT_REPROJ = ', l_reproj=%.3f~%.3f~%.3f'
 
 
 def build_parser():
-    ap = stage1_parser()
+    ap = stage1_parser(reproj_flag=False)
+    ap.add_argument('--reproj', action='store_true', help='add the reprojection loss with the weights 50 / 10 / 10')
+    ap.add_argument('--reproj_weights', type=float, nargs=3, default=None, metavar=('M', 'T', 'KF'),
+                    help='add the reprojection loss with these weights in L_measure, L_temporal and L_KF')
     ap.description = __doc__
     ap.add_argument('--scoordnet', default='', help='model folder whose newest snapshot gives ScoreNet/*')
     ap.add_argument('--oflownet', default='', help='model folder whose newest snapshot gives Temporal/*')
@@ -70,6 +84,12 @@ def main(argv=None):
     if a.fp16 or a.loss_scale is not None:
         print('--fp16 is refused: mixed precision is built for stage 1 (SCoordNet.train) only', file=sys.stderr)
         return 1
+    reproj = a.reproj_weights if a.reproj_weights is not None else (REPROJ_WEIGHTS if a.reproj else None)
+    if reproj is not None and not all(x >= 0.0 for x in reproj):
+        print('--reproj_weights takes three weights >= 0', file=sys.stderr)
+        return 1
+    if reproj is not None and not any(reproj):
+        reproj = None
     if not a.model_folder:
         print('--model_folder is required: the snapshots go there', file=sys.stderr)
         return 1
@@ -86,7 +106,9 @@ def main(argv=None):
         check_size(a.height, a.width, '--height and --width')
         if length < GROUP:
             raise ValueError('--sequence_length must be at least %d' % GROUP)
-        source = open_source(a, False)
+        source = open_source(a, False, needs_poses=reproj is not None)
+        from ..labels import camera_of
+        camera = camera_of(a) if reproj is not None else None
         groups = group_list(source.count, length)
         if not groups:
             raise ValueError('%d frames hold no group of %d consecutive frames' % (source.count, GROUP))
@@ -109,7 +131,8 @@ def main(argv=None):
     torch.cuda.set_device(a.gpu)
     tr = KFNetTrainer(W, image_size=(a.height, a.width), groups=a.groups, transform=source.transform, base_lr=a.base_lr,
                       gamma=a.gamma, stepvalue=stepvalue, weight_decay=a.weight_decay, loss_clip=a.loss_clip,
-                      smooth_weight=a.smooth_weight, device='cuda:%d' % a.gpu, train_flownet=a.joint)
+                      smooth_weight=a.smooth_weight, device='cuda:%d' % a.gpu, train_flownet=a.joint, reproj_weights=reproj,
+                      camera=camera)
     if state is not None:
         tr.load_state(state)
     tr.global_step = start_step(step, stepvalue, a.reset_step, a.scoordnet, a.oflownet)
@@ -125,6 +148,8 @@ def main(argv=None):
         t0 = time.time()
         indices = group_indices(tr.global_step, a.groups, groups, a.shuffle, a.seed)
         frames, labels = source.batch(indices, False)
+        if reproj is not None:
+            tr.set_poses(source.poses[indices])
         stats = tr.step(frames, labels)
         s = tr.global_step
         if s % a.display == 0 or s == max_steps:

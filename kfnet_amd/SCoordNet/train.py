@@ -21,6 +21,10 @@ poses -- at the pixels the loss reads, or at full resolution with
 `--fp16` trains in mixed precision: conv1b .. conv7 on fp16 MFMA operands with fp32 accumulation, tensors and
 master weights in fp32, under dynamic loss scaling that starts at --loss_scale (a power of two, default 32768).  The printed
 line then ends with the scale and the number of steps skipped because of an overflow; `step` counts attempted steps.
+`--reproj [W]` adds W times the reference's reprojection loss (KFNet.ReprojectionLoss, KFNet/KFNet.py:405-428; W = 50 when
+the flag stands alone, as MeasureCoordLoss :246-248) to the loss.  It reads the poses that pose_list.txt of I
+names (`labels make` writes it next to the label files) and the intrinsics of the camera flags; with --augment the pixel map
+is augmented with the batch (KFNet/train.py:181-187).  The printed line then ends with `l_reproj`.
 """
 import argparse
 import sys
@@ -28,6 +32,7 @@ import time
 from datetime import datetime
 
 from .. import modes
+from ..reproj import STAGE1_WEIGHT as REPROJ_WEIGHT
 
 STEPVALUE = {'chess': 100000, 'fire': 30000, 'heads': 60000, 'office': 100000, 'pumpkin': 100000, 'redkitchen': 100000,
              'stairs': 100000}          # KFNet/train.py:330-344
@@ -36,15 +41,18 @@ FORMAT = ('[%s] epoch %d, step %d/%d, loss=%.3f, l_measure=%.3f, l_smooth=%.3f, 
 
 
 FORMAT_FP16 = ', loss_scale=%d, skipped=%d'
+FORMAT_REPROJ = ', l_reproj=%.3f'
 
 
 def format_line(now, epoch, step, max_steps, s, duration):
     """KFNet/train.py:427-432 reduced to the measurement fields; under --fp16 (s holds 'loss_scale') the scale and the
-    skipped steps behind them."""
+    skipped steps behind them; under --reproj (s holds 'l_reproj') the reprojection loss at the end."""
     line = FORMAT % (now, epoch, step, max_steps, s['loss'], s['l_measure'], s['l_smooth'], s['a_measure'], s['pixels'],
                      s['lr'], duration)
     if 'loss_scale' in s:
         line += FORMAT_FP16 % (s['loss_scale'], s['skipped'])
+    if 'l_reproj' in s:
+        line += FORMAT_REPROJ % s['l_reproj']
     return line
 
 
@@ -54,7 +62,8 @@ def schedule(scene, stepvalue=None, max_steps=None):
     return sv, (5 * sv if max_steps is None else max_steps)
 
 
-def build_parser():
+def build_parser(reproj_flag=True):
+    """reproj_flag = False leaves --reproj to the caller (KFNet.train's takes no number)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--input_folder', default='')
     ap.add_argument('--model_folder', default='')
@@ -81,6 +90,9 @@ def build_parser():
     ap.add_argument('--depth', action='store_true', help='make the labels on the device from depth_list.txt and pose_list.txt')
     ap.add_argument('--fp16', action='store_true', help='mixed precision: fp16 MFMA operands under dynamic loss scaling')
     ap.add_argument('--loss_scale', type=int, default=None, help='initial loss scale of --fp16, a power of two (default 32768)')
+    if reproj_flag:
+        ap.add_argument('--reproj', type=float, nargs='?', const=REPROJ_WEIGHT, default=None, metavar='W',
+                        help='add W (default 50) times the reprojection loss; needs pose_list.txt and the camera flags')
     from ..labels import add_camera_flags
     add_camera_flags(ap)
     return ap
@@ -104,13 +116,19 @@ def main(argv=None):
     if loss_scale < 1 or loss_scale > 2 ** 24 or loss_scale & (loss_scale - 1):
         print('--loss_scale must be a power of two in 1 .. 2^24', file=sys.stderr)
         return 1
+    if a.reproj is not None and not a.reproj >= 0.0:
+        print('--reproj takes a weight >= 0', file=sys.stderr)
+        return 1
+    reproj = a.reproj or 0.0
     stepvalue, max_steps = schedule(a.scene, a.stepvalue, a.max_steps)
     from ..batches import open_source
     from ..staging import check_size
+    from ..labels import camera_of
     from ..train import SCoordNetTrainer, batch_indices, restore
     try:
         check_size(a.height, a.width, '--height and --width')
-        source = open_source(a, SCoordNetTrainer.needs_full_resolution(a.augment))
+        source = open_source(a, SCoordNetTrainer.needs_full_resolution(a.augment), needs_poses=reproj > 0.0)
+        camera = camera_of(a) if reproj > 0.0 else None
     except (OSError, ValueError) as e:
         print(e, file=sys.stderr)
         return 1
@@ -124,7 +142,7 @@ def main(argv=None):
     tr = SCoordNetTrainer(W, image_size=(a.height, a.width), batch=a.batch, transform=source.transform, base_lr=a.base_lr,
                           gamma=a.gamma, stepvalue=stepvalue, weight_decay=a.weight_decay, loss_clip=a.loss_clip,
                           smooth_weight=a.smooth_weight, device='cuda:%d' % a.gpu, precision='fp16' if a.fp16 else 'fp32',
-                          loss_scale=loss_scale)
+                          loss_scale=loss_scale, reproj_weight=reproj, camera=camera)
     if state is not None:
         tr.load_state(state)
     tr.global_step = step if a.reset_step < 0 else a.reset_step
@@ -143,6 +161,8 @@ def main(argv=None):
         params = draw(augment_seed, tr.global_step) if a.augment else None
         indices = batch_indices(tr.global_step, a.batch, source.count, a.shuffle, a.seed)
         frames, labels = source.batch(indices, tr.needs_full_resolution(a.augment))
+        if reproj > 0.0:
+            tr.set_poses(source.poses[indices])
         stats = tr.step(frames, labels, augment=params)
         s = tr.global_step
         if s % a.display == 0 or s == max_steps:

@@ -132,6 +132,21 @@ class FlowLossDesc(SizedStructure):
                 ('dist_threshold', C.c_double), ('min_uncertainty', C.c_double)]
 
 
+REPROJ_MAX_OUTPUTS = 3
+
+
+class ReprojOutput(C.Structure):
+    """kfn_reproj_output (include/kfnet_hip.h)."""
+    _fields_ = [('x', C.c_void_p), ('dx', C.c_void_p), ('weight', C.c_float), ('ld_x', C.c_int32), ('ld_dx', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
+class ReprojDesc(SizedStructure):
+    """kfn_reproj_desc (include/kfnet_hip.h); `struct_size` is filled in here.  kfnet_amd.reproj.descriptor derives it."""
+    _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'B', 'h', 'w', 'label_stride', 'outputs')] +
+                [(n, C.c_float) for n in ('u', 'v', 'inv_fx', 'inv_fy')] + [('out', ReprojOutput * REPROJ_MAX_OUTPUTS)])
+
+
 class LossScaleState(C.Structure):
     """kfn_loss_scale_state (include/kfnet_hip.h): the record in device memory that drives dynamic loss scaling."""
     _fields_ = [('beta1_power', C.c_double), ('beta2_power', C.c_double), ('scale', C.c_float), ('good_steps', C.c_int32),
@@ -252,6 +267,9 @@ SYMBOLS = {
     # uncertainty-aware poses: weighted refinement, pose covariance, pose filter (added exports, ABI 13)
     'kfn_pnp_ransac_unc': (_i, [C.POINTER(PnPDesc), C.POINTER(PnPUncDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'kfn_pose_filter': (_i, [C.POINTER(PoseFilterDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the reprojection loss for stages 1 and 3, with the augmented pixel map (added exports, ABI 13)
+    'kfn_reproj_loss_grad': (_i, [C.POINTER(ReprojDesc), _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    'kfn_augment_pixel_map': (_i, [C.POINTER(AugmentDesc), C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),
 }
 
 _lib = None

@@ -114,6 +114,19 @@ class Augmenter(object):
                                               frames_out.data_ptr(), None if labels_out is None else labels_out.data_ptr(),
                                               self.sums.data_ptr(), stream), 'kfn_augment_batch')
 
+    def pixel_map(self, params, camera, out, stream):
+        """kfn_augment_pixel_map: the normalised pixel map of `camera` (a kfnet_amd.labels.DepthCamera) carried through the
+        augmentation of `params` (KFNet/train.py:181-187, channels 7-8 of the bundle), into the device tensor out
+        [H/s,W/s,2] float32.  One parameter set serves the batch, so one map serves every frame."""
+        from .reproj import camera_constants
+        B, H, W = self.shape
+        s = self.label_stride
+        if tuple(out.shape) != (H // s, W // s, 2) or out.dtype != self.torch.float32:
+            raise ValueError('the pixel map must be float32 [%d,%d,2], got %s' % (H // s, W // s, tuple(out.shape)))
+        d = descriptor(params, B, H, W, s)
+        u, v, inv_fx, inv_fy = camera_constants(camera)
+        _lib.check(self.lib.kfn_augment_pixel_map(C.byref(d), u, v, inv_fx, inv_fy, out.data_ptr(), stream), 'kfn_augment_pixel_map')
+
     def stage(self, frames_u8, labels):
         """Copies a batch into the staging buffers; returns (frames, labels or None) on the device."""
         torch = self.torch

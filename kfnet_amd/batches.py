@@ -1,6 +1,7 @@
 """Where the batches of `python -m kfnet_amd.SCoordNet.train` come from: seeded synthetic data, image and label files, or
 images with depth maps and poses.  The three sources are plain classes with one shape: `count` frames, `transform` (the 4x4
-of transform.txt itself) and batch(indices, full_resolution) -> (frames uint8 [n,H,W,3], labels [n,H,W,4] if full_resolution
+of transform.txt itself), `poses` ([count,4,4] camera to world, or None: what the reprojection term reads) and
+batch(indices, full_resolution) -> (frames uint8 [n,H,W,3], labels [n,H,W,4] if full_resolution
 else [n,H/8,W/8,4]).  Which labels a step needs is the trainer's to say (SCoordNetTrainer.needs_full_resolution).  Opening a
 source touches no device: a missing list or a label file of the wrong size is refused before torch initialises one."""
 import os
@@ -20,9 +21,10 @@ class SyntheticSource(object):
     """`count` frames of kfnet_amd.synth's sequence with train.synthetic_labels, for runs without data."""
 
     def __init__(self, count, size):
-        from .synth import synthetic_sequence, synthetic_transform
+        from .synth import synthetic_poses, synthetic_sequence, synthetic_transform
         self.count, self.size = count, size
         self.transform = synthetic_transform()
+        self.poses = synthetic_poses(count)
         self.frames = synthetic_sequence(count, size[0], size[1])
         self._labels = {}          # full_resolution -> [count,h,w,4], made when first asked for
 
@@ -35,10 +37,16 @@ class SyntheticSource(object):
 class LabelFileSource(object):
     """image_list.txt, label_list.txt (one [H,W,4] float32 file per image) and transform.txt of an input folder."""
 
-    def __init__(self, input_folder, size, needs_transform=True):
+    def __init__(self, input_folder, size, needs_transform=True, needs_poses=False):
         self.paths, self.label_paths = modes.read_inputs(input_folder)
         if self.label_paths is None:
             raise ValueError('%s has no label_list.txt: training needs labels' % input_folder)
+        self.poses = None
+        if needs_poses:
+            from .reproj import read_pose_list
+            self.poses = read_pose_list(input_folder)
+            if len(self.poses) != len(self.paths):
+                raise ValueError('pose_list.txt of %s lists %d poses for %d images' % (input_folder, len(self.poses), len(self.paths)))
         # stage 2's loss is invariant under the rigid transform: OFlowNet.train neither needs nor reads the file
         self.transform = np.loadtxt(os.path.join(input_folder, 'transform.txt'), dtype=np.float32) if needs_transform else None
         self.count, self.size = len(self.paths), size
@@ -83,9 +91,10 @@ class DepthSource(object):
         return frames, self._labelers[full_resolution].labels(depth, self.poses[indices])
 
 
-def open_source(a, full_resolution, needs_transform=True):
+def open_source(a, full_resolution, needs_transform=True, needs_poses=False):
     """The source that the parsed arguments of SCoordNet.train ask for (needs_transform = False: OFlowNet.train's, whose label
-    files go without transform.txt).  ValueError or OSError, with the message for the
+    files go without transform.txt; needs_poses: the run has the reprojection term on, so a folder of label files must hold
+    pose_list.txt too).  ValueError or OSError, with the message for the
     user, when the arguments or the folder do not make one; with `full_resolution` the first label file is read here, so
     that grid-sized label files are refused at once."""
     size = (a.height, a.width)
@@ -95,7 +104,7 @@ def open_source(a, full_resolution, needs_transform=True):
         return SyntheticSource(a.synthetic, size)
     if a.depth:
         return DepthSource(a.input_folder, size, a.batch, L.camera_of(a), 'cuda:%d' % a.gpu)
-    source = LabelFileSource(a.input_folder, size, needs_transform)
+    source = LabelFileSource(a.input_folder, size, needs_transform, needs_poses)
     if full_resolution:
         source.label(0, True)
     return source

@@ -229,7 +229,48 @@ __global__ __launch_bounds__(ST) void augment_kernel(AugArgs p) {
   else augment_labels(p);
 }
 
+// one thread per output pixel (s r, s c): augment_labels with the gathered label replaced by the pixel's own normalised
+// coordinates, ((float(qx) - u) inv_fx, (float(qy) - v) inv_fy)
+__global__ __launch_bounds__(ST) void pixel_map_kernel(AugArgs p, float u, float v, float inv_fx, float inv_fy, float2* __restrict__ out) {
+  const int h = p.H / p.s, w = p.W / p.s;
+  const long id = (long)blockIdx.x * ST + threadIdx.x;
+  if (id >= (long)h * w) return;
+  const int c = (int)(id % w), r = (int)(id / w);
+  const int i = r * p.s, j = c * p.s;
+  float2 o;
+  if (p.mode == 0) {
+    o.x = ((float)j - u) * inv_fx;
+    o.y = ((float)i - v) * inv_fy;
+  } else {
+    const Axis ay = resolve(p.mode, i, p.H, p.y0, p.dy, p.new_h, p.off_y, p.scale_y);
+    const Axis ax = resolve(p.mode, j, p.W, p.x0, p.dx, p.new_w, p.off_x, p.scale_x);
+    float2 tap[4];
+    for (int q = 0; q < 4; ++q) {
+      int qx = 0, qy = 0;
+      const bool in = ay.ok && ax.ok && rotated(p, (q & 1) ? ax.hi : ax.lo, (q & 2) ? ay.hi : ay.lo, &qx, &qy);
+      tap[q] = in ? make_float2(((float)qx - u) * inv_fx, ((float)qy - v) * inv_fy) : make_float2(0.0f, 0.0f);
+    }
+    o.x = lerp2(tap[0].x, tap[1].x, tap[2].x, tap[3].x, ax.frac, ay.frac);
+    o.y = lerp2(tap[0].y, tap[1].y, tap[2].y, tap[3].y, ax.frac, ay.frac);
+  }
+  out[id] = o;
+}
+
 bool sized(int B, int H, int W) { return B > 0 && H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0 && (long)B * H * W <= (1L << 30); }
+
+// the descriptor's part of the launch arguments: sizes, mode and the constants of the resampling
+AugArgs geometry(const kfn_augment_desc* d) {
+  AugArgs a;
+  a.fin = nullptr; a.lin = nullptr; a.fout = nullptr; a.lout = nullptr; a.sums = nullptr;
+  a.B = d->B; a.H = d->H; a.W = d->W; a.s = d->label_stride; a.mode = d->mode;
+  a.has_rot = d->mode != 0 && d->has_rotation; a.has_col = d->has_colour;
+  for (int i = 0; i < 6; ++i) a.rot[i] = d->rot[i];
+  a.y0 = d->y0; a.dy = d->dy; a.x0 = d->x0; a.dx = d->dx;
+  a.new_h = d->new_h; a.new_w = d->new_w; a.off_y = d->off_y; a.off_x = d->off_x;
+  a.scale_y = d->scale_y; a.scale_x = d->scale_x; a.delta = d->delta; a.factor = d->factor;
+  a.frame_blocks = 0;
+  return a;
+}
 
 }  // namespace
 
@@ -271,20 +312,36 @@ extern "C" int kfn_augment_batch(const kfn_augment_desc* d, const uint8_t* frame
     const int rc = kfn_frame_channel_sums(frames_in, d->B, d->H, d->W, sums, stream);
     if (rc != KFN_OK) return rc;
   }
-  AugArgs a;
+  AugArgs a = geometry(d);
   a.fin = frames_in; a.lin = reinterpret_cast<const float4*>(labels_in); a.fout = frames_out;
   a.lout = reinterpret_cast<float4*>(labels_out); a.sums = sums;
-  a.B = d->B; a.H = d->H; a.W = d->W; a.s = d->label_stride; a.mode = d->mode;
-  a.has_rot = d->mode != 0 && d->has_rotation; a.has_col = d->has_colour;
-  for (int i = 0; i < 6; ++i) a.rot[i] = d->rot[i];
-  a.y0 = d->y0; a.dy = d->dy; a.x0 = d->x0; a.dx = d->dx;
-  a.new_h = d->new_h; a.new_w = d->new_w; a.off_y = d->off_y; a.off_x = d->off_x;
-  a.scale_y = d->scale_y; a.scale_x = d->scale_x; a.delta = d->delta; a.factor = d->factor;
   const long frame_threads = (long)d->B * d->H * (d->W / PX);
   const long label_threads = labels_in ? (long)d->B * (d->H / d->label_stride) * (d->W / d->label_stride) : 0;
   a.frame_blocks = (unsigned)((frame_threads + ST - 1) / ST);
   const unsigned label_blocks = (unsigned)((label_threads + ST - 1) / ST);
   hipLaunchKernelGGL(augment_kernel, dim3(a.frame_blocks + label_blocks), dim3(ST), 0, reinterpret_cast<hipStream_t>(stream), a);
   KFN_LAUNCH_CHECK("augment_kernel");
+  return KFN_OK;
+}
+
+extern "C" int kfn_augment_pixel_map(const kfn_augment_desc* d, float u, float v, float inv_fx, float inv_fy, float* out,
+                                     void* stream) {
+  KFN_REQUIRE(d && out, "kfn_augment_pixel_map: null argument");
+  KFN_REQUIRE(d->struct_size == (int32_t)sizeof(kfn_augment_desc), "kfn_augment_pixel_map: struct_size %d, expected %d",
+              (int)d->struct_size, (int)sizeof(kfn_augment_desc));
+  KFN_REQUIRE(sized(d->B, d->H, d->W), "kfn_augment_pixel_map: %dx%dx%d: height and width must be multiples of 8, at least 8",
+              d->B, d->H, d->W);
+  KFN_REQUIRE(d->label_stride == 1 || d->label_stride == 8, "kfn_augment_pixel_map: label_stride %d is neither 1 nor 8", d->label_stride);
+  KFN_REQUIRE(d->mode >= 0 && d->mode <= 2, "kfn_augment_pixel_map: unknown mode %d", d->mode);
+  KFN_REQUIRE(((uintptr_t)out & 7) == 0, "kfn_augment_pixel_map: out must be 8-byte aligned");
+  if (d->mode == 2)
+    KFN_REQUIRE(d->new_h >= 1 && d->new_h <= d->H && d->new_w >= 1 && d->new_w <= d->W && d->off_y >= 0 && d->off_y <= d->H - d->new_h &&
+                d->off_x >= 0 && d->off_x <= d->W - d->new_w && d->scale_y > 0.0f && d->scale_x > 0.0f,
+                "kfn_augment_pixel_map: bad shrink constants (new %dx%d at offset %d, %d)", d->new_h, d->new_w, d->off_y, d->off_x);
+  const AugArgs a = geometry(d);
+  const long cells = (long)(d->H / d->label_stride) * (d->W / d->label_stride);
+  hipLaunchKernelGGL(pixel_map_kernel, dim3((unsigned)((cells + ST - 1) / ST)), dim3(ST), 0, reinterpret_cast<hipStream_t>(stream), a,
+                     u, v, inv_fx, inv_fy, reinterpret_cast<float2*>(out));
+  KFN_LAUNCH_CHECK("pixel_map_kernel");
   return KFN_OK;
 }

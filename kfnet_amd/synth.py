@@ -36,3 +36,20 @@ def synthetic_transform(seed=7):
     M[:3, :3] = Q.astype(np.float32)
     M[:3, 3] = rng.uniform(-1, 1, size=3).astype(np.float32)
     return M
+
+
+def synthetic_poses(count, seed=11, start=0):
+    """Seeded rigid camera-to-world poses [count,4,4] of frames [start, start + count): a small rotation about a fixed axis
+    and a drift that grow with the frame index.  They belong to no scene: a reprojection loss on them is finite, not small."""
+    rng = np.random.default_rng(seed)
+    axis = rng.normal(size=3)
+    axis /= np.linalg.norm(axis)
+    K = np.array([[0.0, -axis[2], axis[1]], [axis[2], 0.0, -axis[0]], [-axis[1], axis[0], 0.0]])
+    drift = rng.uniform(-0.05, 0.05, size=3)
+    out = np.zeros((count, 4, 4), dtype=np.float64)
+    for i in range(count):
+        a = 0.02 * (start + i)
+        out[i, :3, :3] = np.eye(3) + np.sin(a) * K + (1.0 - np.cos(a)) * (K @ K)      # Rodrigues
+        out[i, :3, 3] = np.array([0.3, -0.2, -1.0]) + drift * (start + i)
+        out[i, 3, 3] = 1.0
+    return out

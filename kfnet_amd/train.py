@@ -6,6 +6,8 @@ one step is a fixed list of launches of libkfnet_hip.so (DESIGN.md "Training"):
     augment      (step(..., augment=params) only) kfn_augment_batch: the raw batch -> self.frames and grid-sized labels
     forward      kfn_first_conv_u8, then kfn_conv2d_nhwc per layer (the direct route, fp32, every output kept)
     loss         kfn_coord_loss_grad: NLL + smoothness on the prepared labels, and d(loss)/d(prediction)
+                 (reproj_weight > 0 only) kfn_reproj_loss_grad behind it: w_r * R of KFNet.ReprojectionLoss and its gradient
+                 added to d(loss)/d(prediction); with augment= the rays come from kfn_augment_pixel_map
     backward     per layer, last to first: kfn_conv2d_grad_weights; the input gradient on the FORWARD kernel
                  (stride 1: kfn_conv2d_nhwc with the rotated, channel-swapped pack; stride 2: its transposed form);
                  kfn_relu_grad.  conv1a: kfn_first_conv_u8_grad_weights.
@@ -122,12 +124,14 @@ class StepStats(object):
     a_measure, pixels, lr.  dict(stats) gives plain floats."""
     KEYS = ('loss', 'l_measure', 'l_smooth', 'a_measure', 'pixels', 'lr')
     SCALE_KEYS = ('loss_scale', 'skipped')      # precision='fp16' only: the scale after this step, the steps skipped so far
+    REPROJ_KEYS = ('l_reproj',)                 # reproj_weight > 0 only: R itself; `loss` then includes reproj_weight * R
 
-    def __init__(self, stats_dev, lr, scale_dev=None):
-        self._dev, self._lr, self._host, self._scale_dev = stats_dev, lr, None, scale_dev
+    def __init__(self, stats_dev, lr, scale_dev=None, reproj_dev=None):
+        self._dev, self._lr, self._host, self._scale_dev, self._reproj_dev = stats_dev, lr, None, scale_dev, reproj_dev
 
     def keys(self):
-        return list(self.KEYS) + (list(self.SCALE_KEYS) if self._scale_dev is not None else [])
+        return (list(self.KEYS) + (list(self.SCALE_KEYS) if self._scale_dev is not None else []) +
+                (list(self.REPROJ_KEYS) if self._reproj_dev is not None else []))
 
     def __getitem__(self, k):
         if self._host is None:
@@ -138,17 +142,23 @@ class StepStats(object):
             if self._scale_dev is not None:
                 st = _lib.LossScaleState.from_buffer_copy(self._scale_dev.cpu().numpy().tobytes())
                 self._host.update(loss_scale=float(st.scale), skipped=int(st.skipped))
+            if self._reproj_dev is not None:
+                r = self._reproj_dev.cpu().numpy()       # kfn_reproj_loss_grad's stats: R, ., ., weight * R
+                self._host.update(l_reproj=float(r[0]), loss=float(s[4]) + float(r[3]))
         return self._host[k]
 
 
 class SCoordNetTrainer(object):
     def __init__(self, weights, image_size=(480, 640), batch=4, transform=None, base_lr=1e-4, gamma=0.5, stepvalue=80000,
                  weight_decay=1e-4, loss_clip=None, smooth_weight=50.0, device='cuda:0', precision='fp32', loss_scale=2 ** 15,
-                 growth_interval=2000):
+                 growth_interval=2000, reproj_weight=0.0, camera=None):
         """weights: {TF name: array} holding at least ScoreNet/*.  transform: the 4x4 of transform.txt ITSELF (labels are
         mapped by it, KFNet/train.py:279-280), None = identity.  loss_clip: None (no clip) or the reference's -2.0.
         precision: 'fp32', or 'fp16' = fp16 MFMA operands in the layers of f16_layer() under dynamic loss scaling that starts
-        at loss_scale (a power of two in 1 .. 2^24) and doubles after growth_interval applied steps without an overflow."""
+        at loss_scale (a power of two in 1 .. 2^24) and doubles after growth_interval applied steps without an overflow.
+        reproj_weight: w_r of the reprojection term w_r * R (KFNet/KFNet.py:246-248 uses 50; 0 = off: nothing of it is
+        launched or allocated); camera: the kfnet_amd.labels.DepthCamera whose intrinsics give the cells' rays (None: the
+        7-Scenes defaults).  Every step() then needs a set_poses() in front of it."""
         import torch
         H, Wd = image_size
         staging.check_size(H, Wd, 'the height and width of a training batch')
@@ -174,6 +184,12 @@ class SCoordNetTrainer(object):
         self.transform = None if transform is None else np.asarray(transform, dtype=np.float32).reshape(4, 4)
         self.global_step = 0
         self.adam_t = 0
+        from .reproj import check_weights
+        self.reproj_weight = check_weights(reproj_weight, 1)[0]
+        self.reproj = None                # kfnet_amd.reproj.ReprojTerm when the weight is positive
+        self.pixel_map = None             # [h,w,2]: the augmented pixel map, made by the first augmented step with the term on
+        self._poses_set = False           # set_poses() has run since the last step
+        self._pixel_map_live = False      # the staged batch is augmented: the rays come from self.pixel_map
 
         # flat parameter buffer: kernel then bias per layer, TF HWIO order (every offset a multiple of 4 floats)
         self.slots = {}
@@ -221,6 +237,9 @@ class SCoordNetTrainer(object):
             self.workspace = torch.zeros(-(-ws_bytes // 4), **f32)
             self.stats = torch.zeros(8, **f32)
             self._packs_stale = True
+            if self.reproj_weight > 0.0:
+                from .reproj import ReprojTerm
+                self.reproj = ReprojTerm(batch, self.grid[0], self.grid[1], camera, self.transform, self.device)
             self.scale_state = None           # kfn_loss_scale_state on the device
             if precision == 'fp16':
                 self.scale_state = torch.zeros(C.sizeof(_lib.LossScaleState), dtype=torch.uint8, device=self.device)
@@ -375,7 +394,13 @@ class SCoordNetTrainer(object):
             self.labels = aug.labels_out
             stream = staging.current_stream(self.device) if stream is None else stream
             aug.launch(augment, fin, lin, self.frames, self.labels, stream)
+            if self.reproj is not None:       # the cells' rays go through the same rotation and zoom (KFNet/train.py:181-187)
+                if self.pixel_map is None:
+                    self.pixel_map = torch.zeros((h, w, 2), dtype=torch.float32, device=self.device)
+                aug.pixel_map(augment, self.reproj.camera, self.pixel_map, stream)
+                self._pixel_map_live = True
             return 1
+        self._pixel_map_live = False
         staging.stage(self.frames, frames_u8, torch.uint8, (B, H, Wd, 3), 'frames')
         # the labels of either size, converted to float32: their shape picks the stride, so the copy is torch's own
         lb = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.float32))
@@ -439,7 +464,8 @@ class SCoordNetTrainer(object):
             self.forward_layer(li, stream)
 
     def loss(self, label_stride, stream=None):
-        """The loss launch: self.stats, and d(loss)/d(prediction) into self.dact[-1]."""
+        """The loss launch: self.stats, and d(loss)/d(prediction) into self.dact[-1]; with the reprojection term on, its launch
+        behind it (self.reproj.stats; the poses of the staged batch must have been set, self.reproj.set_poses)."""
         stream = staging.current_stream(self.device) if stream is None else stream
         B, (h, w) = self.batch, self.grid
         last = len(LAYERS) - 1
@@ -452,6 +478,9 @@ class SCoordNetTrainer(object):
         _lib.check(self.lib.kfn_coord_loss_grad(C.byref(d), self.act[last].data_ptr(), self.labels.data_ptr(),
                                                 self.frames.data_ptr(), self.dact[last].data_ptr(), self.stats.data_ptr(),
                                                 stream), 'kfn_coord_loss_grad')
+        if self.reproj is not None:           # adds into self.dact[last], so behind the NLL and in front of the loss scale
+            self.reproj.launch([(self.act[last], self.dact[last], self.reproj_weight)], self.labels, label_stride,
+                               self.pixel_map if self._pixel_map_live else None, self.stats, 3, stream)
         if self.precision == 'fp16':          # everything behind this point of the backward pass carries the scale
             _lib.check(self.lib.kfn_loss_scale_apply(self.dact[last].data_ptr(), self.dact[last].numel(),
                                                      self.scale_state.data_ptr(), stream), 'kfn_loss_scale_apply')
@@ -497,12 +526,25 @@ class SCoordNetTrainer(object):
         self._packs_stale = True
         return lr
 
+    def set_poses(self, poses):
+        """The camera-to-world 4x4 of each frame of the NEXT step's batch ([B,4,4]): what the reprojection term reads.  Every
+        step with reproj_weight > 0 needs its own call (step() keeps the signature its callers know); without the term the
+        poses are not looked at."""
+        if self.reproj is not None:
+            with self.torch.cuda.device(self.device):
+                self.reproj.set_poses(poses)
+            self._poses_set = True
+
     def step(self, frames_u8, labels, augment=None):
         """One update on a batch: frames uint8 [B,H,W,3], labels float32 [B,H,W,4] or grid-sized [B,H/8,W/8,4] =
         (gt xyz, mask).  augment: None, or the kfnet_amd.augment.AugmentParams of this batch -- the labels must then be the
         full-resolution ones, and forward pass, loss and smoothness weights see the augmented frames.  Returns
         StepStats (loss, l_measure, l_smooth, a_measure, pixels, lr of THIS step's loss, before the update), read back only
-        when accessed."""
+        when accessed.  With reproj_weight > 0 set_poses() must have handed over this batch's poses (ValueError otherwise);
+        the stats then hold l_reproj too, and loss includes reproj_weight * l_reproj."""
+        if self.reproj is not None and not self._poses_set:
+            raise ValueError('the reprojection term needs the poses of this batch: call set_poses(poses) before every step')
+        self._poses_set = False
         with self.torch.cuda.device(self.device):
             stream = staging.current_stream(self.device)
             stride = self.stage(frames_u8, labels, augment, stream)
@@ -512,7 +554,8 @@ class SCoordNetTrainer(object):
             lr = self.apply_gradients(stream)
             self._repack(stream)
             scale = self.scale_state.clone() if self.precision == 'fp16' else None
-        return StepStats(stats, lr, scale)
+            reproj = self.reproj.stats.clone() if self.reproj is not None else None
+        return StepStats(stats, lr, scale, reproj)
 
 
 def restore(model_folder, verbose=True, scope=SCOPE):

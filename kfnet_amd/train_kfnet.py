@@ -10,6 +10,8 @@ A step sees S groups of T consecutive frames (T = 4 on the command line).  Its l
     measurement kfn_measurement_map: (z, exp(log sigma)) from the raw prediction
     filter      kfn_kalman_scan_ex with a reset on frame 0 of every group: the launch eval runs, writing the temporal and KF maps
     loss        kfn_filter_loss_grad: 0.2 L_measure + 0.2 L_temporal + 0.6 L_KF and the direct gradients of the three outputs
+                (reproj_weights only) kfn_reproj_loss_grad behind it: weight_measure * w_m * R_m + weight_temporal * w_t * R_t +
+                weight_kf * w_kf * R_KF of KFNet.ReprojectionLoss, gradients added to those of the three outputs
     backward    kfn_filter_backward: the reverse scan, whose measurement gradients join d(loss)/d(prediction);
                 then SCoordNetTrainer.backward, Adam and the packs as in stage 1
 
@@ -92,12 +94,13 @@ class StepStats(object):
     NLL + 50 smoothness, as the reference logs them), a_measure, a_temp, a_KF, pixels, lr.  The read-back raises when a flow
     left the radius of the reverse scan."""
     KEYS = ('loss', 'l_measure', 'l_temp', 'l_KF', 'a_measure', 'a_temp', 'a_KF', 'pixels', 'lr')
+    REPROJ_KEYS = ('l_reproj_measure', 'l_reproj_temp', 'l_reproj_kf')   # reproj_weights only: the three R; `loss` includes them
 
-    def __init__(self, stats_dev, lr, radius):
-        self._dev, self._lr, self._radius, self._host = stats_dev, lr, radius, None
+    def __init__(self, stats_dev, lr, radius, reproj_dev=None):
+        self._dev, self._lr, self._radius, self._host, self._reproj_dev = stats_dev, lr, radius, None, reproj_dev
 
     def keys(self):
-        return list(self.KEYS)
+        return list(self.KEYS) + (list(self.REPROJ_KEYS) if self._reproj_dev is not None else [])
 
     def __getitem__(self, k):
         if self._host is None:
@@ -106,6 +109,10 @@ class StepStats(object):
             self._host = dict(loss=float(s[0]), l_measure=float(s[12]), l_temp=float(s[13]), l_KF=float(s[14]),
                               a_measure=float(s[7]), a_temp=float(s[8]), a_KF=float(s[9]), pixels=float(s[10]) - 1.0,
                               lr=self._lr)
+            if self._reproj_dev is not None:
+                r = self._reproj_dev.cpu().numpy()       # kfn_reproj_loss_grad's stats: the three R, their weighted sum
+                self._host.update(l_reproj_measure=float(r[0]), l_reproj_temp=float(r[1]), l_reproj_kf=float(r[2]),
+                                  loss=float(s[0]) + float(r[3]))
         return self._host[k]
 
 
@@ -118,10 +125,13 @@ def check_flow_count(stats_host, radius):
 class KFNetTrainer(object):
     def __init__(self, weights, image_size=(480, 640), groups=1, group=GROUP, transform=None, base_lr=1e-4, gamma=0.5,
                  stepvalue=80000, weight_decay=1e-4, loss_clip=None, smooth_weight=50.0, loss_weights=LOSS_WEIGHTS,
-                 radius=RADIUS, device='cuda:0', train_flownet=False, overlap=True):
+                 radius=RADIUS, device='cuda:0', train_flownet=False, overlap=True, reproj_weights=None, camera=None):
         """weights: {TF name: array} holding ScoreNet/* and Temporal/*.  groups = S, group = T.  The other arguments are
         SCoordNetTrainer's; loss_weights = (measure, temporal, KF).  train_flownet: train Temporal/* too, with the same
-        schedule and weight decay; overlap: run its backward pass on the flow stream beside SCoordNet's (else behind it)."""
+        schedule and weight decay; overlap: run its backward pass on the flow stream beside SCoordNet's (else behind it).
+        reproj_weights: None, or (w_m, w_t, w_kf) of the reprojection terms that join L_measure, L_temporal and L_KF (the
+        reference: 50, 10, 10); all zero = None: nothing of the term is launched or allocated.  camera: the
+        kfnet_amd.labels.DepthCamera of the cells' rays (None: the 7-Scenes defaults).  Every step() then needs a set_poses()."""
         import torch
         from .engine import OFlowNetEngine
         if groups < 1 or group < 2:
@@ -135,6 +145,12 @@ class KFNetTrainer(object):
         self.torch, self.lib, self.device = torch, sc.lib, sc.device
         self.loss_weights = tuple(float(x) for x in loss_weights)
         self.radius = int(radius)
+        from .reproj import check_weights
+        self.reproj_weights = None if reproj_weights is None else check_weights(reproj_weights, 3)
+        if self.reproj_weights is not None and not any(self.reproj_weights):
+            self.reproj_weights = None
+        self.reproj = None
+        self._poses_set = False
         self.train_flownet, self.overlap = bool(train_flownet), bool(overlap)
         self.flow_weights = {k: np.asarray(v, dtype=np.float32).copy() for k, v in weights.items()
                              if k.startswith(FLOW_SCOPE + '/')}
@@ -165,6 +181,9 @@ class KFNetTrainer(object):
             self.records = torch.zeros((B, h, w, 4), **f32)
             self.filter_state = torch.zeros((self.S, h, w, 4), **f32)
             self.stats = torch.zeros(16, **f32)
+            if self.reproj_weights is not None:
+                from .reproj import ReprojTerm
+                self.reproj = ReprojTerm(B, h, w, camera, sc.transform, self.device)
             self._flow_count = torch.zeros(1, dtype=torch.int32).pin_memory()
             self.ev_count = torch.cuda.Event()
             # frame 0 of every group is a reset frame (t0 = 0, reset_period = T): both estimates equal the measurement
@@ -308,6 +327,10 @@ class KFNetTrainer(object):
                                                  sc.labels.data_ptr(), sc.frames.data_ptr(), sc.dact[-1].data_ptr(),
                                                  self.d_temp.data_ptr(), self.d_kf.data_ptr(), self.stats.data_ptr(), stream),
                    'kfn_filter_loss_grad')
+        if self.reproj is not None:           # adds into the three gradient buffers: behind the loss, in front of the reverse scan
+            wr, wl = self.reproj_weights, self.loss_weights
+            self.reproj.launch([(sc.act[-1], sc.dact[-1], wl[0] * wr[0]), (self.temp, self.d_temp, wl[1] * wr[1]),
+                                (self.kf, self.d_kf, wl[2] * wr[2])], sc.labels, label_stride, None, self.stats, 10, stream)
 
     def filter_backward(self, stream=None):
         stream = staging.current_stream(self.device) if stream is None else stream
@@ -324,11 +347,22 @@ class KFNetTrainer(object):
                                                 self.d_kf.data_ptr(), self.sc.dact[-1].data_ptr(), self.stats.data_ptr(),
                                                 self.back_scratch.data_ptr(), stream), 'kfn_filter_backward')
 
+    def set_poses(self, poses):
+        """The camera-to-world 4x4 of each of the S T frames of the NEXT step, as SCoordNetTrainer.set_poses."""
+        if self.reproj is not None:
+            with self.torch.cuda.device(self.device):
+                self.reproj.set_poses(poses)
+            self._poses_set = True
+
     def step(self, frames_u8, labels):
         """One update on S groups: frames uint8 [S T,H,W,3] group after group in group order, labels float32 [S T,H,W,4] or
         grid-sized.  Returns StepStats of THIS step's loss, before the update, read back only when accessed.  Raises, before the
-        update is queued, when a flow left the radius of the reverse scan."""
+        update is queued, when a flow left the radius of the reverse scan.  With reproj_weights set_poses() must have handed over
+        this batch's poses (ValueError otherwise)."""
         sc, torch = self.sc, self.torch
+        if self.reproj is not None and not self._poses_set:
+            raise ValueError('the reprojection term needs the poses of this batch: call set_poses(poses) before every step')
+        self._poses_set = False
         with torch.cuda.device(self.device):
             main = torch.cuda.current_stream(self.device)
             stream = main.cuda_stream
@@ -351,7 +385,8 @@ class KFNetTrainer(object):
                 self.flow_update(main)
             lr = sc.apply_gradients(stream)
             sc._repack(stream)
-        return StepStats(stats, lr, self.radius)
+            reproj = self.reproj.stats.clone() if self.reproj is not None else None
+        return StepStats(stats, lr, self.radius, reproj)
 
     def flow_update(self, main):
         """Temporal/*'s Adam step and packs with SCoordNet's counters, where its backward pass ran; `main` then waits for the

@@ -7,6 +7,7 @@ launch as fractions of the fp32 MFMA peak.
     python tools/mb_train.py --kfnet [--groups 1]
     python tools/mb_train.py --oflownet [--pairs 4]
     python tools/mb_train.py --joint [--groups 1]
+    python tools/mb_train.py --reproj [--kfnet | --joint] [--rounds 5]
 
 --augment times the step with the augmentation of DESIGN.md 6c on: full-resolution labels, the parameters of
 kfnet_amd.augment.draw(0, step) in turn (its kernels are channel_sums_kernel and augment_kernel in a kernel trace).
@@ -25,6 +26,9 @@ normalisation's backward, and the loss.
 --joint times the joint step of KFNetTrainer (train_flownet): ms per step with OFlowNet's backward pass on the
 flow stream beside SCoordNet's and on one stream, the share of the launches the joint step adds to the fixed one (the reverse
 scan's joint form beside the fixed form, the copies between the pair and the scan layout), and the OFlowNet backward alone.
+--reproj times the step with the reprojection term beside the plain step in ONE process: two trainers on the
+same batch in alternating rounds (median, minimum and maximum of --rounds windows), for stage 1, or with --kfnet / --joint
+for stage 3 fixed / joint; then kfn_reproj_loss_grad (one and three outputs) and kfn_augment_pixel_map alone.
 
 Under `rocprofv3 --kernel-trace --stats -- python tools/mb_train.py --steps 5` the kernel table gives the same split per
 kernel name (wgrad_mfma_kernel, conv_mfma_kernel, ...)."""
@@ -271,6 +275,68 @@ def fp16(a):
     return 0
 
 
+def reproj(a):
+    """The step with and without the reprojection term, in alternating rounds; then the two new launches alone."""
+    import torch
+    from kfnet_amd.augment import AugmentParams, Augmenter, ENLARGE
+    from kfnet_amd.labels import DepthCamera
+    from kfnet_amd.reproj import STAGE1_WEIGHT, STAGE3_WEIGHTS, ReprojTerm
+    from kfnet_amd.synth import synthetic_poses, synthetic_sequence, synthetic_transform
+    from kfnet_amd.train import SCoordNetTrainer, synthetic_labels
+    from kfnet_amd.train_kfnet import GROUP, KFNetTrainer
+    from kfnet_amd.weights import initial_weights, synthetic_weights
+    size = (a.height, a.width)
+    stage3 = a.kfnet or a.joint
+    B = a.groups * GROUP if stage3 else a.batch
+    W = initial_weights(0)
+    if stage3:
+        W.update({k: v for k, v in synthetic_weights(1234).items() if k.startswith('Temporal/')})
+        trs = {on: KFNetTrainer(W, image_size=size, groups=a.groups, transform=synthetic_transform(), train_flownet=a.joint,
+                                reproj_weights=STAGE3_WEIGHTS if on else None) for on in (False, True)}
+        grid = trs[True].sc.grid
+    else:
+        trs = {on: SCoordNetTrainer(W, image_size=size, batch=B, transform=synthetic_transform(),
+                                    reproj_weight=STAGE1_WEIGHT if on else 0.0) for on in (False, True)}
+        grid = trs[True].grid
+    frames = torch.from_numpy(synthetic_sequence(B, a.height, a.width)).cuda()
+    labels = torch.from_numpy(synthetic_labels(B, grid)).cuda()
+    poses = synthetic_poses(B)
+    fns = {on: (lambda tr=tr: (tr.set_poses(poses), tr.step(frames, labels))) for on, tr in trs.items()}
+    for fn in fns.values():
+        for _ in range(a.warmup):
+            fn()
+    t = {on: [] for on in fns}
+    for _ in range(a.rounds):
+        for on, fn in fns.items():
+            t[on].append(timed(torch, fn, a.steps))
+    kind = 'stage 3 joint' if a.joint else 'stage 3 fixed' if a.kfnet else 'stage 1'
+    for on in (False, True):
+        print('%dx%d batch %d, %s, %s: %.2f ms per step (median of %d windows of %d steps; %.2f .. %.2f)' %
+              (a.height, a.width, B, kind, 'with the term' if on else 'plain', float(np.median(t[on])), a.rounds, a.steps,
+               min(t[on]), max(t[on])))
+    print('the term costs %.3f ms per step (difference of the medians)' % (float(np.median(t[True])) - float(np.median(t[False]))))
+    # the two launches alone
+    h, w = grid
+    stream = torch.cuda.current_stream().cuda_stream
+    term = ReprojTerm(B, h, w, DepthCamera(), synthetic_transform())
+    term.set_poses(poses)
+    g = torch.Generator(device='cuda').manual_seed(0)
+    xs = [torch.randn(B, h, w, 4, device='cuda', generator=g) for _ in range(3)]
+    dxs = [torch.zeros(B, h, w, 16 if o == 0 else 4, device='cuda') for o in range(3)]
+    nll = torch.zeros(16, device='cuda')
+    nll[3] = float(labels[..., 3].sum().item()) + 1.0
+    for n in (1, 3):
+        outs = [(xs[o], dxs[o], 1.0) for o in range(n)]
+        ms = timed(torch, lambda: term.launch(outs, labels, 1, None, nll, 3, stream), max(a.steps, 50))
+        print('kfn_reproj_loss_grad, %d output(s), %d cells: %.4f ms' % (n, B * h * w, ms))
+    aug = Augmenter(B, a.height, a.width)
+    pm = torch.zeros(h, w, 2, device='cuda')
+    params = AugmentParams(ENLARGE, angle=17.0, x1=0.05, y1=0.1, ratio=0.85)
+    ms = timed(torch, lambda: aug.pixel_map(params, DepthCamera(), pm, stream), max(a.steps, 50))
+    print('kfn_augment_pixel_map, %dx%d: %.4f ms' % (h, w, ms))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--height', type=int, default=480)
@@ -287,8 +353,11 @@ def main(argv=None):
     ap.add_argument('--oflownet', action='store_true', help='time the step of OFlowNetTrainer (stage 2) and the launches it adds')
     ap.add_argument('--pairs', type=int, default=4, help='--oflownet: pairs of frames per step')
     ap.add_argument('--fp16', action='store_true', help='time the mixed-precision step beside the fp32 step')
-    ap.add_argument('--rounds', type=int, default=5, help='--fp16: timing windows per variant, taken in turns')
+    ap.add_argument('--rounds', type=int, default=5, help='--fp16, --reproj: timing windows per variant, taken in turns')
+    ap.add_argument('--reproj', action='store_true', help='time the step with the reprojection term beside the plain step')
     a = ap.parse_args(argv)
+    if a.reproj:
+        return reproj(a)
     if a.fp16:
         return fp16(a)
     if a.joint:
