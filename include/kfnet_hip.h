@@ -136,7 +136,9 @@ typedef struct kfn_conv_desc {
   int32_t stride;       /* 1 or 2 */
   int32_t transposed;   /* 0 = conv2d SAME, 1 = conv2d_transpose SAME (stride 2) */
   int32_t relu;         /* fuse tf.nn.relu */
-  int32_t epilogue;     /* KFN_EPI_* applied after bias(+relu) */
+  int32_t epilogue;     /* KFN_EPI_* applied after bias(+relu).  Forward convolutions only: a transposed call with an
+                         * epilogue, and any value outside KFN_EPI_NONE .. KFN_EPI_EXP_1E2, is KFN_ERR_ARG (both used to
+                         * return KFN_OK with the epilogue not applied; no caller in this repository passed either). */
   int32_t config;       /* 0 = auto tile choice, else KFN_CFG_* */
   int32_t operand_dtype; /* KFN_OPERAND_F32 (exact fp32 MFMA) or KFN_OPERAND_F16: operands rounded
                           * to fp16 while staged, fp32 accumulate on v_mfma_f32_32x32x16_f16

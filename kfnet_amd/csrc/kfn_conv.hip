@@ -1107,6 +1107,11 @@ int validate(const kfn_conv_desc* d) {
   KFN_REQUIRE(d->kh > 0 && d->kw > 0 && d->kh * d->kw <= 32, "kfn_conv2d_nhwc: bad kernel %dx%d", d->kh, d->kw);
   KFN_REQUIRE(d->stride == 1 || d->stride == 2, "kfn_conv2d_nhwc: stride %d unsupported", d->stride);
   KFN_REQUIRE(!d->transposed || d->stride == 2, "kfn_conv2d_nhwc: transposed conv needs stride 2");
+  // an epilogue the kernel would not apply is refused, not dropped: the head epilogues are compiled into the forward
+  // 32-column instantiations only (HEAD_EPI), and their switch has no case for an unknown value
+  KFN_REQUIRE(d->epilogue >= KFN_EPI_NONE && d->epilogue <= KFN_EPI_EXP_1E2, "kfn_conv2d_nhwc: unknown epilogue %d", d->epilogue);
+  KFN_REQUIRE(!d->transposed || d->epilogue == KFN_EPI_NONE,
+              "kfn_conv2d_nhwc: epilogue %d on a transposed convolution (head epilogues are forward only)", d->epilogue);
   KFN_REQUIRE(d->epilogue != KFN_EPI_L2NORM || d->Cout == 32, "kfn_conv2d_nhwc: L2NORM epilogue needs Cout == 32");
   return KFN_OK;
 }
@@ -1231,7 +1236,7 @@ extern "C" int kfn_conv2d_nhwc(const kfn_conv_desc* d, const float* x, const flo
   const int cfg = pick_config(d, a.M);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (x3) {
-    KFN_REQUIRE(!d->transposed, "kfn_conv2d_nhwc: f16x3 operands are implemented for forward convolutions only");
+    KFN_REQUIRE(!d->transposed, "kfn_conv2d_nhwc: operand_dtype KFN_OPERAND_F16X3 is implemented for forward convolutions only");
     return dispatch_cfg<16, MODE_CONV, PREC_F16X3>(cfg, a, s);
   }
   if (x16 || y16) {
