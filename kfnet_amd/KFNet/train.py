@@ -26,12 +26,10 @@ its weights: 50 in L_measure (:246-248), 10 in L_temporal (:270-272), 10 in L_KF
 other ones.  It reads the poses that pose_list.txt of I names and the intrinsics of the camera flags; the
 printed line then ends with the three values of `l_reproj` (measure~temporal~KF).
 """
-import argparse
 import sys
-import time
 from datetime import datetime
 
-from .. import modes
+from .. import modes, train_cli
 from ..reproj import STAGE3_WEIGHTS as REPROJ_WEIGHTS
 from ..SCoordNet.train import build_parser as stage1_parser, schedule
 
@@ -90,20 +88,17 @@ def main(argv=None):
         return 1
     if reproj is not None and not any(reproj):
         reproj = None
-    if not a.model_folder:
-        print('--model_folder is required: the snapshots go there', file=sys.stderr)
-        return 1
-    if a.display < 1 or a.snapshot < 1 or a.groups < 1:
-        print('--display, --snapshot and --groups must be >= 1', file=sys.stderr)
+    message = train_cli.check_flags(a, ('display', 'snapshot', 'groups'))
+    if message:
+        print(message, file=sys.stderr)
         return 1
     from ..train_kfnet import GROUP, group_indices, group_list, sequence_length, start_step
     stepvalue, max_steps = schedule(a.scene, a.stepvalue, a.max_steps)
     length = sequence_length(a.scene) if a.sequence_length is None else a.sequence_length
     from ..batches import open_source
-    from ..staging import check_size
     a.batch = a.groups * GROUP                       # what a DepthSource sizes its labeler by
     try:
-        check_size(a.height, a.width, '--height and --width')
+        train_cli.check_size(a)
         if length < GROUP:
             raise ValueError('--sequence_length must be at least %d' % GROUP)
         source = open_source(a, False, needs_poses=reproj is not None)
@@ -127,38 +122,22 @@ def main(argv=None):
         if not any(k.startswith(scope + '/') for k in W):
             W.update(initial_weights(a.seed, scopes=(scope,)))
             print('nothing restores %s/*: starting from untrained weights (seed %d)' % (scope, a.seed))
-    import torch
-    torch.cuda.set_device(a.gpu)
-    tr = KFNetTrainer(W, image_size=(a.height, a.width), groups=a.groups, transform=source.transform, base_lr=a.base_lr,
-                      gamma=a.gamma, stepvalue=stepvalue, weight_decay=a.weight_decay, loss_clip=a.loss_clip,
-                      smooth_weight=a.smooth_weight, device='cuda:%d' % a.gpu, train_flownet=a.joint, reproj_weights=reproj,
-                      camera=camera)
-    if state is not None:
-        tr.load_state(state)
-    tr.global_step = start_step(step, stepvalue, a.reset_step, a.scoordnet, a.oflownet)
-    print('----------------------------------')
-    print('scene: ', a.scene)
-    print('training image number: ', source.count)
-    print('batch size: ', a.groups * GROUP)
-    print('step value: ', stepvalue)
-    print('max steps: ', max_steps)
-    print('current step: ', tr.global_step)
-    print('----------------------------------')
-    while tr.global_step < max_steps:
-        t0 = time.time()
-        indices = group_indices(tr.global_step, a.groups, groups, a.shuffle, a.seed)
+
+    def make_trainer(**kw):
+        return KFNetTrainer(W, groups=a.groups, transform=source.transform, smooth_weight=a.smooth_weight, train_flownet=a.joint,
+                            reproj_weights=reproj, camera=camera, **kw)
+    tr = train_cli.start(a, stepvalue, make_trainer, state, start_step(step, stepvalue, a.reset_step, a.scoordnet, a.oflownet),
+                         (('scene: ', a.scene), ('training image number: ', source.count), ('batch size: ', a.groups * GROUP),
+                          ('step value: ', stepvalue), ('max steps: ', max_steps)))
+
+    def batch(step):
+        indices = group_indices(step, a.groups, groups, a.shuffle, a.seed)
         frames, labels = source.batch(indices, False)
-        if reproj is not None:
-            tr.set_poses(source.poses[indices])
-        stats = tr.step(frames, labels)
-        s = tr.global_step
-        if s % a.display == 0 or s == max_steps:
-            line = dict(stats)           # the read-back waits for the step
-            print(format_line(datetime.now(), s // source.count, s, max_steps, indices[:GROUP], line, time.time() - t0), flush=True)
-        if s % a.snapshot == 0 or s == max_steps:
-            print('snapshot: %s, %s' % tr.save(a.model_folder, s), flush=True)
-    torch.cuda.synchronize()
-    return 0
+        return indices, frames, labels, (source.poses[indices] if reproj is not None else None), {}
+
+    def line(stats, s, indices, duration):
+        return format_line(datetime.now(), s // source.count, s, max_steps, indices[:GROUP], stats, duration)
+    return train_cli.loop(tr, max_steps, a.display, a.snapshot, a.model_folder, batch, line)
 
 
 if __name__ == '__main__':

@@ -22,8 +22,9 @@ source does read transform.txt).  --augment is refused: a pair would need one dr
 """
 import argparse
 import sys
-import time
 from datetime import datetime
+
+from .. import train_cli
 
 STEPVALUE = 100000
 SEQUENCE_LENGTH = 1000
@@ -36,31 +37,11 @@ def format_line(now, epoch, step, max_steps, pair, s, duration):
 
 def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('--input_folder', default='')
-    ap.add_argument('--model_folder', default='')
+    train_cli.add_shared_flags(ap, STEPVALUE, augment='refused: not built for pairs',
+                               fp16='refused: mixed precision is built for SCoordNet.train only')
     ap.add_argument('--pairs', type=int, default=4, help='pairs of frames per step')
     ap.add_argument('--sequence_length', type=int, default=SEQUENCE_LENGTH,
                     help='no pair reaches across a range of this many frames of the list (default 1000)')
-    ap.add_argument('--base_lr', type=float, default=1e-4)
-    ap.add_argument('--max_steps', type=int, default=None)
-    ap.add_argument('--display', type=int, default=10)
-    ap.add_argument('--stepvalue', type=int, default=STEPVALUE)
-    ap.add_argument('--snapshot', type=int, default=5000)
-    ap.add_argument('--gamma', type=float, default=0.5)
-    ap.add_argument('--weight_decay', type=float, default=1e-4)
-    ap.add_argument('--shuffle', action='store_true')
-    ap.add_argument('--reset_step', type=int, default=-1)
-    ap.add_argument('--gpu', type=int, default=0)
-    ap.add_argument('--height', type=int, default=480)
-    ap.add_argument('--width', type=int, default=640)
-    ap.add_argument('--seed', type=int, default=0)
-    ap.add_argument('--loss_clip', type=float, default=None)
-    ap.add_argument('--synthetic', type=int, default=0, help='train on this many seeded synthetic frames and labels')
-    ap.add_argument('--augment', action='store_true', help='refused: not built for pairs')
-    ap.add_argument('--fp16', action='store_true', help='refused: mixed precision is built for SCoordNet.train only')
-    ap.add_argument('--depth', action='store_true', help='make the labels on the device from depth_list.txt and pose_list.txt')
-    from ..labels import add_camera_flags
-    add_camera_flags(ap)
     return ap
 
 
@@ -72,19 +53,16 @@ def main(argv=None):
     if a.fp16:
         print('--fp16 is refused: mixed precision is built for stage 1 (SCoordNet.train) only', file=sys.stderr)
         return 1
-    if not a.model_folder:
-        print('--model_folder is required: the snapshots go there', file=sys.stderr)
-        return 1
-    if a.display < 1 or a.snapshot < 1 or a.pairs < 1 or a.stepvalue < 1:
-        print('--display, --snapshot, --pairs and --stepvalue must be >= 1', file=sys.stderr)
+    message = train_cli.check_flags(a, ('display', 'snapshot', 'pairs', 'stepvalue'))
+    if message:
+        print(message, file=sys.stderr)
         return 1
     stepvalue, max_steps = a.stepvalue, (5 * a.stepvalue if a.max_steps is None else a.max_steps)
     from ..batches import open_source
-    from ..staging import check_size
     from ..train_kfnet import group_indices, group_list
     a.batch = 2 * a.pairs                            # what a DepthSource sizes its labeler by
     try:
-        check_size(a.height, a.width, '--height and --width')
+        train_cli.check_size(a)
         if a.sequence_length < 2:
             raise ValueError('--sequence_length must be at least 2')
         source = open_source(a, False, needs_transform=False)
@@ -105,33 +83,19 @@ def main(argv=None):
         from ..weights import initial_weights
         W, state = initial_weights(a.seed, scopes=(SCOPE,)), None
         print('no %s/* snapshot in %s: starting from untrained weights (seed %d)' % (SCOPE, a.model_folder, a.seed))
-    import torch
-    torch.cuda.set_device(a.gpu)
-    tr = OFlowNetTrainer(W, image_size=(a.height, a.width), pairs=a.pairs, base_lr=a.base_lr, gamma=a.gamma, stepvalue=stepvalue,
-                         weight_decay=a.weight_decay, loss_clip=a.loss_clip, device='cuda:%d' % a.gpu)
-    if state is not None:
-        tr.load_state(state)
-    tr.global_step = step if a.reset_step < 0 else a.reset_step
-    print('----------------------------------')
-    print('training image number: ', source.count)
-    print('pairs per step: ', a.pairs)
-    print('step value: ', stepvalue)
-    print('max steps: ', max_steps)
-    print('current step: ', tr.global_step)
-    print('----------------------------------')
-    while tr.global_step < max_steps:
-        t0 = time.time()
-        indices = group_indices(tr.global_step, a.pairs, pairs, a.shuffle, a.seed)
+    tr = train_cli.start(a, stepvalue, lambda **kw: OFlowNetTrainer(W, pairs=a.pairs, **kw), state,
+                         step if a.reset_step < 0 else a.reset_step,
+                         (('training image number: ', source.count), ('pairs per step: ', a.pairs), ('step value: ', stepvalue),
+                          ('max steps: ', max_steps)))
+
+    def batch(step):
+        indices = group_indices(step, a.pairs, pairs, a.shuffle, a.seed)
         frames, labels = source.batch(indices, False)
-        stats = tr.step(frames, labels)
-        s = tr.global_step
-        if s % a.display == 0 or s == max_steps:
-            line = dict(stats)           # the read-back waits for the step
-            print(format_line(datetime.now(), (s * a.pairs) // len(pairs), s, max_steps, indices[:2], line, time.time() - t0), flush=True)
-        if s % a.snapshot == 0 or s == max_steps:
-            print('snapshot: %s, %s' % tr.save(a.model_folder, s), flush=True)
-    torch.cuda.synchronize()
-    return 0
+        return indices, frames, labels, None, {}
+
+    def line(stats, s, indices, duration):
+        return format_line(datetime.now(), (s * a.pairs) // len(pairs), s, max_steps, indices[:2], stats, duration)
+    return train_cli.loop(tr, max_steps, a.display, a.snapshot, a.model_folder, batch, line)
 
 
 if __name__ == '__main__':

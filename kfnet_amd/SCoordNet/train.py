@@ -28,10 +28,9 @@ is augmented with the batch (KFNet/train.py:181-187).  The printed line then end
 """
 import argparse
 import sys
-import time
 from datetime import datetime
 
-from .. import modes
+from .. import modes, train_cli
 from ..reproj import STAGE1_WEIGHT as REPROJ_WEIGHT
 
 STEPVALUE = {'chess': 100000, 'fire': 30000, 'heads': 60000, 'office': 100000, 'pumpkin': 100000, 'redkitchen': 100000,
@@ -65,36 +64,15 @@ def schedule(scene, stepvalue=None, max_steps=None):
 def build_parser(reproj_flag=True):
     """reproj_flag = False leaves --reproj to the caller (KFNet.train's takes no number)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('--input_folder', default='')
-    ap.add_argument('--model_folder', default='')
+    train_cli.add_shared_flags(ap)
     ap.add_argument('--scene', default='')
-    ap.add_argument('--base_lr', type=float, default=1e-4)
-    ap.add_argument('--max_steps', type=int, default=None)
-    ap.add_argument('--display', type=int, default=10)
-    ap.add_argument('--stepvalue', type=int, default=None)
-    ap.add_argument('--snapshot', type=int, default=5000)
-    ap.add_argument('--gamma', type=float, default=0.5)
-    ap.add_argument('--weight_decay', type=float, default=1e-4)
-    ap.add_argument('--shuffle', action='store_true')
-    ap.add_argument('--reset_step', type=int, default=-1)
-    ap.add_argument('--gpu', type=int, default=0)
     ap.add_argument('--batch', type=int, default=4)
-    ap.add_argument('--height', type=int, default=480)
-    ap.add_argument('--width', type=int, default=640)
-    ap.add_argument('--seed', type=int, default=0)
-    ap.add_argument('--loss_clip', type=float, default=None)
     ap.add_argument('--smooth_weight', type=float, default=50.0)
-    ap.add_argument('--synthetic', type=int, default=0, help='train on this many seeded synthetic frames and labels')
-    ap.add_argument('--augment', action='store_true', help='brightness, contrast, rotation and zoom / shrink per batch')
     ap.add_argument('--augment_seed', type=int, default=None, help='seed of the augmentation draws (default: --seed)')
-    ap.add_argument('--depth', action='store_true', help='make the labels on the device from depth_list.txt and pose_list.txt')
-    ap.add_argument('--fp16', action='store_true', help='mixed precision: fp16 MFMA operands under dynamic loss scaling')
     ap.add_argument('--loss_scale', type=int, default=None, help='initial loss scale of --fp16, a power of two (default 32768)')
     if reproj_flag:
         ap.add_argument('--reproj', type=float, nargs='?', const=REPROJ_WEIGHT, default=None, metavar='W',
                         help='add W (default 50) times the reprojection loss; needs pose_list.txt and the camera flags')
-    from ..labels import add_camera_flags
-    add_camera_flags(ap)
     return ap
 
 
@@ -103,11 +81,9 @@ def main(argv=None):
     if a.scene not in modes.SCENES:
         print('Invalid scene:', a.scene)
         return 1
-    if not a.model_folder:
-        print('--model_folder is required: the snapshots go there', file=sys.stderr)
-        return 1
-    if a.display < 1 or a.snapshot < 1 or a.batch < 1:
-        print('--display, --snapshot and --batch must be >= 1', file=sys.stderr)
+    message = train_cli.check_flags(a, ('display', 'snapshot', 'batch'))
+    if message:
+        print(message, file=sys.stderr)
         return 1
     if a.loss_scale is not None and not a.fp16:
         print('--loss_scale belongs to --fp16', file=sys.stderr)
@@ -122,11 +98,10 @@ def main(argv=None):
     reproj = a.reproj or 0.0
     stepvalue, max_steps = schedule(a.scene, a.stepvalue, a.max_steps)
     from ..batches import open_source
-    from ..staging import check_size
     from ..labels import camera_of
     from ..train import SCoordNetTrainer, batch_indices, restore
     try:
-        check_size(a.height, a.width, '--height and --width')
+        train_cli.check_size(a)
         source = open_source(a, SCoordNetTrainer.needs_full_resolution(a.augment), needs_poses=reproj > 0.0)
         camera = camera_of(a) if reproj > 0.0 else None
     except (OSError, ValueError) as e:
@@ -137,41 +112,26 @@ def main(argv=None):
         from ..weights import initial_weights
         W = initial_weights(a.seed)
         print('no snapshot in %s: starting from untrained weights (seed %d)' % (a.model_folder, a.seed))
-    import torch
-    torch.cuda.set_device(a.gpu)
-    tr = SCoordNetTrainer(W, image_size=(a.height, a.width), batch=a.batch, transform=source.transform, base_lr=a.base_lr,
-                          gamma=a.gamma, stepvalue=stepvalue, weight_decay=a.weight_decay, loss_clip=a.loss_clip,
-                          smooth_weight=a.smooth_weight, device='cuda:%d' % a.gpu, precision='fp16' if a.fp16 else 'fp32',
-                          loss_scale=loss_scale, reproj_weight=reproj, camera=camera)
-    if state is not None:
-        tr.load_state(state)
-    tr.global_step = step if a.reset_step < 0 else a.reset_step
+
+    def make_trainer(**kw):
+        return SCoordNetTrainer(W, batch=a.batch, transform=source.transform, smooth_weight=a.smooth_weight,
+                                precision='fp16' if a.fp16 else 'fp32', loss_scale=loss_scale, reproj_weight=reproj,
+                                camera=camera, **kw)
+    tr = train_cli.start(a, stepvalue, make_trainer, state, step if a.reset_step < 0 else a.reset_step,
+                         (('scene: ', a.scene), ('training image number: ', source.count), ('batch size: ', a.batch),
+                          ('step value: ', stepvalue), ('max steps: ', max_steps)))
     from ..augment import draw
     augment_seed = a.seed if a.augment_seed is None else a.augment_seed
-    print('----------------------------------')
-    print('scene: ', a.scene)
-    print('training image number: ', source.count)
-    print('batch size: ', a.batch)
-    print('step value: ', stepvalue)
-    print('max steps: ', max_steps)
-    print('current step: ', tr.global_step)
-    print('----------------------------------')
-    while tr.global_step < max_steps:
-        t0 = time.time()
-        params = draw(augment_seed, tr.global_step) if a.augment else None
-        indices = batch_indices(tr.global_step, a.batch, source.count, a.shuffle, a.seed)
+
+    def batch(step):
+        params = draw(augment_seed, step) if a.augment else None
+        indices = batch_indices(step, a.batch, source.count, a.shuffle, a.seed)
         frames, labels = source.batch(indices, tr.needs_full_resolution(a.augment))
-        if reproj > 0.0:
-            tr.set_poses(source.poses[indices])
-        stats = tr.step(frames, labels, augment=params)
-        s = tr.global_step
-        if s % a.display == 0 or s == max_steps:
-            line = dict(stats)           # the read-back waits for the step
-            print(format_line(datetime.now(), (s * a.batch) // source.count, s, max_steps, line, time.time() - t0), flush=True)
-        if s % a.snapshot == 0 or s == max_steps:
-            print('snapshot: %s, %s' % tr.save(a.model_folder, s), flush=True)
-    torch.cuda.synchronize()
-    return 0
+        return indices, frames, labels, (source.poses[indices] if reproj > 0.0 else None), dict(augment=params)
+
+    def line(stats, s, indices, duration):
+        return format_line(datetime.now(), (s * a.batch) // source.count, s, max_steps, stats, duration)
+    return train_cli.loop(tr, max_steps, a.display, a.snapshot, a.model_folder, batch, line)
 
 
 if __name__ == '__main__':

@@ -1,6 +1,6 @@
-"""What the classes that feed training batches to the device share (SCoordNetTrainer, Augmenter, DepthLabeler) and the two
-command lines above them: the rule for an image size, the stream the launches go to, and the copy of a host or device batch
-into a device buffer.  A leaf module: torch is imported where it is used, nothing else of the project is."""
+"""What the classes that feed training batches to the device share (the trainers, Augmenter, DepthLabeler) and the command
+lines above them: the rule for an image size, the stream the launches go to, the copy of a host or device batch into a
+device buffer, and the labels' copy.  A leaf module: torch is imported where it is used, nothing else of the project is."""
 import numpy as np
 
 
@@ -27,3 +27,20 @@ def stage(dst, src, dtype, shape, name):
         raise ValueError('%s must be %s %s, got %s %s' % (name, str(dtype).replace('torch.', ''), list(shape),
                                                          str(src.dtype).replace('torch.', ''), list(src.shape)))
     dst.copy_(src, non_blocking=True)
+
+
+def stage_labels(buf, labels, batch, image_size, grid, device):
+    """Copies a batch's labels, a numpy array or a tensor, full-resolution [B,H,W,4] or grid-sized [B,h,w,4], into a float32
+    buffer on `device` without blocking: their shape picks the stride, so the copy is torch's own.  `buf` is the buffer of
+    the call before (None at first), reused when the shape repeats.  Returns (the buffer, the stride at which the loss
+    reads it: 8 or 1)."""
+    import torch
+    B, (H, Wd), (h, w) = batch, image_size, grid
+    lb = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.float32))
+    if tuple(lb.shape) not in ((B, H, Wd, 4), (B, h, w, 4)):
+        raise ValueError('labels must be float32 [%d,%d,%d,4] or grid-sized [%d,%d,%d,4], got %s'
+                         % (B, H, Wd, B, h, w, tuple(lb.shape)))
+    if buf is None or buf.shape != lb.shape:
+        buf = torch.zeros(tuple(lb.shape), dtype=torch.float32, device=device)
+    buf.copy_(lb.to(torch.float32), non_blocking=True)
+    return buf, (8 if tuple(lb.shape) == (B, H, Wd, 4) else 1)

@@ -28,18 +28,16 @@ applies the update only if every gradient is finite.  `global_step` then counts 
 rate and the batch stream; the host cannot know whether a step was applied), Adam's t counts applied ones on the device.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _lib, staging
 from .cnn_wrapper.SCoordNet import layers
+from .train_common import BETA1, BETA2, EPSILON, LazyStats, ParamStore, learning_rate, read_snapshot, size_query
+from .train_common import adam_lr_t, snapshot_paths  # noqa: F401  (callers of this module read them here)
 
 LAYERS = layers()                                 # (name, kernel, Cin, Cout, stride, relu), the architecture's own table
 SCOPE = 'ScoreNet'
-BETA1, BETA2, EPSILON = 0.9, 0.999, 1e-8          # tf.train.AdamOptimizer defaults (KFNet/train.py:313)
-WEIGHTS_NAME = 'kfnet_weights-%d.npz'             # tools.io.get_snapshot's kind: SCoordNet.eval --model_folder reads it
-STATE_NAME = 'kfnet_train_state-%d.npz'           # NOT matched by get_snapshot's kfnet_weights*.npz
 PRECISIONS = ('fp32', 'fp16')
 MAX_LOSS_SCALE = 2 ** 24
 
@@ -56,16 +54,6 @@ def f16_layer(kernel, cin, cout):
 def power_of_two(x):
     m, _ = np.frexp(float(x))
     return float(x) > 0 and m == 0.5
-
-
-def learning_rate(base_lr, gamma, stepvalue, global_step):
-    """tf.train.exponential_decay without staircase (KFNet/train.py:306-310): a real-valued exponent."""
-    return float(base_lr) * float(gamma) ** (float(global_step) / float(stepvalue))
-
-
-def adam_lr_t(lr, t):
-    """lr_t of TensorFlow's Adam for update number t (from 1)."""
-    return lr * np.sqrt(1.0 - BETA2 ** t) / (1.0 - BETA1 ** t)
 
 
 def batch_indices(step, batch, count, shuffle=False, seed=0):
@@ -115,40 +103,34 @@ def beta_powers(t):
     return p1, p2
 
 
-def snapshot_paths(folder, step):
-    return os.path.join(folder, WEIGHTS_NAME % step), os.path.join(folder, STATE_NAME % step)
-
-
-class StepStats(object):
-    """What a step reports, read from the device on first access (so that steps queue): loss, l_measure, l_smooth,
-    a_measure, pixels, lr.  dict(stats) gives plain floats."""
+class StepStats(LazyStats):
+    """loss, l_measure, l_smooth, a_measure, pixels, lr."""
     KEYS = ('loss', 'l_measure', 'l_smooth', 'a_measure', 'pixels', 'lr')
     SCALE_KEYS = ('loss_scale', 'skipped')      # precision='fp16' only: the scale after this step, the steps skipped so far
     REPROJ_KEYS = ('l_reproj',)                 # reproj_weight > 0 only: R itself; `loss` then includes reproj_weight * R
 
     def __init__(self, stats_dev, lr, scale_dev=None, reproj_dev=None):
-        self._dev, self._lr, self._host, self._scale_dev, self._reproj_dev = stats_dev, lr, None, scale_dev, reproj_dev
+        LazyStats.__init__(self, stats_dev, lr)
+        self._scale_dev, self._reproj_dev = scale_dev, reproj_dev
 
     def keys(self):
         return (list(self.KEYS) + (list(self.SCALE_KEYS) if self._scale_dev is not None else []) +
                 (list(self.REPROJ_KEYS) if self._reproj_dev is not None else []))
 
-    def __getitem__(self, k):
-        if self._host is None:
-            s = self._dev.cpu().numpy()
-            # kfn_coord_loss_grad's stats; valid = sum(mask) + 1, the reference logs np.sum(masks)
-            self._host = dict(loss=float(s[4]), l_measure=float(s[0]), l_smooth=float(s[1]), a_measure=float(s[2]),
-                              pixels=float(s[3]) - 1.0, lr=self._lr)
-            if self._scale_dev is not None:
-                st = _lib.LossScaleState.from_buffer_copy(self._scale_dev.cpu().numpy().tobytes())
-                self._host.update(loss_scale=float(st.scale), skipped=int(st.skipped))
-            if self._reproj_dev is not None:
-                r = self._reproj_dev.cpu().numpy()       # kfn_reproj_loss_grad's stats: R, ., ., weight * R
-                self._host.update(l_reproj=float(r[0]), loss=float(s[4]) + float(r[3]))
-        return self._host[k]
+    def _decode(self, s):
+        # kfn_coord_loss_grad's stats; valid = sum(mask) + 1, the reference logs np.sum(masks)
+        host = dict(loss=float(s[4]), l_measure=float(s[0]), l_smooth=float(s[1]), a_measure=float(s[2]),
+                    pixels=float(s[3]) - 1.0, lr=self._lr)
+        if self._scale_dev is not None:
+            st = _lib.LossScaleState.from_buffer_copy(self._scale_dev.cpu().numpy().tobytes())
+            host.update(loss_scale=float(st.scale), skipped=int(st.skipped))
+        if self._reproj_dev is not None:
+            r = self._reproj_dev.cpu().numpy()       # kfn_reproj_loss_grad's stats: R, ., ., weight * R
+            host.update(l_reproj=float(r[0]), loss=float(s[4]) + float(r[3]))
+        return host
 
 
-class SCoordNetTrainer(object):
+class SCoordNetTrainer(ParamStore):
     def __init__(self, weights, image_size=(480, 640), batch=4, transform=None, base_lr=1e-4, gamma=0.5, stepvalue=80000,
                  weight_decay=1e-4, loss_clip=None, smooth_weight=50.0, device='cuda:0', precision='fp32', loss_scale=2 ** 15,
                  growth_interval=2000, reproj_weight=0.0, camera=None):
@@ -173,17 +155,11 @@ class SCoordNetTrainer(object):
         self.precision, self.loss_scale, self.growth_interval = precision, float(loss_scale), int(growth_interval)
         self.f16 = [precision == 'fp16' and f16_layer(k, ci, co) for _, k, ci, co, _, _ in LAYERS]
         self.lib = _lib.load()
-        self.torch = torch
-        self.device = torch.device(device)
         self.image_size, self.batch = (H, Wd), batch
         self.grid = (H // 8, Wd // 8)
-        self.base_lr, self.gamma, self.stepvalue = float(base_lr), float(gamma), float(stepvalue)
-        self.weight_decay = float(weight_decay)
         self.loss_clip = None if loss_clip is None else float(loss_clip)
         self.smooth_weight = float(smooth_weight)
         self.transform = None if transform is None else np.asarray(transform, dtype=np.float32).reshape(4, 4)
-        self.global_step = 0
-        self.adam_t = 0
         from .reproj import check_weights
         self.reproj_weight = check_weights(reproj_weight, 1)[0]
         self.reproj = None                # kfnet_amd.reproj.ReprojTerm when the weight is positive
@@ -191,21 +167,12 @@ class SCoordNetTrainer(object):
         self._poses_set = False           # set_poses() has run since the last step
         self._pixel_map_live = False      # the staged batch is augmented: the rays come from self.pixel_map
 
-        # flat parameter buffer: kernel then bias per layer, TF HWIO order (every offset a multiple of 4 floats)
-        self.slots = {}
-        off = 0
-        for li, (name, k, ci, co, _, _) in enumerate(LAYERS):
-            for kind, shape in (('kernel', (k, k, ci, co)), ('bias', (co,))):
-                n = int(np.prod(shape))
-                self.slots[self.variable(li, kind)] = (off, n, shape)
-                off += -(-n // 4) * 4
-        self.num_floats = off
+        # the flat parameter store: kernel then bias per layer, TF HWIO order
+        specs = [(self.variable(li, kind), shape) for li, (name, k, ci, co, _, _) in enumerate(LAYERS)
+                 for kind, shape in (('kernel', (k, k, ci, co)), ('bias', (co,)))]
+        ParamStore.__init__(self, specs, device, base_lr, gamma, stepvalue, weight_decay)
         with torch.cuda.device(self.device):
             f32 = dict(dtype=torch.float32, device=self.device)
-            self.params = torch.zeros(off, **f32)
-            self.grads = torch.zeros(off, **f32)
-            self.m = torch.zeros(off, **f32)
-            self.v = torch.zeros(off, **f32)
             self.set_weights(weights)
 
             # activations (each layer's output after its ReLU) and the gradients with respect to them
@@ -214,7 +181,7 @@ class SCoordNetTrainer(object):
             self._augmenter = None        # kfnet_amd.augment.Augmenter, made by the first step(..., augment=params)
             self.shapes, self.act, self.dact, self.packs = [], [], [], []
             h, w = H, Wd
-            ws_bytes = self._first_ws_bytes(batch, H, Wd, LAYERS[0][3])
+            ws_bytes = size_query(self.lib.kfn_first_conv_u8_grad_weights_workspace_bytes, batch, H, Wd, LAYERS[0][3])
             for li, (name, k, ci, co, s, relu) in enumerate(LAYERS):
                 hin, win = h, w
                 h, w = -(-h // s), -(-w // s)
@@ -225,18 +192,14 @@ class SCoordNetTrainer(object):
                     self.packs.append(None)
                     continue
                 pk = dict(f32, dtype=torch.float16) if self.f16[li] else f32     # the same layout, halfs under fp16 operands
-                fwd = torch.zeros(self._pack_floats(k, ci, co, _lib.PACK_FORWARD), **pk)
+                fwd = torch.zeros(size_query(self.lib.kfn_pack_conv_weights_floats, k, k, ci, co, _lib.PACK_FORWARD), **pk)
                 kind = _lib.PACK_INPUT_GRAD_S2 if s == 2 else _lib.PACK_INPUT_GRAD_S1
-                back = torch.zeros(self._pack_floats(k, ci, co, kind), **pk)
+                back = torch.zeros(size_query(self.lib.kfn_pack_conv_weights_floats, k, k, ci, co, kind), **pk)
                 self.packs.append((fwd, back, kind))
                 d = self._fwd_desc(li)
-                nbytes = C.c_size_t()
-                _lib.check(self.lib.kfn_conv2d_grad_weights_workspace_bytes(C.byref(d), C.byref(nbytes)),
-                           'kfn_conv2d_grad_weights_workspace_bytes[%s]' % name)
-                ws_bytes = max(ws_bytes, nbytes.value)
+                ws_bytes = max(ws_bytes, size_query(self.lib.kfn_conv2d_grad_weights_workspace_bytes, C.byref(d)))
             self.workspace = torch.zeros(-(-ws_bytes // 4), **f32)
             self.stats = torch.zeros(8, **f32)
-            self._packs_stale = True
             if self.reproj_weight > 0.0:
                 from .reproj import ReprojTerm
                 self.reproj = ReprojTerm(batch, self.grid[0], self.grid[1], camera, self.transform, self.device)
@@ -245,18 +208,7 @@ class SCoordNetTrainer(object):
                 self.scale_state = torch.zeros(C.sizeof(_lib.LossScaleState), dtype=torch.uint8, device=self.device)
                 self._write_scale_state(self.loss_scale, 0, 0, 0, 1.0, 1.0)
 
-    # ---- sizes and descriptors ------------------------------------------------------------------------------------
-    def _first_ws_bytes(self, n, h, w, c1):
-        nbytes = C.c_size_t()
-        _lib.check(self.lib.kfn_first_conv_u8_grad_weights_workspace_bytes(n, h, w, c1, C.byref(nbytes)),
-                   'kfn_first_conv_u8_grad_weights_workspace_bytes')
-        return nbytes.value
-
-    def _pack_floats(self, k, ci, co, kind):
-        n = C.c_size_t()
-        _lib.check(self.lib.kfn_pack_conv_weights_floats(k, k, ci, co, kind, C.byref(n)), 'kfn_pack_conv_weights_floats')
-        return n.value
-
+    # ---- descriptors ----------------------------------------------------------------------------------------------
     def _fwd_desc(self, li):
         """The forward convolution of layer li; as the weight gradient's descriptor its ldy is dZ's pixel stride."""
         name, k, ci, co, s, relu = LAYERS[li]
@@ -275,34 +227,7 @@ class SCoordNetTrainer(object):
     def _ptr(self, buf, li, kind):
         return buf.data_ptr() + 4 * self.slots[self.variable(li, kind)][0]
 
-    # ---- weights and optimiser state ---------------------------------------------------------------------------------
-    def _fill(self, buf, arrays, prefix=''):
-        """Every variable's slot of the flat buffer `buf` from arrays[prefix + its name]."""
-        for name, (off, n, shape) in self.slots.items():
-            if prefix + name not in arrays:
-                raise KeyError('weights lack %s%s' % (prefix, name))
-            a = np.ascontiguousarray(np.asarray(arrays[prefix + name], dtype=np.float32))
-            if a.shape != tuple(shape):
-                raise ValueError('%s%s has shape %s, expected %s' % (prefix, name, a.shape, tuple(shape)))
-            buf[off:off + n].copy_(self.torch.from_numpy(a.reshape(-1)))
-
-    def set_weights(self, weights):
-        self._fill(self.params, weights)
-        self._packs_stale = True
-
-    def _named(self, buf, prefix=''):
-        host = buf.cpu().numpy()
-        return {prefix + name: host[off:off + n].reshape(shape).copy() for name, (off, n, shape) in self.slots.items()}
-
-    def weights(self):
-        """{TF variable name: float32 array}: what kfnet_amd.weights.save_npz stores and the engines load."""
-        return self._named(self.params)
-
-    def gradients(self):
-        """Debug view of the last step's gradients of the loss (without the regulariser, which kfn_adam_step adds), in TF
-        layout under the variables' names."""
-        return self._named(self.grads)
-
+    # ---- the loss-scale record beside the store's optimiser state ---------------------------------------------------
     def _write_scale_state(self, scale, good_steps, skipped, adam_t, beta1_power, beta2_power):
         rec = _lib.LossScaleState(beta1_power=beta1_power, beta2_power=beta2_power, scale=scale, good_steps=good_steps,
                                   overflow=0, skipped=skipped, adam_t=adam_t)
@@ -316,43 +241,27 @@ class SCoordNetTrainer(object):
                     beta1_power=float(rec.beta1_power), beta2_power=float(rec.beta2_power))
 
     def state(self):
-        """The Adam slots and the counters, as numpy arrays (an .npz's content); with precision='fp16' the loss-scale record
-        too, whose adam_t counts the APPLIED steps."""
-        if self.precision == 'fp16':
-            ls = self.loss_scale_state()
-            self.adam_t = ls['adam_t']
-        st = dict(global_step=np.int64(self.global_step), adam_t=np.int64(self.adam_t))
-        if self.precision == 'fp16':
-            st.update(loss_scale=np.float32(ls['scale']), loss_scale_good_steps=np.int64(ls['good_steps']),
-                      loss_scale_skipped=np.int64(ls['skipped']), adam_beta1_power=np.float64(ls['beta1_power']),
-                      adam_beta2_power=np.float64(ls['beta2_power']))
-        st.update(self._named(self.m, 'adam_m/'))
-        st.update(self._named(self.v, 'adam_v/'))
+        """The store's state; with precision='fp16' the loss-scale record too, whose adam_t counts the APPLIED steps."""
+        if self.precision != 'fp16':
+            return ParamStore.state(self)
+        ls = self.loss_scale_state()
+        self.adam_t = ls['adam_t']
+        st = ParamStore.state(self)
+        st.update(loss_scale=np.float32(ls['scale']), loss_scale_good_steps=np.int64(ls['good_steps']),
+                  loss_scale_skipped=np.int64(ls['skipped']), adam_beta1_power=np.float64(ls['beta1_power']),
+                  adam_beta2_power=np.float64(ls['beta2_power']))
         return st
 
     def load_state(self, st):
         """A state file written without the loss-scale record (before it existed, or by an fp32 run) loads with the
         constructor's scale, zero counters and the powers of beta that adam_t applied steps accumulate."""
-        self._fill(self.m, st, 'adam_m/')
-        self._fill(self.v, st, 'adam_v/')
-        self.global_step = int(st['global_step'])
-        self.adam_t = int(st['adam_t'])
+        ParamStore.load_state(self, st)
         if self.precision == 'fp16':
             if 'loss_scale' in st:
                 self._write_scale_state(float(st['loss_scale']), int(st['loss_scale_good_steps']), int(st['loss_scale_skipped']),
                                         self.adam_t, float(st['adam_beta1_power']), float(st['adam_beta2_power']))
             else:
                 self._write_scale_state(self.loss_scale, 0, 0, self.adam_t, *beta_powers(self.adam_t))
-
-    def save(self, folder, step=None):
-        """Writes kfnet_weights-<step>.npz (ScoreNet/* only) and kfnet_train_state-<step>.npz; returns the two paths."""
-        from .weights import save_npz
-        step = self.global_step if step is None else step
-        os.makedirs(folder, exist_ok=True)
-        wp, sp = snapshot_paths(folder, step)
-        save_npz(wp, self.weights())
-        np.savez(sp, **self.state())
-        return wp, sp
 
     # ---- one step ----------------------------------------------------------------------------------------------------
     @staticmethod
@@ -402,15 +311,8 @@ class SCoordNetTrainer(object):
             return 1
         self._pixel_map_live = False
         staging.stage(self.frames, frames_u8, torch.uint8, (B, H, Wd, 3), 'frames')
-        # the labels of either size, converted to float32: their shape picks the stride, so the copy is torch's own
-        lb = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.float32))
-        if tuple(lb.shape) not in ((B, H, Wd, 4), (B, h, w, 4)):
-            raise ValueError('labels must be float32 [%d,%d,%d,4] or grid-sized [%d,%d,%d,4], got %s'
-                             % (B, H, Wd, B, h, w, tuple(lb.shape)))
-        if self.labels is None or self.labels.shape != lb.shape:
-            self.labels = torch.zeros(tuple(lb.shape), dtype=torch.float32, device=self.device)
-        self.labels.copy_(lb.to(torch.float32), non_blocking=True)
-        return 8 if tuple(lb.shape) == (B, H, Wd, 4) else 1
+        self.labels, stride = staging.stage_labels(self.labels, labels, B, (H, Wd), (h, w), self.device)
+        return stride
 
     def forward_layer(self, li, stream):
         """Layer li's forward launch: self.act[li] from self.act[li - 1] (conv1a: from self.frames)."""
@@ -505,23 +407,16 @@ class SCoordNetTrainer(object):
         self.backward(stream)
 
     def apply_gradients(self, stream=None):
-        """TensorFlow's Adam on the flat buffer, with the regulariser's weight_decay * w folded into the gradient."""
+        """The store's Adam step; with precision='fp16' the guarded one: applied or skipped, the device decides, and its
+        record supplies Adam's bias correction."""
+        if self.precision != 'fp16':
+            return ParamStore.apply_gradients(self, stream)
         stream = staging.current_stream(self.device) if stream is None else stream
         lr = learning_rate(self.base_lr, self.gamma, self.stepvalue, self.global_step)
-        if self.precision == 'fp16':
-            # applied or skipped, the device decides; its record supplies Adam's bias correction
-            _lib.check(self.lib.kfn_adam_step_guarded(self.params.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                                      self.grads.data_ptr(), self.num_floats, lr, BETA1, BETA2, EPSILON,
-                                                      self.weight_decay, self.growth_interval, self.scale_state.data_ptr(),
-                                                      stream), 'kfn_adam_step_guarded')
-            self.global_step += 1
-            self._packs_stale = True
-            return lr
-        t = self.adam_t + 1
-        _lib.check(self.lib.kfn_adam_step(self.params.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.grads.data_ptr(),
-                                          self.num_floats, adam_lr_t(lr, t), BETA1, BETA2, EPSILON, self.weight_decay, stream),
-                   'kfn_adam_step')
-        self.adam_t = t
+        _lib.check(self.lib.kfn_adam_step_guarded(self.params.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                                  self.grads.data_ptr(), self.num_floats, lr, BETA1, BETA2, EPSILON,
+                                                  self.weight_decay, self.growth_interval, self.scale_state.data_ptr(),
+                                                  stream), 'kfn_adam_step_guarded')
         self.global_step += 1
         self._packs_stale = True
         return lr
@@ -561,19 +456,7 @@ class SCoordNetTrainer(object):
 def restore(model_folder, verbose=True, scope=SCOPE):
     """The newest snapshot of a model folder for resuming: (weights of `scope` or None, state or None, step).  The snapshot may
     be a TF checkpoint or a kfnet_weights*.npz, with or without a kfnet_train_state-<step>.npz beside it."""
-    from .tools.io import get_snapshot
-    from .weights import load_snapshot
-    snapshot, step = get_snapshot(model_folder) if model_folder and os.path.isdir(model_folder) else (None, 0)
-    if snapshot is None:
-        return None, None, 0
-    W = load_snapshot(snapshot, scopes=(scope,), verbose=verbose)
-    W = {k: v for k, v in W.items() if k.startswith(scope + '/')}
-    sp = snapshot_paths(model_folder, step)[1]
-    state = None
-    if os.path.exists(sp):
-        with np.load(sp) as z:
-            state = {k: z[k] for k in z.files}
-    if verbose:
-        print('Adam slots restored from %s' % sp if state is not None else
-              'no %s: the Adam slots start at zero' % os.path.basename(sp))
+    W, state, step = read_snapshot(model_folder, (scope,), verbose)
+    if W is not None:
+        W = {k: v for k, v in W.items() if k.startswith(scope + '/')}
     return W, state, step

@@ -25,13 +25,12 @@ the rows of the b frames and adds d_fa at the rows of the a frames.
 There is no fallback: a missing entry point or an unsupported shape raises.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _lib, staging
 from .cnn_wrapper.OFlowNet import DECODER, ENCODER, FC, LOGITS
-from .train import BETA1, BETA2, EPSILON, adam_lr_t, learning_rate, snapshot_paths
+from .train_common import LazyStats, ParamStore, size_query
 from .weights import variable_specs
 
 SCOPE = 'Temporal'
@@ -84,25 +83,15 @@ class Layer(object):
         self.name, self.kind, self.k, self.ci, self.co, self.stride, self.relu, self.epilogue = name, kind, k, ci, co, stride, relu, epilogue
 
 
-class StepStats(object):
-    """What a step reports, read from the device on first access: loss, accuracy, pixels (sum M), lost (cells whose warp left the
-    grid or met a masked corner), lr."""
+class StepStats(LazyStats):
+    """loss, accuracy, pixels (sum M), lost (cells whose warp left the grid or met a masked corner), lr."""
     KEYS = ('loss', 'accuracy', 'pixels', 'lost', 'lr')
 
-    def __init__(self, stats_dev, lr):
-        self._dev, self._lr, self._host = stats_dev, lr, None
-
-    def keys(self):
-        return list(self.KEYS)
-
-    def __getitem__(self, k):
-        if self._host is None:
-            s = self._dev.cpu().numpy()
-            self._host = dict(loss=float(s[0]), accuracy=float(s[1]), pixels=float(s[2]) - 1.0, lost=float(s[3]), lr=self._lr)
-        return self._host[k]
+    def _decode(self, s):
+        return dict(loss=float(s[0]), accuracy=float(s[1]), pixels=float(s[2]) - 1.0, lost=float(s[3]), lr=self._lr)
 
 
-class OFlowNetTrainer(object):
+class OFlowNetTrainer(ParamStore):
     def __init__(self, weights, image_size=(480, 640), pairs=4, base_lr=1e-4, gamma=0.5, stepvalue=100000, weight_decay=1e-4,
                  loss_clip=None, device='cuda:0', frames=None, pair_index=None):
         """weights: {TF name: array} holding at least Temporal/*.  pairs = P: a batch is 2P frames, pair p = frames (2p, 2p + 1).
@@ -114,12 +103,9 @@ class OFlowNetTrainer(object):
         staging.check_size(H, Wd, 'the height and width of a training batch')
         if pairs < 1:
             raise ValueError('pairs must be >= 1')
-        self.lib, self.torch, self.device = _lib.load(), torch, torch.device(device)
+        self.lib = _lib.load()
         self.image_size, self.pairs, self.grid = (H, Wd), int(pairs), (H // 8, Wd // 8)
-        self.base_lr, self.gamma, self.stepvalue = float(base_lr), float(gamma), float(stepvalue)
-        self.weight_decay = float(weight_decay)
         self.loss_clip = None if loss_clip is None else float(loss_clip)
-        self.global_step = self.adam_t = 0
         P, (h, w) = self.pairs, self.grid
         if (frames is None) != (pair_index is None):
             raise ValueError('frames and pair_index go together')
@@ -128,20 +114,14 @@ class OFlowNetTrainer(object):
         self.windows = N = P * h * w
 
         specs = {n.split('/', 1)[1]: (kind, shape) for n, kind, shape in variable_specs() if n.startswith(SCOPE + '/')}
-        self.slots, off = {}, 0
-        for name, (kind, shape) in specs.items():
-            nb = shape[2] if kind == 'deconv' else shape[-1]
-            for var, shp in (('kernel', shape), ('bias', (nb,))):
-                n = int(np.prod(shp))
-                self.slots['%s/%s/%s' % (SCOPE, name, var)] = (off, n, tuple(shp))
-                off += -(-n // 4) * 4
-        self.num_floats = off
+        # the flat parameter store: kernel then bias per variable of the scope; a transposed layer's bias has its Cout = shape[2]
+        ParamStore.__init__(self, [('%s/%s/%s' % (SCOPE, name, var), shp) for name, (kind, shape) in specs.items()
+                                   for var, shp in (('kernel', shape), ('bias', (shape[2] if kind == 'deconv' else shape[-1],)))],
+                            device, base_lr, gamma, stepvalue, weight_decay)
 
         with torch.cuda.device(self.device):
             f32 = dict(dtype=torch.float32, device=self.device)
-            self.params, self.grads = torch.zeros(off, **f32), torch.zeros(off, **f32)
-            self.m, self.v = torch.zeros(off, **f32), torch.zeros(off, **f32)
-            self._fill(self.params, weights)
+            self.set_weights(weights)
             self.frames = torch.zeros((F, H, Wd, 3), dtype=torch.uint8, device=self.device)
             if self.pair_index is not None:
                 self.a_idx, self.b_idx = (torch.from_numpy(x).to(self.device) for x in self.pair_index)
@@ -234,28 +214,21 @@ class OFlowNetTrainer(object):
             self.d_flow, self.d_sigma = buf(N, 2), buf(N, 1)
             self.stats = torch.zeros(16, **f32)
 
-            ws_bytes = self._size(self.lib.kfn_first_conv_u8_grad_weights_workspace_bytes, F, H, Wd, self.tower[0].co)
+            ws_bytes = size_query(self.lib.kfn_first_conv_u8_grad_weights_workspace_bytes, F, H, Wd, self.tower[0].co)
             for L in self.layers[1:]:
                 k, ci, co = L.k, L.ci, L.co
                 if L.kind == 'deconv':                              # the stride-2 convolution V: Cout -> Cin
                     ci, co = L.co, L.ci
                 L.vci, L.vco = ci, co
-                L.fwd = torch.zeros(self._size(self.lib.kfn_pack_conv_weights_floats, k, k, ci, co, _lib.PACK_FORWARD), **f32)
+                L.fwd = torch.zeros(size_query(self.lib.kfn_pack_conv_weights_floats, k, k, ci, co, _lib.PACK_FORWARD), **f32)
                 L.back_kind = _lib.PACK_INPUT_GRAD_S2 if L.stride == 2 else _lib.PACK_INPUT_GRAD_S1
-                L.back = torch.zeros(self._size(self.lib.kfn_pack_conv_weights_floats, k, k, ci, co, L.back_kind), **f32)
+                L.back = torch.zeros(size_query(self.lib.kfn_pack_conv_weights_floats, k, k, ci, co, L.back_kind), **f32)
                 for d in self._wgrad_descs(L):
-                    ws_bytes = max(ws_bytes, self._size(self.lib.kfn_conv2d_grad_weights_workspace_bytes, C.byref(d)))
+                    ws_bytes = max(ws_bytes, size_query(self.lib.kfn_conv2d_grad_weights_workspace_bytes, C.byref(d)))
             self.workspace = torch.zeros(-(-ws_bytes // 4), **f32)
             self.scratch_dw = torch.zeros(128 * 128 + 128, **f32)      # the unused halves of the bias-only launches
-            self._packs_stale = True
 
-    # ---- sizes and descriptors -----------------------------------------------------------------------------------------------
-    @staticmethod
-    def _size(fn, *args):
-        n = C.c_size_t()
-        _lib.check(fn(*(args + (C.byref(n),))), 'size query')
-        return n.value
-
+    # ---- descriptors -----------------------------------------------------------------------------------------------------------
     def _ptr(self, flat, L, var):
         return flat.data_ptr() + 4 * self.slots['%s/%s/%s' % (SCOPE, L.name, var)][0]
 
@@ -271,53 +244,6 @@ class OFlowNetTrainer(object):
             return [v, b]
         return [_lib.ConvDesc(N=L.x.n, H=L.x.h, W=L.x.w, Cin=L.ci, ldx=L.x.ld, Cout=L.co, cout_pad=cp(L.co), ldy=L.dy.ld, kh=L.k,
                               kw=L.k, stride=L.stride)]
-
-    # ---- weights and optimiser state: SCoordNetTrainer's conventions -------------------------------------------------------------
-    def _fill(self, flat, arrays, prefix=''):
-        for name, (off, n, shape) in self.slots.items():
-            if prefix + name not in arrays:
-                raise KeyError('weights lack %s%s' % (prefix, name))
-            a = np.ascontiguousarray(np.asarray(arrays[prefix + name], dtype=np.float32))
-            if a.shape != tuple(shape):
-                raise ValueError('%s%s has shape %s, expected %s' % (prefix, name, a.shape, tuple(shape)))
-            flat[off:off + n].copy_(self.torch.from_numpy(a.reshape(-1)))
-
-    def set_weights(self, weights):
-        self._fill(self.params, weights)
-        self._packs_stale = True
-
-    def _named(self, flat, prefix=''):
-        host = flat.cpu().numpy()
-        return {prefix + name: host[off:off + n].reshape(shape).copy() for name, (off, n, shape) in self.slots.items()}
-
-    def weights(self):
-        """{TF variable name: float32 array} of Temporal/*: what OFlowNet.eval and KFNet.train --oflownet load."""
-        return self._named(self.params)
-
-    def gradients(self):
-        """The last backward pass's gradients of the loss (without the regulariser), in TF layout under the variables' names."""
-        return self._named(self.grads)
-
-    def state(self):
-        st = dict(global_step=np.int64(self.global_step), adam_t=np.int64(self.adam_t))
-        st.update(self._named(self.m, 'adam_m/'))
-        st.update(self._named(self.v, 'adam_v/'))
-        return st
-
-    def load_state(self, st):
-        self._fill(self.m, st, 'adam_m/')
-        self._fill(self.v, st, 'adam_v/')
-        self.global_step, self.adam_t = int(st['global_step']), int(st['adam_t'])
-
-    def save(self, folder, step=None):
-        """Writes kfnet_weights-<step>.npz (Temporal/* only) and kfnet_train_state-<step>.npz; returns the two paths."""
-        from .weights import save_npz
-        step = self.global_step if step is None else step
-        os.makedirs(folder, exist_ok=True)
-        wp, sp = snapshot_paths(folder, step)
-        save_npz(wp, self.weights())
-        np.savez(sp, **self.state())
-        return wp, sp
 
     # ---- one step ----------------------------------------------------------------------------------------------------------------
     def _repack(self, stream):
@@ -342,14 +268,7 @@ class OFlowNetTrainer(object):
             staging.stage(self.frames, frames_u8, torch.uint8, (B, H, Wd, 3), 'frames')
         if labels is None and self.pair_index is not None:
             return None
-        lb = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels, dtype=np.float32))
-        if tuple(lb.shape) not in ((B, H, Wd, 4), (B, h, w, 4)):
-            raise ValueError('labels must be float32 [%d,%d,%d,4] or grid-sized [%d,%d,%d,4], got %s'
-                             % (B, H, Wd, B, h, w, tuple(lb.shape)))
-        if self.labels is None or self.labels.shape != lb.shape:
-            self.labels = torch.zeros(tuple(lb.shape), dtype=torch.float32, device=self.device)
-        self.labels.copy_(lb.to(torch.float32), non_blocking=True)
-        self.label_stride = 8 if tuple(lb.shape) == (B, H, Wd, 4) else 1
+        self.labels, self.label_stride = staging.stage_labels(self.labels, labels, B, (H, Wd), (h, w), self.device)
         return self.label_stride
 
     def _conv(self, L, x, y, pack, stream, transposed=0, relu=0, bias=None, epilogue=_lib.EPI_NONE, cin=None, cout=None, stride=1):
@@ -484,19 +403,6 @@ class OFlowNetTrainer(object):
         _lib.check(self.lib.kfn_first_conv_u8_grad_weights(self.frames.data_ptr(), F, H, Wd, first.dy.ptr, first.co,
                                                            self._ptr(self.grads, first, 'kernel'), self._ptr(self.grads, first, 'bias'),
                                                            self.workspace.data_ptr(), stream), 'kfn_first_conv_u8_grad_weights')
-
-    def apply_gradients(self, stream=None):
-        """TensorFlow's Adam on the flat buffer, with the regulariser's weight_decay * w folded into the gradient (6b)."""
-        stream = staging.current_stream(self.device) if stream is None else stream
-        lr = learning_rate(self.base_lr, self.gamma, self.stepvalue, self.global_step)
-        t = self.adam_t + 1
-        _lib.check(self.lib.kfn_adam_step(self.params.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.grads.data_ptr(),
-                                          self.num_floats, adam_lr_t(lr, t), BETA1, BETA2, EPSILON, self.weight_decay, stream),
-                   'kfn_adam_step')
-        self.adam_t = t
-        self.global_step += 1
-        self._packs_stale = True
-        return lr
 
     def step(self, frames_u8, labels):
         """One update on 2P frames and their labels.  Returns StepStats of THIS step's loss, before the update."""

@@ -25,12 +25,12 @@ backward pass, and both scopes take an Adam step with one global_step, learning 
 There is no fallback: a missing entry point raises, and so does a flow outside the radius the reverse scan gathers over.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _lib, staging
-from .train import LAYERS, SCOPE, SCoordNetTrainer, snapshot_paths
+from .train import LAYERS, SCOPE, SCoordNetTrainer
+from .train_common import LazyStats, ParamStore, read_snapshot, size_query
 
 FLOW_SCOPE = 'Temporal'
 GROUP = 4                                 # frames per group, KFNet/train.py:60-66
@@ -89,31 +89,28 @@ def start_step(snapshot_step, stepvalue, reset_step, scoordnet, oflownet):
     return snapshot_step if reset_step < 0 else reset_step
 
 
-class StepStats(object):
-    """What a step reports, read from the device on first access (so that steps queue): loss, l_measure, l_temp, l_KF (each
-    NLL + 50 smoothness, as the reference logs them), a_measure, a_temp, a_KF, pixels, lr.  The read-back raises when a flow
-    left the radius of the reverse scan."""
+class StepStats(LazyStats):
+    """loss, l_measure, l_temp, l_KF (each NLL + 50 smoothness, as the reference logs them), a_measure, a_temp, a_KF, pixels,
+    lr.  The read-back raises when a flow left the radius of the reverse scan."""
     KEYS = ('loss', 'l_measure', 'l_temp', 'l_KF', 'a_measure', 'a_temp', 'a_KF', 'pixels', 'lr')
     REPROJ_KEYS = ('l_reproj_measure', 'l_reproj_temp', 'l_reproj_kf')   # reproj_weights only: the three R; `loss` includes them
 
     def __init__(self, stats_dev, lr, radius, reproj_dev=None):
-        self._dev, self._lr, self._radius, self._host, self._reproj_dev = stats_dev, lr, radius, None, reproj_dev
+        LazyStats.__init__(self, stats_dev, lr)
+        self._radius, self._reproj_dev = radius, reproj_dev
 
     def keys(self):
         return list(self.KEYS) + (list(self.REPROJ_KEYS) if self._reproj_dev is not None else [])
 
-    def __getitem__(self, k):
-        if self._host is None:
-            s = self._dev.cpu().numpy()
-            check_flow_count(s, self._radius)
-            self._host = dict(loss=float(s[0]), l_measure=float(s[12]), l_temp=float(s[13]), l_KF=float(s[14]),
-                              a_measure=float(s[7]), a_temp=float(s[8]), a_KF=float(s[9]), pixels=float(s[10]) - 1.0,
-                              lr=self._lr)
-            if self._reproj_dev is not None:
-                r = self._reproj_dev.cpu().numpy()       # kfn_reproj_loss_grad's stats: the three R, their weighted sum
-                self._host.update(l_reproj_measure=float(r[0]), l_reproj_temp=float(r[1]), l_reproj_kf=float(r[2]),
-                                  loss=float(s[0]) + float(r[3]))
-        return self._host[k]
+    def _decode(self, s):
+        check_flow_count(s, self._radius)
+        host = dict(loss=float(s[0]), l_measure=float(s[12]), l_temp=float(s[13]), l_KF=float(s[14]), a_measure=float(s[7]),
+                    a_temp=float(s[8]), a_KF=float(s[9]), pixels=float(s[10]) - 1.0, lr=self._lr)
+        if self._reproj_dev is not None:
+            r = self._reproj_dev.cpu().numpy()       # kfn_reproj_loss_grad's stats: the three R, their weighted sum
+            host.update(l_reproj_measure=float(r[0]), l_reproj_temp=float(r[1]), l_reproj_kf=float(r[2]),
+                        loss=float(s[0]) + float(r[3]))
+        return host
 
 
 def check_flow_count(stats_host, radius):
@@ -189,15 +186,12 @@ class KFNetTrainer(object):
             # frame 0 of every group is a reset frame (t0 = 0, reset_period = T): both estimates equal the measurement
             self.scan_desc = _lib.KalmanDesc(S=self.S, T=self.T, H=h, W=w, t0=0, reset_period=self.T,
                                              min_uncertainty=MIN_UNCERTAINTY, nis_gate=0.0, has_transform=0)
-            need = C.c_size_t(0)
-            _lib.check(self.lib.kfn_kalman_scan_scratch_bytes(C.byref(self.scan_desc), C.byref(need)),
-                       'kfn_kalman_scan_scratch_bytes')
-            self.scan_scratch = torch.zeros(-(-need.value // 4), **f32) if need.value else None
+            need = size_query(self.lib.kfn_kalman_scan_scratch_bytes, C.byref(self.scan_desc))
+            self.scan_scratch = torch.zeros(-(-need // 4), **f32) if need else None
             self.back_desc = _lib.FilterBackwardDesc(S=self.S, T=self.T, H=h, W=w, ld_dpred=sc.dact[-1].shape[3],
                                                      radius=self.radius, min_uncertainty=MIN_UNCERTAINTY)
-            _lib.check(self.lib.kfn_filter_backward_scratch_bytes(C.byref(self.back_desc), C.byref(need)),
-                       'kfn_filter_backward_scratch_bytes')
-            self.back_scratch = torch.zeros(-(-need.value // 4), **f32)
+            need = size_query(self.lib.kfn_filter_backward_scratch_bytes, C.byref(self.back_desc))
+            self.back_scratch = torch.zeros(-(-need // 4), **f32)
 
     # ---- what the stage-1 trainer keeps ------------------------------------------------------------------------------
     global_step = property(lambda self: self.sc.global_step, lambda self, v: setattr(self.sc, 'global_step', v))
@@ -232,24 +226,14 @@ class KFNetTrainer(object):
         for scope, held in split_state(st).items():
             tr = self.sc if scope == SCOPE else self.ft
             if held:
-                tr._fill(tr.m, st, 'adam_m/')
-                tr._fill(tr.v, st, 'adam_v/')
+                tr.load_slots(st)
             else:
-                tr.m.zero_()
-                tr.v.zero_()
+                tr.zero_slots()
                 if verbose:
                     print('the train state holds no Adam slots of %s/*: they start at zero' % scope)
         self.sc.global_step, self.sc.adam_t = int(st['global_step']), int(st['adam_t'])
 
-    def save(self, folder, step=None):
-        """Writes kfnet_weights-<step>.npz (both scopes) and kfnet_train_state-<step>.npz; returns the two paths."""
-        from .weights import save_npz
-        step = self.global_step if step is None else step
-        os.makedirs(folder, exist_ok=True)
-        wp, sp = snapshot_paths(folder, step)
-        save_npz(wp, self.weights())
-        np.savez(sp, **self.state())
-        return wp, sp
+    save = ParamStore.save        # both scopes' weights() and state() in the two files
 
     # ---- one step ----------------------------------------------------------------------------------------------------
     def flow(self, main):
@@ -391,12 +375,10 @@ class KFNetTrainer(object):
     def flow_update(self, main):
         """Temporal/*'s Adam step and packs with SCoordNet's counters, where its backward pass ran; `main` then waits for the
         flow stream, so that the next step may overwrite the frames."""
-        ft = self.ft
-        ft.global_step, ft.adam_t = self.sc.global_step, self.sc.adam_t
         side = self.flow_stream if self.overlap else main
         with self.torch.cuda.stream(side):
-            ft.apply_gradients(side.cuda_stream)
-            ft._repack(side.cuda_stream)
+            self.ft.apply_gradients(side.cuda_stream, counters=(self.sc.global_step, self.sc.adam_t))
+            self.ft._repack(side.cuda_stream)
         if self.overlap:
             self.ev_flow_done.record(side)
             main.wait_event(self.ev_flow_done)
@@ -408,18 +390,8 @@ def restore(model_folder, scoordnet='', oflownet='', verbose=True):
     lacking a scope --, Adam state or None, step of model_folder's snapshot)."""
     from .tools.io import get_snapshot
     from .weights import load_snapshot
-    W, state, step = {}, None, 0
-    snapshot, s = get_snapshot(model_folder) if model_folder and os.path.isdir(model_folder) else (None, 0)
-    if snapshot is not None:
-        W.update(load_snapshot(snapshot, verbose=verbose))
-        step = s
-        sp = snapshot_paths(model_folder, step)[1]
-        if os.path.exists(sp):
-            with np.load(sp) as z:
-                state = {k: z[k] for k in z.files}
-        if verbose:
-            print('Adam slots restored from %s' % sp if state is not None else
-                  'no %s: the Adam slots start at zero' % os.path.basename(sp))
+    W, state, step = read_snapshot(model_folder, (SCOPE, FLOW_SCOPE), verbose)
+    W = W or {}
     for folder, scope in ((scoordnet, SCOPE), (oflownet, FLOW_SCOPE)):
         if not folder:
             continue

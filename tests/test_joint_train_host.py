@@ -15,6 +15,7 @@ import torch
 import joint_train_ref as JR
 import kf_train_ref as KR
 from kfnet_amd import _lib
+from kfnet_amd.train_common import ParamStore
 from kfnet_amd.train_flow import check_pair_index
 from kfnet_amd.train_kfnet import pair_table, split_state
 
@@ -253,18 +254,13 @@ def test_graph_api_keeps_refusing_to_train_oflownet():
 
 
 # -- state files ---------------------------------------------------------------------------------------------------------------------
-class _FlatTrainer(object):
-    """What load_state touches of a trainer: named slots of two flat buffers (train.py's and train_flow.py's convention)."""
+class _FlatTrainer(ParamStore):
+    """What load_state touches of a trainer: the parameter store both trainers are, on CPU tensors, its Adam slots holding 9."""
 
     def __init__(self, names):
-        self.torch = torch
-        self.slots = {n: (4 * i, 3, (3,)) for i, n in enumerate(names)}
-        self.m, self.v = torch.full((4 * len(names),), 9.0), torch.full((4 * len(names),), 9.0)
-        self.global_step = self.adam_t = 0
-
-    def _fill(self, buf, arrays, prefix=''):
-        for name, (off, n, shape) in self.slots.items():
-            buf[off:off + n].copy_(torch.from_numpy(np.asarray(arrays[prefix + name], np.float32)))
+        ParamStore.__init__(self, [(n, (3,)) for n in names])
+        self.m.fill_(9.0)
+        self.v.fill_(9.0)
 
 
 def _state(names, step):
