@@ -4,7 +4,8 @@ tests/test_conv_modes_host.py).
 kfn_conv2d_nhwc (csrc/kfn_conv.hip, conv_mfma_kernel) is steered by many descriptor fields at once; the op tests exercise
 each of them mostly alone.  Here every field is a FACTOR with a few LEVELS, RULES restate what the launcher accepts (its
 validate(), its dispatch and pick_config(); nothing else), and a seeded greedy generator draws cases until every pair of
-levels that the rules allow together occurs in at least one case.  Nothing below touches the GPU."""
+levels that the rules allow together occurs in at least one case.  The generator itself (class Table) knows nothing of this
+table: tests/wino_modes.py hands it another.  Nothing below touches the GPU."""
 import collections
 
 import numpy as np
@@ -74,81 +75,114 @@ RULES = (
 )
 
 
-def valid(partial):
-    """`partial`: dict factor -> level (any subset).  False as soon as a rule whose fields are all present fails."""
-    for fields, pred in RULES:
-        if all(f in partial for f in fields) and not pred(*[partial[f] for f in fields]):
-            return False
-    return True
+class Table:
+    """The generator, for any table of factors and rules (tests/wino_modes.py builds its own from it): FACTORS an ordered
+    dict factor -> levels, RULES a list of (fields, predicate) as above."""
+
+    def __init__(self, factors, rules, case_type=None, constrained_first=False):
+        self.factors = factors
+        self.constrained_first = constrained_first      # complete() sets the factors that most rules name first (less backtracking)
+        self.rules = tuple(rules)
+        self.names = tuple(factors)
+        self.Case = case_type or collections.namedtuple('Case', self.names)
+        # the rules that name a factor: when that factor is the last one set, only these can newly fail
+        self._naming = {n: tuple(r for r in self.rules if n in r[0]) for n in self.names}
+
+    def valid(self, partial):
+        """`partial`: dict factor -> level (any subset).  False as soon as a rule whose fields are all present fails."""
+        for fields, pred in self.rules:
+            if all(f in partial for f in fields) and not pred(*[partial[f] for f in fields]):
+                return False
+        return True
+
+    def _still_valid(self, cur, name):
+        """valid(cur) for a `cur` that was valid before `name` was set."""
+        for fields, pred in self._naming[name]:
+            try:
+                args = [cur[f] for f in fields]
+            except KeyError:
+                continue
+            if not pred(*args):
+                return False
+        return True
+
+    def complete(self, partial, rng=None, constrained_first=None):
+        """A valid full case extending `partial` (levels in random order when `rng` is given), or None if there is none."""
+        todo = [n for n in self.names if n not in partial]
+        if rng is not None:
+            todo = [todo[i] for i in rng.permutation(len(todo))]
+        if self.constrained_first if constrained_first is None else constrained_first:
+            todo.sort(key=lambda n: -len(self._naming[n]))      # stable: the drawn order among equals
+
+        def rec(k, cur):
+            if k == len(todo):
+                return dict(cur)
+            levels = self.factors[todo[k]]
+            order = rng.permutation(len(levels)) if rng is not None else range(len(levels))
+            for j in order:
+                cur[todo[k]] = levels[j]
+                if self._still_valid(cur, todo[k]):
+                    got = rec(k + 1, cur)
+                    if got is not None:
+                        return got
+                del cur[todo[k]]
+            return None
+
+        if not self.valid(partial):
+            return None
+        return rec(0, dict(partial))
+
+    def all_pairs(self):
+        """Every ((factor, level), (factor, level)) of two different factors, factors in table order."""
+        names = self.names
+        out = []
+        for a in range(len(names)):
+            for b in range(a + 1, len(names)):
+                for la in self.factors[names[a]]:
+                    for lb in self.factors[names[b]]:
+                        out.append(((names[a], la), (names[b], lb)))
+        return out
+
+    def allowed_pairs(self):
+        """The pairs that some valid case contains (exhaustive search per pair, pruned by the rules; whether a completion
+        exists does not depend on the order in which the search sets the factors)."""
+        return [p for p in self.all_pairs() if self.complete({p[0][0]: p[0][1], p[1][0]: p[1][1]}, None, True) is not None]
+
+    def pairs_of(self, case):
+        names = self.names
+        d = case._asdict() if hasattr(case, '_asdict') else case
+        return {((names[a], d[names[a]]), (names[b], d[names[b]]))
+                for a in range(len(names)) for b in range(a + 1, len(names))}
+
+    def generate(self, seed):
+        """Seeded greedy all-pairs table: while a pair is uncovered, draw random valid completions of it and keep the one
+        that covers the most pairs still uncovered."""
+        rng = np.random.default_rng(seed)
+        open_pairs = self.allowed_pairs()
+        uncovered = set(open_pairs)
+        cases = []
+        for p in open_pairs:
+            if p not in uncovered:
+                continue
+            best, gain = None, 0
+            for _ in range(CANDIDATES):
+                c = self.complete({p[0][0]: p[0][1], p[1][0]: p[1][1]}, rng)
+                g = len(self.pairs_of(c) & uncovered)
+                if g > gain:
+                    best, gain = c, g
+            cases.append(self.Case(**best))
+            uncovered -= self.pairs_of(best)
+        assert not uncovered
+        return cases
 
 
-def complete(partial, rng=None):
-    """A valid full case extending `partial` (levels in random order when `rng` is given), or None if there is none."""
-    todo = [n for n in NAMES if n not in partial]
-    if rng is not None:
-        todo = [todo[i] for i in rng.permutation(len(todo))]
-
-    def rec(k, cur):
-        if k == len(todo):
-            return dict(cur)
-        levels = FACTORS[todo[k]]
-        order = rng.permutation(len(levels)) if rng is not None else range(len(levels))
-        for j in order:
-            cur[todo[k]] = levels[j]
-            if valid(cur):
-                got = rec(k + 1, cur)
-                if got is not None:
-                    return got
-            del cur[todo[k]]
-        return None
-
-    if not valid(partial):
-        return None
-    return rec(0, dict(partial))
-
-
-def all_pairs():
-    """Every ((factor, level), (factor, level)) of two different factors, factors in table order."""
-    out = []
-    for a in range(len(NAMES)):
-        for b in range(a + 1, len(NAMES)):
-            for la in FACTORS[NAMES[a]]:
-                for lb in FACTORS[NAMES[b]]:
-                    out.append(((NAMES[a], la), (NAMES[b], lb)))
-    return out
-
-
-def allowed_pairs():
-    """The pairs that some valid case contains (exhaustive search per pair, pruned by the rules)."""
-    return [p for p in all_pairs() if complete({p[0][0]: p[0][1], p[1][0]: p[1][1]}) is not None]
-
-
-def pairs_of(case):
-    d = case._asdict() if isinstance(case, Case) else case
-    return {((NAMES[a], d[NAMES[a]]), (NAMES[b], d[NAMES[b]]))
-            for a in range(len(NAMES)) for b in range(a + 1, len(NAMES))}
+DIRECT = Table(FACTORS, RULES, Case)
+valid, complete, all_pairs, allowed_pairs, pairs_of = (DIRECT.valid, DIRECT.complete, DIRECT.all_pairs, DIRECT.allowed_pairs,
+                                                       DIRECT.pairs_of)
 
 
 def generate(seed=SEED):
-    """Seeded greedy all-pairs table: while a pair is uncovered, draw random valid completions of it and keep the one
-    that covers the most pairs still uncovered."""
-    rng = np.random.default_rng(seed)
-    open_pairs = allowed_pairs()
-    uncovered = set(open_pairs)
-    cases = []
-    for p in open_pairs:
-        if p not in uncovered:
-            continue
-        best, gain = None, 0
-        for _ in range(CANDIDATES):
-            c = complete({p[0][0]: p[0][1], p[1][0]: p[1][1]}, rng)
-            g = len(pairs_of(c) & uncovered)
-            if g > gain:
-                best, gain = c, g
-        cases.append(Case(**best))
-        uncovered -= pairs_of(best)
-    assert not uncovered
-    return cases
+    return DIRECT.generate(seed)
 
 
 # Outside the table: an explicit config that pick_config() forces to 128x32 beside a head epilogue -- (index, the config-4

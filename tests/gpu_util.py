@@ -74,18 +74,24 @@ def run_conv(x, w, b, stride=1, relu=False, transposed=False, epilogue=0, config
     return out
 
 
-def run_winograd(kind, x, wt, b, relu=False, form=0, ldx_pad=0, ldy_pad=8, config=0, x_layout='nhwc', y_layout='nhwc'):
+def run_winograd(kind, x, wt, b, relu=False, form=0, ldx_pad=0, ldy_pad=8, config=0, x_layout='nhwc', y_layout='nhwc',
+                 order=0, x_off=0, y_off=0, x_fill=9.0, f16=False, k_split=None, relaunch=None):
     """One launch of a minimal-filtering entry point on x [N,H,W,Cin] fp32 with the TF-layout 3x3 kernel wt:
       kind 'wino'  kfn_conv2d_winograd        (two kernels + workspace; F(2x2,3x3))
            'fused' kfn_conv2d_winograd_fused  (form 0 = the library's routing, 1 = KFN_WINO_FORM_ONE_WAVE)
            'f43'   kfn_conv2d_winograd_f43    (form 2 = four waves, 3 = eight waves)
            's2'    kfn_conv2d_winograd_s2     (stride 2; form 0 = four waves, 4 = eight waves, 5 = the F(4,2) form)
-    Input and output live in wider buffers (ldx = Cin + ldx_pad filled with 9.0 behind Cin, ldy = Cout + ldy_pad); guard
-    rows behind the output and the columns behind Cout must come back untouched.  x_layout / y_layout 'c16': that tensor is handed
+    Input and output live in wider buffers (ldx = Cin + ldx_pad filled with x_fill outside the window, which starts x_off floats
+    in; ldy = Cout + ldy_pad, the window y_off floats in); guard rows behind the output and the columns before and behind the
+    window must come back untouched.  x_layout / y_layout 'c16': that tensor is handed
     over / comes back channel-blocked (KFN_LAYOUT_C16, per image [C/16][H][W][16]; dense, so its pad is dropped); the conversion
-    from / to NHWC happens here on the host.  Returns y [N,Ho,Wo,Cout] np fp32."""
+    from / to NHWC happens here on the host.  order: kfn_conv_desc.wino_order.  f16: operand_dtype = KFN_OPERAND_F16 with the
+    packed kernel stored as halfs ('fused', and 's2' form 0).  k_split: through the split-K entry point of 'f43' (form 3) / 's2'
+    (form 4) with a workspace of its own, whose guard behind the planes must come back untouched.  relaunch: a sequence of
+    dicts of descriptor fields; each is one more launch on the same device buffers (y refilled with its sentinel) with those
+    fields changed, and the return value becomes the list of all results.  Returns y [N,Ho,Wo,Cout] np fp32."""
     import torch
-    from kfnet_amd.graph import (pack_winograd_f43_kernel, pack_winograd_f43_kernel_b, pack_winograd_fused_kernel,
+    from kfnet_amd.graph import (as_f16, pack_winograd_f43_kernel, pack_winograd_f43_kernel_b, pack_winograd_fused_kernel,
                                  pack_winograd_kernel, pack_winograd_s2_kernel, pack_winograd_s2_kernel_b, pack_winograd_s2_kernel_c)
     lib = _lib.load()
     n, h, w, ci = x.shape
@@ -93,48 +99,71 @@ def run_winograd(kind, x, wt, b, relu=False, form=0, ldx_pad=0, ldy_pad=8, confi
     stride = 2 if kind == 's2' else 1
     ho, wo = -(-h // stride), -(-w // stride)
     if x_layout == 'c16':
-        ldx_pad = 0
+        ldx_pad = x_off = 0
     if y_layout == 'c16':
-        ldy_pad = 0
+        ldy_pad = y_off = 0
+    assert 0 <= x_off <= ldx_pad and 0 <= y_off <= ldy_pad
     ldx, ldy = ci + ldx_pad, co + ldy_pad
-    d = _lib.ConvDesc(N=n, H=h, W=w, Cin=ci, ldx=ldx, Cout=co, cout_pad=-(-co // 32) * 32, ldy=ldy, kh=3, kw=3,
-                      stride=stride, relu=int(relu), wino_form=form, config=config,
-                      x_layout=_lib.LAYOUT_C16 if x_layout == 'c16' else 0, y_layout=_lib.LAYOUT_C16 if y_layout == 'c16' else 0)
+    fields = dict(N=n, H=h, W=w, Cin=ci, ldx=ldx, Cout=co, cout_pad=-(-co // 32) * 32, ldy=ldy, kh=3, kw=3,
+                  stride=stride, relu=int(relu), wino_form=form, config=config, wino_order=order, operand_dtype=int(f16),
+                  x_layout=_lib.LAYOUT_C16 if x_layout == 'c16' else 0, y_layout=_lib.LAYOUT_C16 if y_layout == 'c16' else 0)
     if x_layout == 'c16':
         xb = np.ascontiguousarray(x.reshape(n, h, w, ci // 16, 16).transpose(0, 3, 1, 2, 4)).reshape(n * h * w, ci)
     else:
-        xb = np.full((n * h * w, ldx), 9.0, dtype=np.float32)
-        xb[:, :ci] = x.reshape(-1, ci)
+        xb = np.full((n * h * w, ldx), x_fill, dtype=np.float32)
+        xb[:, x_off:x_off + ci] = x.reshape(-1, ci)
     GUARD = 64
-    y = torch.full((n * ho * wo + GUARD, ldy), -5.0, device='cuda')
     dx = dev(xb)
     db = dev(np.concatenate([b, np.zeros((-co) % 4, np.float32)]).astype(np.float32)) if b is not None else None
     bp = db.data_ptr() if db is not None else None
+    xp = dx.data_ptr() + 4 * x_off
+    ws = None
     if kind == 'wino':
+        assert not f16 and k_split is None
         nb = C.c_size_t()
-        _lib.check(lib.kfn_winograd_workspace_bytes(C.byref(d), C.byref(nb)), 'ws')
+        _lib.check(lib.kfn_winograd_workspace_bytes(C.byref(_lib.ConvDesc(**fields)), C.byref(nb)), 'ws')
         ws = torch.empty((nb.value // 4 + 64,), device='cuda')
         du = dev(pack_winograd_kernel(wt))
-        _lib.check(lib.kfn_conv2d_winograd(C.byref(d), dx.data_ptr(), du.data_ptr(), bp, y.data_ptr(), ws.data_ptr(), 3,
-                                           stream()), 'kfn_conv2d_winograd')
+        call = lambda d, yp: lib.kfn_conv2d_winograd(C.byref(d), xp, du.data_ptr(), bp, yp, ws.data_ptr(), 3, stream())
     elif kind == 'fused':
-        du = dev(pack_winograd_fused_kernel(wt))
-        _lib.check(lib.kfn_conv2d_winograd_fused(C.byref(d), dx.data_ptr(), du.data_ptr(), bp, y.data_ptr(), stream()),
-                   'kfn_conv2d_winograd_fused')
+        assert k_split is None
+        du = dev((as_f16(pack_winograd_fused_kernel) if f16 else pack_winograd_fused_kernel)(wt))
+        call = lambda d, yp: lib.kfn_conv2d_winograd_fused(C.byref(d), xp, du.data_ptr(), bp, yp, stream())
     elif kind == 'f43':
+        assert not f16
         du = dev((pack_winograd_f43_kernel_b if form == 3 else pack_winograd_f43_kernel)(wt))
-        _lib.check(lib.kfn_conv2d_winograd_f43(C.byref(d), dx.data_ptr(), du.data_ptr(), bp, y.data_ptr(), stream()),
-                   'kfn_conv2d_winograd_f43')
+        call = lambda d, yp: lib.kfn_conv2d_winograd_f43(C.byref(d), xp, du.data_ptr(), bp, yp, stream())
+        split_fns = (lib.kfn_winograd_f43_splitk_workspace_bytes, lib.kfn_conv2d_winograd_f43_splitk)
     elif kind == 's2':
-        du = dev({4: pack_winograd_s2_kernel_b, 5: pack_winograd_s2_kernel_c}.get(form, pack_winograd_s2_kernel)(wt))
-        _lib.check(lib.kfn_conv2d_winograd_s2(C.byref(d), dx.data_ptr(), du.data_ptr(), bp, y.data_ptr(), stream()),
-                   'kfn_conv2d_winograd_s2')
+        assert not f16 or form == 0
+        pack = {4: pack_winograd_s2_kernel_b, 5: pack_winograd_s2_kernel_c}.get(form, pack_winograd_s2_kernel)
+        du = dev((as_f16(pack) if f16 else pack)(wt))
+        call = lambda d, yp: lib.kfn_conv2d_winograd_s2(C.byref(d), xp, du.data_ptr(), bp, yp, stream())
+        split_fns = (lib.kfn_winograd_s2_splitk_workspace_bytes, lib.kfn_conv2d_winograd_s2_splitk)
     else:
         raise ValueError(kind)
-    sync()
-    got = y.cpu().numpy()
-    assert np.all(got[n * ho * wo:] == -5.0), '%s wrote past the last output pixel' % kind
-    assert np.all(got[:, co:] == -5.0), '%s wrote outside its channel window' % kind
-    if y_layout == 'c16':
-        return np.ascontiguousarray(got[:n * ho * wo].reshape(n, co // 16, ho, wo, 16).transpose(0, 2, 3, 1, 4)).reshape(n, ho, wo, co)
-    return got[:n * ho * wo, :co].reshape(n, ho, wo, co)
+    ws_used = 0
+    if k_split is not None:
+        nb = C.c_size_t()
+        _lib.check(split_fns[0](C.byref(_lib.ConvDesc(**fields)), k_split, C.byref(nb)), 'split-K workspace bytes')
+        assert nb.value == (k_split * n * ho * wo * co * 4 if k_split > 1 else 0)
+        ws_used = nb.value // 4
+        ws = torch.full((ws_used + GUARD,), -7.0, device='cuda')
+        call = lambda d, yp: split_fns[1](C.byref(d), xp, du.data_ptr(), bp, yp, ws.data_ptr(), k_split, stream())
+    window = np.zeros(ldy, dtype=bool)
+    window[y_off:y_off + co] = True
+    outs = []
+    for change in [{}] + list(relaunch or []):
+        y = torch.full((n * ho * wo + GUARD, ldy), -5.0, device='cuda')
+        _lib.check(call(_lib.ConvDesc(**dict(fields, **change)), y.data_ptr() + 4 * y_off), 'kfn_conv2d_winograd (%s)' % kind)
+        sync()
+        got = y.cpu().numpy()
+        assert np.all(got[n * ho * wo:] == -5.0), '%s wrote past the last output pixel' % kind
+        assert np.all(got[:, ~window] == -5.0), '%s wrote outside its channel window' % kind
+        if k_split is not None:
+            assert bool((ws[ws_used:] == -7.0).all()), '%s: the partial sums went past the workspace' % kind
+        if y_layout == 'c16':
+            outs.append(np.ascontiguousarray(got[:n * ho * wo].reshape(n, co // 16, ho, wo, 16).transpose(0, 2, 3, 1, 4)).reshape(n, ho, wo, co))
+        else:
+            outs.append(got[:n * ho * wo, y_off:y_off + co].reshape(n, ho, wo, co).copy())
+    return outs if relaunch is not None else outs[0]
