@@ -56,7 +56,8 @@ extern "C" {
  * and kfn_cost_volume_backward, kfn_flow_head_backward, kfn_l2norm_backward and kfn_flow_loss_grad (training OFlowNet),
  * and kfn_filter_backward_joint (joint stage 3: both networks trained through the filter), and kfn_pnp_ransac_unc and
  * kfn_pose_filter (uncertainty-aware poses: weighted refinement, pose covariance, pose filter), and kfn_reproj_loss_grad
- * and kfn_augment_pixel_map (the reprojection loss of KFNet/KFNet.py:405-428 for stages 1 and 3). */
+ * and kfn_augment_pixel_map (the reprojection loss of KFNet/KFNet.py:405-428 for stages 1 and 3), and kfn_pose_track,
+ * kfn_pose_track_state_bytes and kfn_pose_track_scratch_bytes (the pose tracker: motion models, backward pass, carried state). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -673,6 +674,57 @@ typedef struct kfn_pose_filter_desc {
 #define KFN_POSE_FILTER_DESC_INIT {(int32_t)sizeof(kfn_pose_filter_desc), 0, 0, 0.02f, 0.02f, 22.46f, 3}
 int kfn_pose_filter(const kfn_pose_filter_desc* desc, const float* poses, const float* cov, float* out_poses, float* out_cov,
                     int32_t* flags, float* nis, void* stream);
+
+/* The pose tracker: kfn_pose_filter's recursion under one of two motion models, an optional backward pass, and a state that
+ * is carried from call to call (added exports; kfn_pose_filter is unchanged).  One sequence per lane, fp64, serial over t.
+ * Shapes and flags are kfn_pose_filter's; out_cov and smooth_cov [S,T,36] are the 6x6 pose block.
+ *   model = KFN_POSE_MODEL_WALK      kfn_pose_filter word for word: with smooth = 0 and state = NULL the four outputs are its
+ *                                    bits.  Error state (dtheta, drho), P 6x6.
+ *   model = KFN_POSE_MODEL_VELOCITY  the state also holds a body-frame twist xi = (omega, v) per frame; error state (dtheta,
+ *                                    drho, domega, dv), P 12x12.  Predict: p <- p + R v, then R <- R exp(omega), xi kept;
+ *                                    P <- F P F^T + Q with F = [[I6, I6], [0, I6]] and, per axis, Q = [[q/3, q/2], [q/2, q]]
+ *                                    on (pose axis, rate axis), q = rot_sigma^2 or trans_sigma^2.  Measurement H = [I6 0]:
+ *                                    y, the gate, the reject count and the flags as kfn_pose_filter, S = P[:6,:6] + Sigma_z;
+ *                                    K = P[:, :6] S^-1 (12x6), delta = K y, the pose takes delta[:6] as there,
+ *                                    xi <- xi + delta[6:], P in Joseph form.  (Re-)initialisation: pose and pose block from
+ *                                    the measurement, xi = 0, rate block diag(rot_rate_sigma^2 I3, trans_rate_sigma^2 I3),
+ *                                    cross blocks 0.  A missing or rejected frame outputs the prediction, which has moved.
+ *   smooth = 1   Rauch-Tung-Striebel smoothing over the T frames of this call into smooth_poses / smooth_cov.  The last frame's
+ *                smoothed estimate is its filtered one; frame t is smoothed from t+1 if both hold an estimate, t+1 is not a
+ *                (re-)initialisation (KFN_POSE_INIT) and its predicted P_p is positive definite:
+ *                e = (log_SO3(R_p^T R_s), R_p^T (p_s - p_p), xi_s - xi_p) of t+1, C = P_f F^T P_p^-1, d = C e,
+ *                p_s = p_f + R_f d_rho, R_s = R_f exp(d_theta), xi_s = xi_f + d_xi, P_s = P_f + C (P_s,t+1 - P_p,t+1) C^T;
+ *                otherwise the filtered estimate.  Frames without an estimate give NaN.  smooth_poses, smooth_cov and scratch
+ *                (kfn_pose_track_scratch_bytes; 0 bytes when smooth = 0) are all non-NULL with smooth = 1, and the two
+ *                outputs are NULL with smooth = 0.
+ *   state        kfn_pose_track_state_bytes of device memory, or NULL for a fresh state that is thrown away.  Per sequence, in
+ *                fp64: have, rejects, R, p, xi (velocity model), P.  All zero means "no estimate yet".  Read at the start and
+ *                written at the end of the call: T frames run in consecutive calls of any lengths give the forward outputs of
+ *                one call bit for bit.  The layout depends on model and S; the backward pass covers the frames of its own
+ *                call only.
+ * Approximations: F takes the adjoint of exp(-xi) and the right Jacobian as the identity, and the smoother applies a
+ * correction expressed in frame t+1's predicted body frame in frame t's (both first order in one frame's motion); S as
+ * kfn_pose_filter.  Bit-identical from launch to launch. */
+#define KFN_POSE_MODEL_WALK 0
+#define KFN_POSE_MODEL_VELOCITY 1
+typedef struct kfn_pose_track_desc {
+  int32_t struct_size;     /* = sizeof(kfn_pose_track_desc) as the caller compiled it */
+  int32_t S, T;            /* sequences, frames per sequence in this call */
+  int32_t model;           /* KFN_POSE_MODEL_* */
+  int32_t smooth;          /* 1: also the backward pass over the T frames of this call */
+  float rot_sigma;         /* walk: rad per frame (0.02), as kfn_pose_filter; velocity: white acceleration per frame (0.005); >= 0 */
+  float trans_sigma;       /* walk: metres per frame (0.02); velocity: white acceleration per frame (0.005); >= 0 */
+  float rot_rate_sigma;    /* velocity: sigma of the unknown angular rate at (re-)initialisation, rad per frame (0.05); > 0 */
+  float trans_rate_sigma;  /* velocity: sigma of the unknown velocity at (re-)initialisation, metres per frame (0.05); > 0 */
+  float gate;              /* as kfn_pose_filter */
+  int32_t max_rejects;     /* as kfn_pose_filter */
+} kfn_pose_track_desc;
+#define KFN_POSE_TRACK_DESC_INIT {(int32_t)sizeof(kfn_pose_track_desc), 0, 0, KFN_POSE_MODEL_WALK, 0, 0.02f, 0.02f, 0.05f, 0.05f, 22.46f, 3}
+int kfn_pose_track_state_bytes(const kfn_pose_track_desc* desc, size_t* bytes);
+int kfn_pose_track_scratch_bytes(const kfn_pose_track_desc* desc, size_t* bytes);
+int kfn_pose_track(const kfn_pose_track_desc* desc, const float* poses, const float* cov, void* state, float* out_poses,
+                   float* out_cov, int32_t* flags, float* nis, float* smooth_poses, float* smooth_cov, void* scratch,
+                   void* stream);
 
 /* ---- multi-GPU: rank -> rank hand-off of the recurrent state (RCCL point-to-point) ----
  * No reference counterpart (the reference is single-device: KFNet/train.py:375 is its only

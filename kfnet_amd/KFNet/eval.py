@@ -24,6 +24,9 @@ When label_list.txt is present the reference's per-frame log line (losses, accur
 distance errors in cm, NIS-in-band fraction) and the final summary are printed
 (kfnet_amd/KFNet/metrics.py).  Not reproduced: --show plotting.
 `--pose_weighted` is `--pose` with the refinement weighted by the records' uncertainty; it also writes `pose_cov_<i>.txt`.
+`--pose_smooth` (single-process runs) is `--pose_weighted`, and at the end the poses are cut into sequences of
+`--pose_sequence_length` frames (default: the reset period, 500), tracked under `--pose_motion` (walk) and smoothed backwards
+(kfnet_amd/KFNet/pose_filter.py PoseTracker); it writes `pose_smooth_<i>.txt`.
 `--pose` also solves every frame's camera pose on the device (kfnet_amd/KFNet/pnp.py) and writes `pose_<i>.txt` next to
 each `coord_<i>.npy`.
 """
@@ -132,8 +135,10 @@ def main(argv=None):
     ap.add_argument('--block', type=int, default=32, help='--sharding cyclic: frames per block')
     modes.add_pose_flags(ap)
     a = ap.parse_args(argv)
-    pose = modes.pose_argument(a)
+    pose = modes.pose_argument(a, ap)
     rank, world, local = modes.sharded_env()
+    if world > 1 and a.pose_smooth:
+        return modes.refuse_sharded_smooth(world)
     if a.scene not in SCENES:
         print('Invalid scene:', a.scene)   # KFNet/train.py:142-144
         return 1
@@ -189,7 +194,8 @@ def main(argv=None):
     out = eval(image_paths, transform, W, a.output_folder, a.NIS, frames=frames_of(0, T) if image_paths is None else None,
                device='cuda:%d' % a.gpu, **kw)
     if a.pose:
-        modes.write_poses(out[0] if label_paths is not None else out, a.output_folder, pose=pose)
+        smooth = dict(motion=a.pose_motion, sequence_length=a.pose_sequence_length or RESET_PERIOD) if a.pose_smooth else None
+        modes.write_poses(out[0] if label_paths is not None else out, a.output_folder, pose=pose, smooth=smooth)
     return 0
 
 

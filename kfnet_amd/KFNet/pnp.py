@@ -7,7 +7,8 @@ a git-lfs pointer; this module is that last stage, with the reference's command-
                                   [--focal_x F --focal_y F --u U --v V] [--hypotheses 256] [--batch 64]
                                   [--weighted] [--pixel_sigma 1.0] [--covariance]
                                   [--smooth [--rot_sigma 0.02 --trans_sigma 0.02 --gate 22.46 --max_rejects 3
-                                             --sequence_length N]]
+                                             --sequence_length N
+                                             --motion {walk,velocity} --rts --rot_rate_sigma 0.05 --trans_rate_sigma 0.05]]
 
 writes one `pose_<i>.txt` (4x4 camera-to-world, the 7-Scenes `frame-*.pose.txt` format; NaN where no pose was found)
 per listed map, i = the map's position in the list.  With --gt (one pose file per map) it prints every frame's rotation
@@ -17,8 +18,11 @@ observes pixel (8c, 8r)), the candidate rule and the sampling are fixed in DESIG
 --weighted weighs the refinement by the maps' own uncertainty (channel 3 = 1/sigma) propagated to the image plane;
 --covariance writes `pose_cov_<i>.txt` (6 rows of 6: the covariance of the pose's body-frame perturbation, rotation
 first) next to each pose; --smooth runs the listed frames, cut into sequences of --sequence_length (default: one
-sequence), through the pose filter and writes `pose_smooth_<i>.txt`.  Without these flags the program does and prints
-what it always did.
+sequence), through the pose filter and writes `pose_smooth_<i>.txt`.  --motion, --rts and the two rate sigmas run the
+pose tracker instead (kfn_pose_track, DESIGN.md 5c "Pose tracker"): --motion velocity also estimates a body-frame twist
+per frame, --rts smooths each sequence backwards as well, and `pose_smooth_<i>.txt` then holds the smoothed pose; with
+--covariance the tracker also writes `pose_smooth_cov_<i>.txt`.  Without these flags the program does and prints what it
+always did.
 """
 import argparse
 import ctypes as C
@@ -206,15 +210,20 @@ def read_covariance(path):
 
 def smooth_in_sequences(filt, poses, cov, sequence_length=0):
     """poses [T,4,4], cov [T,6,6] cut into sequences of `sequence_length` frames (0: one sequence; the last may be
-    shorter), each filtered from a fresh state -> (poses, cov, flags [T], nis [T])."""
+    shorter), each filtered from a fresh state -> (poses, cov, flags [T], nis [T]); a PoseTracker with `smooth` adds
+    (smoothed poses, smoothed cov), and its carried state is reset in front of each run."""
+    def run(p, c):
+        if hasattr(filt, 'reset'):
+            filt.reset()
+        return filt.run(p, c)
     T = poses.shape[0]
     N = T if sequence_length <= 0 else min(sequence_length, T)
     full = (T // N) * N
-    out = [filt.run(poses[:full].reshape(-1, N, 4, 4), cov[:full].reshape(-1, N, 6, 6))]
+    out = [run(poses[:full].reshape(-1, N, 4, 4), cov[:full].reshape(-1, N, 6, 6))]
     out = [[x.reshape((full,) + x.shape[2:]) for x in out[0]]]
     if full < T:
-        out.append(filt.run(poses[full:], cov[full:]))
-    return tuple(np.concatenate([o[k] for o in out]) for k in range(4))
+        out.append(run(poses[full:], cov[full:]))
+    return tuple(np.concatenate([o[k] for o in out]) for k in range(len(out[0])))
 
 
 def summarize(rot, trans):
@@ -252,25 +261,40 @@ def main(argv=None):
     ap.add_argument('--gate', type=float, default=None, help='--smooth: gate on the NIS (22.46: 99.9 %% of chi^2_6)')
     ap.add_argument('--max_rejects', type=int, default=None, help='--smooth: consecutive rejections that reset (3)')
     ap.add_argument('--sequence_length', type=int, default=None, help='--smooth: frames per sequence (all of them)')
+    ap.add_argument('--motion', choices=['walk', 'velocity'], default=None,
+                    help='--smooth: the motion model of the pose tracker (walk: the filter above; velocity: a body-frame '
+                         'twist is estimated too, and --rot_sigma / --trans_sigma are its white acceleration, 0.005)')
+    ap.add_argument('--rts', action='store_true',
+                    help='--smooth: also smooth backwards over each sequence; pose_smooth_<i>.txt holds the smoothed pose')
+    ap.add_argument('--rot_rate_sigma', type=float, default=None,
+                    help='--smooth --motion velocity: sigma of the unknown angular rate at a (re-)start, rad per frame (0.05)')
+    ap.add_argument('--trans_rate_sigma', type=float, default=None,
+                    help='--smooth --motion velocity: sigma of the unknown velocity at a (re-)start, m per frame (0.05)')
     a = ap.parse_args(argv)
     uncertain = a.weighted or a.covariance or a.smooth
     if a.pixel_sigma is not None and not uncertain:
         ap.error('--pixel_sigma needs --weighted, --covariance or --smooth')
     if a.pixel_sigma is not None and not a.pixel_sigma > 0.0:
         ap.error('--pixel_sigma must be > 0')
-    for name in ('rot_sigma', 'trans_sigma', 'gate', 'max_rejects', 'sequence_length'):
+    for name in ('rot_sigma', 'trans_sigma', 'gate', 'max_rejects', 'sequence_length', 'motion', 'rot_rate_sigma',
+                 'trans_rate_sigma'):
         if getattr(a, name) is not None and not a.smooth:
             ap.error('--%s needs --smooth' % name)
+    if a.rts and not a.smooth:
+        ap.error('--rts needs --smooth')
+    # the pose tracker (kfn_pose_track) runs only when one of its flags asks for it: --smooth alone stays the filter
+    tracked = a.rts or any(getattr(a, k) is not None for k in ('motion', 'rot_rate_sigma', 'trans_rate_sigma'))
     filt = None
     if a.smooth:
-        from .pose_filter import PoseFilter
+        from .pose_filter import PoseFilter, PoseTracker
         if a.sequence_length is not None and a.sequence_length < 1:
             ap.error('--sequence_length must be >= 1')
+        kw = {k: getattr(a, k) for k in ('rot_sigma', 'trans_sigma', 'gate', 'max_rejects', 'rot_rate_sigma',
+                                         'trans_rate_sigma') if getattr(a, k) is not None}
         try:
-            filt = PoseFilter(**{k: getattr(a, k) for k in ('rot_sigma', 'trans_sigma', 'gate', 'max_rejects')
-                                 if getattr(a, k) is not None})
+            filt = PoseTracker(a.motion or 'walk', smooth=a.rts, **kw) if tracked else PoseFilter(**kw)
         except ValueError as e:
-            ap.error('--rot_sigma / --trans_sigma / --gate / --max_rejects: %s' % e)
+            ap.error('--rot_sigma / --trans_sigma / --rot_rate_sigma / --trans_rate_sigma / --gate / --max_rejects: %s' % e)
     paths = read_lines(a.coord_file_list)
     paths = [p for p in paths if p]
     if not paths:
@@ -303,9 +327,13 @@ def main(argv=None):
         if a.covariance:
             write_covariance(os.path.join(a.output_folder, 'pose_cov_%d.txt' % i), cov[i])
     if filt is not None:
-        smooth, _, flags, _ = smooth_in_sequences(filt, poses, cov, a.sequence_length or 0)
+        out = smooth_in_sequences(filt, poses, cov, a.sequence_length or 0)
+        flags = out[2]
+        smooth, smooth_cov = (out[4], out[5]) if a.rts else (out[0], out[1])
         for i in range(len(paths)):
             write_pose(os.path.join(a.output_folder, 'pose_smooth_%d.txt' % i), smooth[i])
+            if tracked and a.covariance:
+                write_covariance(os.path.join(a.output_folder, 'pose_smooth_cov_%d.txt' % i), smooth_cov[i])
     failed = int((info[:, 0] != _lib.PNP_OK).sum())
     print('%d poses written to %s (%d frames without a pose)' % (len(paths), a.output_folder, failed))
     if gt_paths is not None:

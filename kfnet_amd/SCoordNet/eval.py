@@ -8,7 +8,9 @@ the record KFNet writes on a reset frame (kfn_coord_records).  Only SCoordNet ru
 model folder's newest snapshot (a TF checkpoint model.ckpt-<step> or a kfnet_weights*.npz) may hold just the ScoreNet/*
 scope.  `--synthetic T` / `--random_weights` replace the images / the checkpoint; `--pose` also writes pose_<i>.txt
 (modes.write_poses); `--pose_weighted` is --pose with the refinement weighted by the records' uncertainty, and also writes
-pose_cov_<i>.txt.
+pose_cov_<i>.txt; `--pose_smooth` (single-process runs) is --pose_weighted, and at the end the poses are tracked under
+`--pose_motion` (walk) and smoothed backwards in sequences of `--pose_sequence_length` frames (default: the whole run), into
+pose_smooth_<i>.txt (modes.write_smoothed_poses).
 With label_list.txt every frame's median distance error d_m (cm) is printed, then the median / mean / stddev over d_m.
 
 Under `python -m torch.distributed.run --nproc-per-node N -m kfnet_amd.SCoordNet.eval ...` every rank processes a
@@ -72,9 +74,12 @@ def build_parser():
 
 
 def main(argv=None):
-    a = build_parser().parse_args(argv)
-    pose = modes.pose_argument(a)
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    pose = modes.pose_argument(a, ap)
     rank, world, local = modes.sharded_env()
+    if world > 1 and a.pose_smooth:
+        return modes.refuse_sharded_smooth(world)
     if a.scene not in modes.SCENES:
         print('Invalid scene:', a.scene)
         return 1
@@ -110,7 +115,8 @@ def main(argv=None):
     out = eval(paths, transform, W, a.output_folder, image_size=size, batch=a.batch,
                frames=frames_of(0, T) if paths is None else None, label_paths=label_paths, device='cuda:%d' % a.gpu)
     if a.pose:
-        modes.write_poses(out[0] if label_paths is not None else out, a.output_folder, pose=pose)
+        smooth = dict(motion=a.pose_motion, sequence_length=a.pose_sequence_length or 0) if a.pose_smooth else None
+        modes.write_poses(out[0] if label_paths is not None else out, a.output_folder, pose=pose, smooth=smooth)
     return 0
 
 

@@ -26,6 +26,7 @@ WINO_FORM_S2_F42 = 5                                       # ... its polyphase +
 PNP_OK, PNP_TOO_FEW_POINTS, PNP_NO_HYPOTHESIS = 0, 1, 2      # kfn_pnp_ransac info[:, 0] (KFN_PNP_*)
 PNP_MAX_HYPOTHESES = 1024
 POSE_UPDATED, POSE_MISSING, POSE_REJECTED, POSE_INIT, POSE_NONE = 0, 1, 2, 3, 4     # kfn_pose_filter flags (KFN_POSE_*)
+POSE_MODEL_WALK, POSE_MODEL_VELOCITY = 0, 1                                        # kfn_pose_track_desc.model (KFN_POSE_MODEL_*)
 PACK_FORWARD, PACK_INPUT_GRAD_S1, PACK_INPUT_GRAD_S2 = 0, 1, 2     # kfn_pack_conv_weights kind (KFN_PACK_*)
 CFG_AUTO, CFG_160x128, CFG_128x128, CFG_128x64, CFG_128x32, CFG_64x64, CFG_256x32, CFG_192x64 = 0, 1, 2, 3, 4, 5, 6, 7
 
@@ -78,6 +79,13 @@ class PoseFilterDesc(SizedStructure):
     """kfn_pose_filter_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
     _fields_ = [('struct_size', C.c_int32), ('S', C.c_int32), ('T', C.c_int32), ('rot_sigma', C.c_float),
                 ('trans_sigma', C.c_float), ('gate', C.c_float), ('max_rejects', C.c_int32)]
+
+
+class PoseTrackDesc(SizedStructure):
+    """kfn_pose_track_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
+    _fields_ = [('struct_size', C.c_int32), ('S', C.c_int32), ('T', C.c_int32), ('model', C.c_int32), ('smooth', C.c_int32),
+                ('rot_sigma', C.c_float), ('trans_sigma', C.c_float), ('rot_rate_sigma', C.c_float),
+                ('trans_rate_sigma', C.c_float), ('gate', C.c_float), ('max_rejects', C.c_int32)]
 
 
 class CoordLossDesc(SizedStructure):
@@ -267,6 +275,10 @@ SYMBOLS = {
     # uncertainty-aware poses: weighted refinement, pose covariance, pose filter (added exports, ABI 13)
     'kfn_pnp_ransac_unc': (_i, [C.POINTER(PnPDesc), C.POINTER(PnPUncDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'kfn_pose_filter': (_i, [C.POINTER(PoseFilterDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the pose tracker: motion models, backward pass, carried state (added exports, ABI 13)
+    'kfn_pose_track_state_bytes': (_i, [C.POINTER(PoseTrackDesc), C.POINTER(_sz)]),
+    'kfn_pose_track_scratch_bytes': (_i, [C.POINTER(PoseTrackDesc), C.POINTER(_sz)]),
+    'kfn_pose_track': (_i, [C.POINTER(PoseTrackDesc)] + [_vp] * 11),
     # the reprojection loss for stages 1 and 3, with the augmented pixel map (added exports, ABI 13)
     'kfn_reproj_loss_grad': (_i, [C.POINTER(ReprojDesc), _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'kfn_augment_pixel_map': (_i, [C.POINTER(AugmentDesc), C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),

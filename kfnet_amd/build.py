@@ -43,6 +43,8 @@ EXTRA = {
     'kfn_loss_scale.hip': ['-ffp-contract=off'],
     # the pose filter: a serial fp64 recursion per sequence, rounded product by product as its numpy restatement, like the scan
     'kfn_pose_filter.hip': ['-ffp-contract=off'],
+    # the pose tracker: the filter's recursion under two motion models and its backward pass, rounded as their restatement
+    'kfn_pose_track.hip': ['-ffp-contract=off'],
     # the reprojection loss: per-cell terms as the other loss launches' 
     'kfn_reproj.hip': ['-ffp-contract=off'],
 }

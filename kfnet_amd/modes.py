@@ -10,6 +10,7 @@ File contracts (float32 .npy, one per frame, [h,w,C] on the label grid h = ceil(
                  images k and k+1 of image_list.txt (vis/vis_optical_flow_list.py's arguments)
   pose_<i>.txt   --pose: the camera-to-world pose solved from coord_<i>.npy (kfnet_amd/KFNet/pnp.py)
   pose_cov_<i>.txt   --pose_weighted: that pose refined with the records' uncertainty as weights, and its 6x6 covariance
+  pose_smooth_<i>.txt   --pose_smooth: the --pose_weighted poses tracked and smoothed in time (single-process runs)
 """
 import contextlib
 import os
@@ -142,13 +143,38 @@ def add_pose_flags(ap):
     ap.add_argument('--pose', action='store_true', help='also write pose_<i>.txt (RANSAC-PnP on the device)')
     ap.add_argument('--pose_weighted', action='store_true',
                     help='--pose with the refinement weighted by the records\' uncertainty; also writes pose_cov_<i>.txt')
+    ap.add_argument('--pose_smooth', action='store_true',
+                    help='--pose_weighted, and at the end the poses are tracked and smoothed backwards in time '
+                         '(kfn_pose_track); writes pose_smooth_<i>.txt.  Single-process runs only')
+    ap.add_argument('--pose_motion', choices=['walk', 'velocity'], default=None,
+                    help='--pose_smooth: the tracker\'s motion model (walk)')
+    ap.add_argument('--pose_sequence_length', type=int, default=None,
+                    help='--pose_smooth: frames per tracked sequence (the run\'s Kalman reset period where the program '
+                         'has one, otherwise the whole run)')
 
 
-def pose_argument(a):
-    """The parsed flags -> the run functions' `pose`; --pose_weighted implies --pose (a.pose is set)."""
+def pose_argument(a, ap=None):
+    """The parsed flags -> the run functions' `pose`; --pose_smooth implies --pose_weighted, which implies --pose (a.pose
+    is set).  With the parser `ap`, --pose_motion / --pose_sequence_length without --pose_smooth are argparse errors."""
+    if ap is not None:
+        for name in ('pose_motion', 'pose_sequence_length'):
+            if getattr(a, name) is not None and not a.pose_smooth:
+                ap.error('--%s needs --pose_smooth' % name)
+        if a.pose_sequence_length is not None and a.pose_sequence_length < 1:
+            ap.error('--pose_sequence_length must be >= 1')
+    if a.pose_smooth:
+        a.pose_weighted = True
     if a.pose_weighted:
         a.pose = True
     return POSE_WEIGHTED if a.pose_weighted else a.pose
+
+
+def refuse_sharded_smooth(world):
+    """Exit status 1, after one line, for --pose_smooth in a sharded run (WORLD_SIZE > 1): the tracker runs over whole
+    sequences, which no rank holds.  Called before any device is initialised."""
+    print('--pose_smooth is not supported in the sharded run (WORLD_SIZE=%d): run one process, or smooth the written '
+          'poses with python -m kfnet_amd.KFNet.pnp --smooth --rts' % world, file=sys.stderr)
+    return 1
 
 
 def pose_solver(h, w, weighted=False):
@@ -159,9 +185,23 @@ def pose_solver(h, w, weighted=False):
     return PnPSolver(h, w, spec.focal_x, spec.focal_y, spec.u, spec.v, weighted=weighted)
 
 
-def write_poses(records, output_folder, batch=POSE_BATCH, pose=True):
+def write_smoothed_poses(poses, cov, output_folder, motion=None, sequence_length=0):
+    """--pose_smooth of a single-process run: the run's poses [T,4,4] and covariances [T,6,6] (the 52 floats per frame that
+    --pose_weighted writes) cut into sequences of `sequence_length` frames (0: one), each tracked from a fresh state and
+    smoothed backwards (PoseTracker(motion, smooth=True)); pose_smooth_<i>.txt.  Returns the smoothed poses [T,4,4]."""
+    from .KFNet.pnp import smooth_in_sequences, write_pose
+    from .KFNet.pose_filter import PoseTracker
+    smooth = smooth_in_sequences(PoseTracker(motion or 'walk', smooth=True), poses, cov, sequence_length or 0)[4]
+    if _is_dir(output_folder):
+        for i in range(poses.shape[0]):
+            write_pose(os.path.join(output_folder, 'pose_smooth_%d.txt' % i), smooth[i])
+    return smooth
+
+
+def write_poses(records, output_folder, batch=POSE_BATCH, pose=True, smooth=None):
     """--pose of a single-process run: camera-to-world poses of the in-memory records [T,h,w,4] (KFNetDataSpec
-    intrinsics), pose_<i>.txt next to coord_<i>.npy; pose = POSE_WEIGHTED: the weighted refinement, and pose_cov_<i>.txt.
+    intrinsics), pose_<i>.txt next to coord_<i>.npy; pose = POSE_WEIGHTED: the weighted refinement, and pose_cov_<i>.txt;
+    `smooth` (with POSE_WEIGHTED): write_smoothed_poses' keyword arguments for --pose_smooth.
     Returns (poses [T,4,4], info [T,4])."""
     from .KFNet.pnp import solve_in_batches, solve_unc_in_batches, write_covariance, write_pose
     solver = pose_solver(records.shape[1], records.shape[2], pose == POSE_WEIGHTED)
@@ -175,6 +215,10 @@ def write_poses(records, output_folder, batch=POSE_BATCH, pose=True):
             if solver.weighted:
                 write_covariance(os.path.join(output_folder, 'pose_cov_%d.txt' % i), cov[i])
     print('poses: %d of %d frames solved' % (int((info[:, 0] == 0).sum()), records.shape[0]))
+    if smooth is not None:
+        if not solver.weighted:
+            raise ValueError('smoothing needs the covariances of pose = POSE_WEIGHTED')
+        write_smoothed_poses(poses, cov, output_folder, **smooth)
     return poses, info
 
 

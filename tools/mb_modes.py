@@ -8,7 +8,9 @@ resident chunk (KFNetEngine: heavy phase on two streams + the Kalman scan; the s
 the record launch).  Several --batch values show where an engine stops scaling with the batch.
 
 `--engines pose` times the pose stage instead: ms per PnPSolver.solve of --frames records on a 60x80 grid (20 % outliers,
-per-cell sigma 0.5-4 cm) against solve_unc unweighted and weighted, in the same JSON line under "pose_ms".
+per-cell sigma 0.5-4 cm) against solve_unc unweighted and weighted, in the same JSON line under "pose_ms"; and, under
+"pose_track_ms", ms per call of PoseFilter.run and of PoseTracker.run (both models, with and without the backward pass)
+at S x T = 1 x 1000, 8 x 500 and 64 x 64, the five taken in turns.
 """
 import argparse
 import json
@@ -50,6 +52,42 @@ def time_pose_stage(frames, reps, warmup, h=60, w=80):
     return ms
 
 
+def time_pose_track(reps, warmup, shapes=((1, 1000), (8, 500), (64, 64))):
+    """{'SxT': {call: ms}}: kfn_pose_filter and kfn_pose_track on S random-walk sequences of T frames (1 cm per frame,
+    measurements of 2 cm and 0.3 degrees that all pass the gate), resident on the device; the calls take turns, each
+    timed with its own pair of events, and the mean over `reps` turns is reported."""
+    import numpy as np
+    import torch
+    from kfnet_amd.KFNet.pose_filter import PoseFilter, PoseTracker
+    rng = np.random.default_rng(0)
+    out = {}
+    for S, T in shapes:
+        poses = np.tile(np.eye(4, dtype=np.float32), (S, T, 1, 1))
+        poses[..., :3, 3] = np.cumsum(rng.normal(scale=0.01, size=(S, T, 3)), axis=1) + rng.normal(scale=0.02, size=(S, T, 3))
+        cov = np.tile(np.diag([0.005 ** 2] * 3 + [0.02 ** 2] * 3).astype(np.float32), (S, T, 1, 1))
+        p, c = torch.from_numpy(poses).cuda(), torch.from_numpy(cov).cuda()
+        trackers = {'%s%s' % (m, '+rts' if sm else ''): PoseTracker(m, smooth=sm)
+                    for m in ('walk', 'velocity') for sm in (False, True)}
+
+        def tracked(tr):
+            tr.reset()
+            return tr.run(p, c)
+        calls = {'pose_filter': lambda: PoseFilter().run(p, c)}
+        calls.update({name: (lambda tr=tr: tracked(tr)) for name, tr in trackers.items()})
+        total = {name: 0.0 for name in calls}
+        for turn in range(max(warmup, 1) + reps):
+            for name, call in calls.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                call()
+                e1.record()
+                e1.synchronize()
+                if turn >= max(warmup, 1):
+                    total[name] += e0.elapsed_time(e1)
+        out['%dx%d' % (S, T)] = {name: round(v / reps, 3) for name, v in total.items()}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, nargs='+', default=[4])
@@ -78,6 +116,7 @@ def main():
     if 'pose' in a.engines:
         a.engines.remove('pose')
         out['pose_ms'] = time_pose_stage(a.frames, a.reps, a.warmup)
+        out['pose_track_ms'] = time_pose_track(a.reps, a.warmup)
     for name in a.engines:
         out['fps'][name] = {}
         for B in a.batch:
