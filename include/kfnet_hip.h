@@ -57,7 +57,8 @@ extern "C" {
  * and kfn_filter_backward_joint (joint stage 3: both networks trained through the filter), and kfn_pnp_ransac_unc and
  * kfn_pose_filter (uncertainty-aware poses: weighted refinement, pose covariance, pose filter), and kfn_reproj_loss_grad
  * and kfn_augment_pixel_map (the reprojection loss of KFNet/KFNet.py:405-428 for stages 1 and 3), and kfn_pose_track,
- * kfn_pose_track_state_bytes and kfn_pose_track_scratch_bytes (the pose tracker: motion models, backward pass, carried state). */
+ * kfn_pose_track_state_bytes and kfn_pose_track_scratch_bytes (the pose tracker: motion models, backward pass, carried state),
+ * and kfn_pnp_guided_scratch_bytes, kfn_pnp_ransac_guided and kfn_pnp_hypotheses_guided (hypotheses drawn by confidence). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -644,6 +645,36 @@ typedef struct kfn_pnp_unc_desc {
 #define KFN_PNP_UNC_DESC_INIT {(int32_t)sizeof(kfn_pnp_unc_desc), 0, 1.0f}
 int kfn_pnp_ransac_unc(const kfn_pnp_desc* desc, const kfn_pnp_unc_desc* unc, const float* records, float* poses, float* cov,
                        float* quality, int32_t* info, void* scratch, void* stream);
+
+/* ---- guided sampling: hypotheses drawn by the maps' confidence (added exports, the ABI number stays 13) -----------------
+ * kfn_pnp_ransac_guided is kfn_pnp_ransac / kfn_pnp_ransac_unc with one step changed: the four cells of a hypothesis are
+ * drawn in proportion to an integer weight of their confidence instead of uniformly ("Guided sampling").
+ * Candidates, the hash, the 16-draw limit, P3P, scoring, selection and refinement are unchanged.
+ *   weight      c = record[3]; q = (int)floorf((fminf(c, confidence_cap) - min_confidence) * 16.0f) + 1 in binary32, every
+ *               operation rounded to nearest; q >= 1, c = +inf takes the cap's weight.  w = q (KFN_PNP_SAMPLE_CONFIDENCE) or
+ *               q * q (KFN_PNP_SAMPLE_CONFIDENCE_SQ), unsigned 64-bit.  0 <= min_confidence < confidence_cap <= 4096.
+ *   cum         cum[i] = w[0] + .. + w[i] over the n candidates in raster order, uint64; total = cum[n-1] < 2^48
+ *   draw        h as above; target = floor(h * total / 2^32), the exact integer; the candidate drawn is the first i with
+ *               cum[i] > target.  With equal confidences this is (uint64(h) * n) >> 32: the uniform draw, bit for bit.
+ *   unc         NULL: the refinement is kfn_pnp_ransac's, cov and quality must be NULL; otherwise kfn_pnp_ransac_unc's rules
+ *   scratch     kfn_pnp_guided_scratch_bytes: kfn_pnp_scratch_bytes' arrays, then cum [B][h*w] uint64 and n [B]
+ * kfn_pnp_hypotheses_guided is the probe (kfn_pnp_hypotheses' three outputs) and also returns cum [B][h*w] (row b: n[b]
+ * entries are written) and n [B]; either may be NULL.  Bit-identical from launch to launch. */
+#define KFN_PNP_SAMPLE_CONFIDENCE 1
+#define KFN_PNP_SAMPLE_CONFIDENCE_SQ 2
+typedef struct kfn_pnp_sample_desc {
+  int32_t struct_size;     /* = sizeof(kfn_pnp_sample_desc) as the caller compiled it */
+  int32_t mode;            /* KFN_PNP_SAMPLE_CONFIDENCE or KFN_PNP_SAMPLE_CONFIDENCE_SQ */
+  float confidence_cap;    /* confidences above it weigh as it does (1000); finite, > min_confidence, <= 4096 */
+} kfn_pnp_sample_desc;
+#define KFN_PNP_SAMPLE_DESC_INIT {(int32_t)sizeof(kfn_pnp_sample_desc), KFN_PNP_SAMPLE_CONFIDENCE, 1000.0f}
+int kfn_pnp_guided_scratch_bytes(const kfn_pnp_desc* desc, const kfn_pnp_sample_desc* sample, size_t* bytes);
+int kfn_pnp_ransac_guided(const kfn_pnp_desc* desc, const kfn_pnp_sample_desc* sample, const kfn_pnp_unc_desc* unc,
+                          const float* records, float* poses, float* cov, float* quality, int32_t* info, void* scratch,
+                          void* stream);
+int kfn_pnp_hypotheses_guided(const kfn_pnp_desc* desc, const kfn_pnp_sample_desc* sample, const float* records,
+                              int32_t* samples, float* hyp_poses, int32_t* counts, uint64_t* cum, int32_t* n, void* scratch,
+                              void* stream);
 
 /* Random-walk error-state filter over a sequence of such poses, one sequence per lane, fp64, serial over t.  State: (R, p)
  * camera-to-world and P (6x6, the body-frame coordinates (dtheta, drho) above).  flags [S,T]:

@@ -28,7 +28,8 @@ distance errors in cm, NIS-in-band fraction) and the final summary are printed
 `--pose_sequence_length` frames (default: the reset period, 500), tracked under `--pose_motion` (walk) and smoothed backwards
 (kfnet_amd/KFNet/pose_filter.py PoseTracker); it writes `pose_smooth_<i>.txt`.
 `--pose` also solves every frame's camera pose on the device (kfnet_amd/KFNet/pnp.py) and writes `pose_<i>.txt` next to
-each `coord_<i>.npy`.
+each `coord_<i>.npy`.  `--pose_sampling confidence | confidence2 [--pose_confidence_cap]` draws its hypotheses by the
+records' confidence (DESIGN.md 5c "Guided sampling"), in the sharded runs too.
 """
 import argparse
 import os

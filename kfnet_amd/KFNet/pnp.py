@@ -6,6 +6,7 @@ a git-lfs pointer; this module is that last stage, with the reference's command-
     python -m kfnet_amd.KFNet.pnp <coord_file_list> <output_folder> [--gt <pose_list>] [--thread_num N]
                                   [--focal_x F --focal_y F --u U --v V] [--hypotheses 256] [--batch 64]
                                   [--weighted] [--pixel_sigma 1.0] [--covariance]
+                                  [--sampling {uniform,confidence,confidence2} [--confidence_cap 1000]]
                                   [--smooth [--rot_sigma 0.02 --trans_sigma 0.02 --gate 22.46 --max_rejects 3
                                              --sequence_length N
                                              --motion {walk,velocity} --rts --rot_rate_sigma 0.05 --trans_rate_sigma 0.05]]
@@ -21,8 +22,10 @@ first) next to each pose; --smooth runs the listed frames, cut into sequences of
 sequence), through the pose filter and writes `pose_smooth_<i>.txt`.  --motion, --rts and the two rate sigmas run the
 pose tracker instead (kfn_pose_track, DESIGN.md 5c "Pose tracker"): --motion velocity also estimates a body-frame twist
 per frame, --rts smooths each sequence backwards as well, and `pose_smooth_<i>.txt` then holds the smoothed pose; with
---covariance the tracker also writes `pose_smooth_cov_<i>.txt`.  Without these flags the program does and prints what it
-always did.
+--covariance the tracker also writes `pose_smooth_cov_<i>.txt`.  --sampling confidence / confidence2 draws the four cells
+of every hypothesis in proportion to the maps' confidence above --min_confidence, or to its square, capped at
+--confidence_cap (kfn_pnp_ransac_guided, DESIGN.md 5c "Guided sampling").  Without these flags the program does and prints
+what it always did.
 """
 import argparse
 import ctypes as C
@@ -34,6 +37,7 @@ import numpy as np
 from .. import _lib
 from ..tools.io import read_lines
 
+SAMPLING_MODES = {'uniform': 0, 'confidence': _lib.PNP_SAMPLE_CONFIDENCE, 'confidence2': _lib.PNP_SAMPLE_CONFIDENCE_SQ}
 STATUS_NAMES = {_lib.PNP_OK: 'ok', _lib.PNP_TOO_FEW_POINTS: 'too few points', _lib.PNP_NO_HYPOTHESIS: 'no hypothesis'}
 
 
@@ -42,14 +46,28 @@ class PnPSolver(object):
     (fx = fy = 525, u = 320, v = 240).  `solve` returns camera-to-world poses [B,4,4] (NaN on failure) and info [B,4] =
     (status, candidates, final inliers, best hypothesis): numpy in, numpy out; a CUDA tensor in, tensors out (no sync).
     `solve_unc` (kfn_pnp_ransac_unc) also returns every pose's 6x6 covariance and (cost, degrees of freedom); `weighted`
-    and `pixel_sigma` act on it alone."""
+    and `pixel_sigma` act on it alone.  `sampling` = 'confidence' or 'confidence2' draws every hypothesis' cells in
+    proportion to the confidence above `min_confidence`, capped at `confidence_cap`, or to its square
+    (kfn_pnp_ransac_guided, DESIGN.md 5c "Guided sampling"); 'uniform' makes the calls above."""
 
     def __init__(self, h, w, fx=525., fy=525., u=320., v=240., hypotheses=256, refine_iters=10, min_points=16, seed=0,
-                 min_confidence=20., inlier_px=10., cell_stride=8, weighted=False, pixel_sigma=1.0):
+                 min_confidence=20., inlier_px=10., cell_stride=8, weighted=False, pixel_sigma=1.0, sampling='uniform',
+                 confidence_cap=1000.):
         if not 1 <= int(hypotheses) <= _lib.PNP_MAX_HYPOTHESES:
             raise ValueError('hypotheses must be in 1..%d' % _lib.PNP_MAX_HYPOTHESES)
         if not float(pixel_sigma) > 0.0:
             raise ValueError('pixel_sigma must be > 0')
+        if sampling not in SAMPLING_MODES:
+            raise ValueError('sampling must be one of %s' % ', '.join(sorted(SAMPLING_MODES)))
+        if sampling != 'uniform':
+            # what kfn_pnp_ransac_guided would refuse, in float32 as it sees the two numbers
+            cap, minc = float(np.float32(confidence_cap)), float(np.float32(min_confidence))
+            if not minc >= 0.0:
+                raise ValueError('guided sampling needs min_confidence >= 0')
+            if not (np.isfinite(cap) and minc < cap <= _lib.PNP_MAX_CONFIDENCE_CAP):
+                raise ValueError('confidence_cap must be finite, above min_confidence and at most %g'
+                                 % _lib.PNP_MAX_CONFIDENCE_CAP)
+        self.sampling, self.confidence_cap = sampling, float(confidence_cap)
         self.weighted, self.pixel_sigma = bool(weighted), float(pixel_sigma)
         self.h, self.w = int(h), int(w)
         self.fx, self.fy, self.u, self.v = float(fx), float(fy), float(u), float(v)
@@ -63,6 +81,24 @@ class PnPSolver(object):
                             refine_iters=self.refine_iters, min_points=self.min_points, fx=self.fx, fy=self.fy, u=self.u,
                             v=self.v, cell_stride=self.cell_stride, min_confidence=self.min_confidence,
                             inlier_px=self.inlier_px)
+
+    def sample_desc(self):
+        """kfn_pnp_sample_desc of a guided solver; None with sampling = 'uniform'."""
+        if self.sampling == 'uniform':
+            return None
+        return _lib.PnPSampleDesc(mode=SAMPLING_MODES[self.sampling], confidence_cap=self.confidence_cap)
+
+    def _scratch_for(self, lib, d, s, device):
+        import torch
+        nbytes = C.c_size_t()
+        if s is None:
+            _lib.check(lib.kfn_pnp_scratch_bytes(C.byref(d), C.byref(nbytes)), 'kfn_pnp_scratch_bytes')
+        else:
+            _lib.check(lib.kfn_pnp_guided_scratch_bytes(C.byref(d), C.byref(s), C.byref(nbytes)),
+                       'kfn_pnp_guided_scratch_bytes')
+        if self._scratch is None or self._scratch.numel() < nbytes.value or self._scratch.device != device:
+            self._scratch = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=device)
+        return self._scratch
 
     def _device_records(self, records):
         import torch
@@ -82,15 +118,17 @@ class PnPSolver(object):
         rec, host = self._device_records(records)
         B = rec.shape[0]
         d = self.desc(B, t0, rec.shape[3])
-        nbytes = C.c_size_t()
-        _lib.check(lib.kfn_pnp_scratch_bytes(C.byref(d), C.byref(nbytes)), 'kfn_pnp_scratch_bytes')
-        if self._scratch is None or self._scratch.numel() < nbytes.value or self._scratch.device != rec.device:
-            self._scratch = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=rec.device)
+        s = self.sample_desc()
+        scratch = self._scratch_for(lib, d, s, rec.device)
         poses = torch.empty((B, 4, 4), dtype=torch.float32, device=rec.device)
         info = torch.empty((B, 4), dtype=torch.int32, device=rec.device)
         stream = torch.cuda.current_stream(rec.device).cuda_stream
-        _lib.check(lib.kfn_pnp_ransac(C.byref(d), rec.data_ptr(), poses.data_ptr(), info.data_ptr(),
-                                      self._scratch.data_ptr(), stream), 'kfn_pnp_ransac')
+        if s is None:
+            _lib.check(lib.kfn_pnp_ransac(C.byref(d), rec.data_ptr(), poses.data_ptr(), info.data_ptr(),
+                                          scratch.data_ptr(), stream), 'kfn_pnp_ransac')
+        else:
+            _lib.check(lib.kfn_pnp_ransac_guided(C.byref(d), C.byref(s), None, rec.data_ptr(), poses.data_ptr(), None, None,
+                                                 info.data_ptr(), scratch.data_ptr(), stream), 'kfn_pnp_ransac_guided')
         if host:
             return poses.cpu().numpy(), info.cpu().numpy()
         return poses, info
@@ -106,25 +144,30 @@ class PnPSolver(object):
         B = rec.shape[0]
         d = self.desc(B, t0, rec.shape[3])
         q = _lib.PnPUncDesc(weighted=int(self.weighted), pixel_sigma=self.pixel_sigma)
-        nbytes = C.c_size_t()
-        _lib.check(lib.kfn_pnp_scratch_bytes(C.byref(d), C.byref(nbytes)), 'kfn_pnp_scratch_bytes')
-        if self._scratch is None or self._scratch.numel() < nbytes.value or self._scratch.device != rec.device:
-            self._scratch = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=rec.device)
+        s = self.sample_desc()
+        scratch = self._scratch_for(lib, d, s, rec.device)
         poses = torch.empty((B, 4, 4), dtype=torch.float32, device=rec.device)
         cov = torch.empty((B, 6, 6), dtype=torch.float32, device=rec.device)
         quality = torch.empty((B, 2), dtype=torch.float32, device=rec.device)
         info = torch.empty((B, 4), dtype=torch.int32, device=rec.device)
         stream = torch.cuda.current_stream(rec.device).cuda_stream
-        _lib.check(lib.kfn_pnp_ransac_unc(C.byref(d), C.byref(q), rec.data_ptr(), poses.data_ptr(), cov.data_ptr(),
-                                          quality.data_ptr(), info.data_ptr(), self._scratch.data_ptr(), stream),
-                   'kfn_pnp_ransac_unc')
+        if s is None:
+            _lib.check(lib.kfn_pnp_ransac_unc(C.byref(d), C.byref(q), rec.data_ptr(), poses.data_ptr(), cov.data_ptr(),
+                                              quality.data_ptr(), info.data_ptr(), scratch.data_ptr(), stream),
+                       'kfn_pnp_ransac_unc')
+        else:
+            _lib.check(lib.kfn_pnp_ransac_guided(C.byref(d), C.byref(s), C.byref(q), rec.data_ptr(), poses.data_ptr(),
+                                                 cov.data_ptr(), quality.data_ptr(), info.data_ptr(), scratch.data_ptr(),
+                                                 stream), 'kfn_pnp_ransac_guided')
         if host:
             return poses.cpu().numpy(), cov.cpu().numpy(), quality.cpu().numpy(), info.cpu().numpy()
         return poses, cov, quality, info
 
-    def hypotheses_probe(self, records, t0=0):
+    def hypotheses_probe(self, records, t0=0, with_cdf=False):
         """kfn_pnp_hypotheses: (samples [B,H,4], hypothesis poses [B,H,12] = [R | t] world-to-camera, counts [B,H]) as
-        numpy arrays -- the sampled and scored hypotheses before selection."""
+        numpy arrays -- the sampled and scored hypotheses before selection.  A guided solver goes through
+        kfn_pnp_hypotheses_guided, and `with_cdf` then appends (cum [B,h*w] uint64, of which row b holds n[b] entries and
+        zeros behind them, n [B])."""
         import torch
         lib = _lib.load()
         rec, _ = self._device_records(records)
@@ -133,9 +176,25 @@ class PnPSolver(object):
         samples = torch.empty((B, H, 4), dtype=torch.int32, device=rec.device)
         hp = torch.empty((B, H, 12), dtype=torch.float32, device=rec.device)
         counts = torch.empty((B, H), dtype=torch.int32, device=rec.device)
-        _lib.check(lib.kfn_pnp_hypotheses(C.byref(d), rec.data_ptr(), samples.data_ptr(), hp.data_ptr(), counts.data_ptr(),
-                                          torch.cuda.current_stream(rec.device).cuda_stream), 'kfn_pnp_hypotheses')
-        return samples.cpu().numpy(), hp.cpu().numpy(), counts.cpu().numpy()
+        stream = torch.cuda.current_stream(rec.device).cuda_stream
+        s = self.sample_desc()
+        if s is None:
+            if with_cdf:
+                raise ValueError("with_cdf needs sampling = 'confidence' or 'confidence2'")
+            _lib.check(lib.kfn_pnp_hypotheses(C.byref(d), rec.data_ptr(), samples.data_ptr(), hp.data_ptr(),
+                                              counts.data_ptr(), stream), 'kfn_pnp_hypotheses')
+            return samples.cpu().numpy(), hp.cpu().numpy(), counts.cpu().numpy()
+        scratch = self._scratch_for(lib, d, s, rec.device)
+        cum = torch.zeros((B, self.h * self.w), dtype=torch.int64, device=rec.device) if with_cdf else None
+        n = torch.zeros((B,), dtype=torch.int32, device=rec.device) if with_cdf else None
+        _lib.check(lib.kfn_pnp_hypotheses_guided(C.byref(d), C.byref(s), rec.data_ptr(), samples.data_ptr(), hp.data_ptr(),
+                                                 counts.data_ptr(), cum.data_ptr() if with_cdf else None,
+                                                 n.data_ptr() if with_cdf else None, scratch.data_ptr(), stream),
+                   'kfn_pnp_hypotheses_guided')
+        out = (samples.cpu().numpy(), hp.cpu().numpy(), counts.cpu().numpy())
+        if with_cdf:
+            out += (cum.cpu().numpy().view(np.uint64), n.cpu().numpy())
+        return out
 
 
 def read_pose(path):
@@ -270,7 +329,19 @@ def main(argv=None):
                     help='--smooth --motion velocity: sigma of the unknown angular rate at a (re-)start, rad per frame (0.05)')
     ap.add_argument('--trans_rate_sigma', type=float, default=None,
                     help='--smooth --motion velocity: sigma of the unknown velocity at a (re-)start, m per frame (0.05)')
+    ap.add_argument('--sampling', choices=['uniform', 'confidence', 'confidence2'], default='uniform',
+                    help='how the four cells of a hypothesis are drawn: uniformly, or in proportion to the confidence '
+                         'above --min_confidence (confidence) or to its square (confidence2)')
+    ap.add_argument('--confidence_cap', type=float, default=None,
+                    help='--sampling confidence / confidence2: confidences above it weigh as it does (1000)')
     a = ap.parse_args(argv)
+    if a.confidence_cap is not None and a.sampling == 'uniform':
+        ap.error('--confidence_cap needs --sampling confidence or confidence2')
+    guided = dict(sampling=a.sampling, confidence_cap=1000. if a.confidence_cap is None else a.confidence_cap)
+    try:
+        PnPSolver(1, 1, min_confidence=a.min_confidence, **guided)
+    except ValueError as e:
+        ap.error('--sampling / --confidence_cap / --min_confidence: %s' % e)
     uncertain = a.weighted or a.covariance or a.smooth
     if a.pixel_sigma is not None and not uncertain:
         ap.error('--pixel_sigma needs --weighted, --covariance or --smooth')
@@ -316,7 +387,7 @@ def main(argv=None):
             return 1
     solver = PnPSolver(h, w, a.focal_x, a.focal_y, a.u, a.v, hypotheses=a.hypotheses, refine_iters=a.refine_iters,
                        seed=a.seed, min_confidence=a.min_confidence, inlier_px=a.inlier_px, weighted=a.weighted,
-                       pixel_sigma=1.0 if a.pixel_sigma is None else a.pixel_sigma)
+                       pixel_sigma=1.0 if a.pixel_sigma is None else a.pixel_sigma, **guided)
     if uncertain:
         poses, cov, _, info = solve_unc_in_batches(solver, np.stack(records), max(1, a.batch))
     else:

@@ -25,6 +25,8 @@ WINO_FORM_S2_EIGHT_WAVE = 4                                # ... for kfn_conv2d_
 WINO_FORM_S2_F42 = 5                                       # ... its polyphase + F(4,2) form (wino_s2c_kernel)
 PNP_OK, PNP_TOO_FEW_POINTS, PNP_NO_HYPOTHESIS = 0, 1, 2      # kfn_pnp_ransac info[:, 0] (KFN_PNP_*)
 PNP_MAX_HYPOTHESES = 1024
+PNP_SAMPLE_CONFIDENCE, PNP_SAMPLE_CONFIDENCE_SQ = 1, 2       # kfn_pnp_sample_desc.mode (KFN_PNP_SAMPLE_*)
+PNP_MAX_CONFIDENCE_CAP = 4096.
 POSE_UPDATED, POSE_MISSING, POSE_REJECTED, POSE_INIT, POSE_NONE = 0, 1, 2, 3, 4     # kfn_pose_filter flags (KFN_POSE_*)
 POSE_MODEL_WALK, POSE_MODEL_VELOCITY = 0, 1                                        # kfn_pose_track_desc.model (KFN_POSE_MODEL_*)
 PACK_FORWARD, PACK_INPUT_GRAD_S1, PACK_INPUT_GRAD_S2 = 0, 1, 2     # kfn_pack_conv_weights kind (KFN_PACK_*)
@@ -73,6 +75,11 @@ class PnPDesc(SizedStructure):
 class PnPUncDesc(SizedStructure):
     """kfn_pnp_unc_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
     _fields_ = [('struct_size', C.c_int32), ('weighted', C.c_int32), ('pixel_sigma', C.c_float)]
+
+
+class PnPSampleDesc(SizedStructure):
+    """kfn_pnp_sample_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
+    _fields_ = [('struct_size', C.c_int32), ('mode', C.c_int32), ('confidence_cap', C.c_float)]
 
 
 class PoseFilterDesc(SizedStructure):
@@ -282,6 +289,10 @@ SYMBOLS = {
     # the reprojection loss for stages 1 and 3, with the augmented pixel map (added exports, ABI 13)
     'kfn_reproj_loss_grad': (_i, [C.POINTER(ReprojDesc), _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'kfn_augment_pixel_map': (_i, [C.POINTER(AugmentDesc), C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]),
+    # guided sampling: hypotheses drawn by the maps' confidence (added exports, ABI 13)
+    'kfn_pnp_guided_scratch_bytes': (_i, [C.POINTER(PnPDesc), C.POINTER(PnPSampleDesc), C.POINTER(_sz)]),
+    'kfn_pnp_ransac_guided': (_i, [C.POINTER(PnPDesc), C.POINTER(PnPSampleDesc), C.POINTER(PnPUncDesc)] + [_vp] * 7),
+    'kfn_pnp_hypotheses_guided': (_i, [C.POINTER(PnPDesc), C.POINTER(PnPSampleDesc)] + [_vp] * 8),
 }
 
 _lib = None

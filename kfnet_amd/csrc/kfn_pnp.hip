@@ -16,6 +16,9 @@
 //                         order (per-lane strided sums, a butterfly per wave, the four waves in order).
 //      pnp_refine_unc_kernel   its sibling behind kfn_pnp_ransac_unc: optionally weighted by the records' sigma propagated
 //                         to the image plane; also writes the pose's 6x6 covariance and (cost, degrees of freedom).
+//   kfn_pnp_ransac_guided runs pnp_cdf_kernel (per frame: integer weights from the confidence, their cumulative sums in
+//                         uint64) and pnp_hyp_guided_kernel (stage 1 with every draw taken from those sums) in front of
+//                         stages 2 and 3: DESIGN.md 5c "Guided sampling".
 // No host round trip between the stages, no device RNG state, no float atomics: the result is the same bits on every launch.
 #include <cmath>
 
@@ -832,6 +835,108 @@ __global__ __launch_bounds__(NT) void pnp_refine_unc_kernel(PnPArgs a, double ps
   }
 }
 
+// ---- guided sampling (kfn_pnp_ransac_guided): draws in proportion to the confidence above the threshold ----------------
+// DESIGN.md 5c "Guided sampling" and tests/pnp_guided_ref.py state the same rule.  A candidate's integer weight, from
+// c = record[3] in binary32, every operation rounded to nearest (a subtraction feeds a multiplication by a power of two: no
+// contraction applies): q = (int)floorf((fminf(c, cap) - minc) * 16) + 1 >= 1; w = q, or q * q in the squared mode.
+// With cap <= 4096, q <= 65537 and the sum of 32768 weights stays below 2^48.
+__device__ __forceinline__ unsigned long long guided_weight(float c, float minc, float cap, int squared) {
+  const float d = fminf(c, cap) - minc;
+  const unsigned long long q = (unsigned long long)((int)floorf(d * 16.0f) + 1);
+  return squared ? q * q : q;
+}
+
+// grid (B): cum[b][i] = w[0] + .. + w[i] over the frame's candidates in raster order (build_candidates' order and rule),
+// ncand[b] = n.  An order-preserving block scan in uint64: a ballot prefix places a candidate, a shuffle prefix sums the
+// weights within a wave, the wave totals are added in wave order and a carry runs from chunk to chunk.
+__global__ __launch_bounds__(NT) void pnp_cdf_kernel(PnPArgs a, float cap, int squared, unsigned long long* __restrict__ cum,
+                                                     int* __restrict__ ncand) {
+  __shared__ int wave_tot[NT / 64];
+  __shared__ unsigned long long wave_sum[NT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int b = blockIdx.x;
+  const int hw = a.h * a.w;
+  const float* r = a.rec + (size_t)b * hw * a.ld;
+  unsigned long long* out = cum + (size_t)b * hw;
+  int base = 0;
+  unsigned long long carry = 0;
+  for (int c0 = 0; c0 < hw; c0 += NT) {
+    const int c = c0 + tid;
+    const bool keep = c < hw && is_candidate(r + (size_t)c * a.ld, a.minc);
+    unsigned long long x = keep ? guided_weight(r[(size_t)c * a.ld + 3], a.minc, cap, squared) : 0ull;
+    const unsigned long long m = __ballot(keep);
+    const int pre = __popcll(m & ((1ull << lane) - 1ull));
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned long long y = __shfl_up(x, o);
+      if (lane >= o) x += y;
+    }
+    if (lane == 63) { wave_tot[wv] = __popcll(m); wave_sum[wv] = x; }
+    __syncthreads();
+    int off = base;
+    unsigned long long s = carry;
+    for (int k = 0; k < wv; ++k) { off += wave_tot[k]; s += wave_sum[k]; }
+    if (keep) out[off + pre] = s + x;
+    base += (wave_tot[0] + wave_tot[1]) + (wave_tot[2] + wave_tot[3]);
+    carry += (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+    __syncthreads();
+  }
+  if (tid == 0) ncand[b] = base;
+}
+
+// pnp_hyp_kernel's sibling behind kfn_pnp_ransac_guided: the same grid, candidate list, hash, P3P and outputs; the index of
+// a draw is the first i with cum[i] > floor(hash * total / 2^32), found by bisection in the frame's row of `cum`.  A
+// sibling, not a template over both: pnp_hyp_kernel is left as it was compiled before.
+__global__ __launch_bounds__(NT) void pnp_hyp_guided_kernel(PnPArgs a, const unsigned long long* __restrict__ cum,
+                                                            int* __restrict__ samples, float* __restrict__ hp,
+                                                            int* __restrict__ counts) {
+  extern __shared__ unsigned short list[];
+  __shared__ int wave_tot[NT / 64];
+  const int b = blockIdx.y;
+  const int k = blockIdx.x * NT + threadIdx.x;
+  const float* r = a.rec + (size_t)b * a.h * a.w * a.ld;
+  const unsigned long long* cf = cum + (size_t)b * a.h * a.w;
+  const int n = build_candidates(a, r, list, wave_tot);
+  if (k >= a.H) return;
+  int s[4] = {-1, -1, -1, -1};
+  int got = 0;
+  if (n >= a.min_points) {
+    const unsigned long long total = cf[n - 1];
+    const uint32_t frame = (uint32_t)(a.t0 + b);
+    const uint32_t key = a.seed ^ (frame * 0x9E3779B1u) ^ ((uint32_t)k * 0x85EBCA77u);
+    for (int draw = 0; draw < MAX_DRAWS && got < 4; ++draw) {
+      const unsigned long long hsh = lowbias32(key ^ ((uint32_t)draw * 0xC2B2AE3Du));
+      // the 96-bit product's bits 32..95 (bits 80.. are 0: hsh < 2^32, total < 2^48); target < total = cum[n - 1]
+      const unsigned long long target = (__umul64hi(hsh, total) << 32) | ((hsh * total) >> 32);
+      int lo = 0, hi = n - 1;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cf[mid] > target) hi = mid; else lo = mid + 1;
+      }
+      const int idx = lo;
+      bool dup = false;
+      for (int i = 0; i < got; ++i) dup |= s[i] == idx;
+      if (!dup) s[got++] = idx;
+    }
+  }
+  const bool sampled = got == 4;
+  const size_t hk = (size_t)b * a.H + k;
+  if (samples)
+    for (int i = 0; i < 4; ++i) samples[hk * 4 + i] = sampled ? s[i] : -1;
+  double R[9], t[3];
+  bool ok = false;
+  if (sampled) {
+    double X[4][3], px[4][2];
+    for (int i = 0; i < 4; ++i) load_point(a, r, list[s[i]], X[i], px[i]);
+    ok = p3p_hypothesis(a, X, px, R, t);
+  }
+  float* o = hp + hk * 12;
+  for (int rr = 0; rr < 3; ++rr) {
+    for (int c = 0; c < 3; ++c) o[rr * 4 + c] = ok ? (float)R[rr * 3 + c] : __builtin_nanf("");
+    o[rr * 4 + 3] = ok ? (float)t[rr] : __builtin_nanf("");
+  }
+  counts[hk] = ok ? 0 : -1;
+}
+
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Copy of the caller's descriptor (struct_size bytes, the rest 0) and the argument checks shared by the entry points.
@@ -964,4 +1069,142 @@ extern "C" int kfn_pnp_hypotheses(const kfn_pnp_desc* desc, const float* records
   if (rc != KFN_OK) return rc;
   KFN_REQUIRE(records && samples && hyp_poses && counts, "kfn_pnp_hypotheses: null argument");
   return launch_hyp_and_score(pnp_args(&d, records), samples, hyp_poses, counts, (hipStream_t)stream);
+}
+
+// ---- guided sampling: the entry points -----------------------------------------------------------------------------------
+
+namespace {
+
+// The checks on kfn_pnp_sample_desc shared by the guided entry points; `d` has passed pnp_desc_in.
+int pnp_sample_in(const kfn_pnp_sample_desc* in, const kfn_pnp_desc& d, kfn_pnp_sample_desc* s, const char* who) {
+  if (in == nullptr) return kfn::fail(KFN_ERR_ARG, "%s: null kfn_pnp_sample_desc", who);
+  if (in->struct_size < (int32_t)sizeof(kfn_pnp_sample_desc) || (in->struct_size & 3) != 0)
+    return kfn::fail(KFN_ERR_ARG, "%s: kfn_pnp_sample_desc.struct_size = %d (this library: %d bytes) -- use "
+                     "KFN_PNP_SAMPLE_DESC_INIT", who, (int)in->struct_size, (int)sizeof(kfn_pnp_sample_desc));
+  *s = *in;
+  KFN_REQUIRE(s->mode == KFN_PNP_SAMPLE_CONFIDENCE || s->mode == KFN_PNP_SAMPLE_CONFIDENCE_SQ,
+              "%s: mode = %d (KFN_PNP_SAMPLE_CONFIDENCE = 1 or KFN_PNP_SAMPLE_CONFIDENCE_SQ = 2)", who, s->mode);
+  KFN_REQUIRE(d.min_confidence >= 0.f, "%s: min_confidence = %g < 0", who, (double)d.min_confidence);
+  KFN_REQUIRE(std::isfinite(s->confidence_cap), "%s: confidence_cap = %g is not finite", who, (double)s->confidence_cap);
+  KFN_REQUIRE(s->confidence_cap > d.min_confidence, "%s: confidence_cap = %g <= min_confidence = %g", who,
+              (double)s->confidence_cap, (double)d.min_confidence);
+  KFN_REQUIRE(s->confidence_cap <= 4096.f, "%s: confidence_cap = %g > 4096", who, (double)s->confidence_cap);
+  return KFN_OK;
+}
+
+// The caller's scratch of a guided call: kfn_pnp_scratch_bytes' two arrays, then cum [B][h*w] uint64 and n [B].
+struct GuidedScratch {
+  float* hp;
+  int* counts;
+  unsigned long long* cum;
+  int* ncand;
+  size_t bytes;
+};
+
+GuidedScratch guided_scratch(const kfn_pnp_desc& d, void* scratch) {
+  const size_t bh = (size_t)d.B * d.hypotheses, cells = (size_t)d.B * d.h * d.w;
+  char* p = static_cast<char*>(scratch);
+  GuidedScratch g;
+  size_t off = 0;
+  g.hp = reinterpret_cast<float*>(p + off);                off += align256(bh * 12 * sizeof(float));
+  g.counts = reinterpret_cast<int*>(p + off);              off += align256(bh * sizeof(int32_t));
+  g.cum = reinterpret_cast<unsigned long long*>(p + off);  off += align256(cells * sizeof(uint64_t));
+  g.ncand = reinterpret_cast<int*>(p + off);               off += align256((size_t)d.B * sizeof(int32_t));
+  g.bytes = off;
+  return g;
+}
+
+int launch_guided_hyp_and_score(const PnPArgs& a, const kfn_pnp_sample_desc& s, unsigned long long* cum, int* ncand,
+                                int* samples, float* hp, int* counts, hipStream_t st) {
+  static std::atomic<uint64_t> hyp_lds_done{0};
+  const int rc = kfn::set_max_dynamic_lds((const void*)pnp_hyp_guided_kernel, 2 * MAX_CELLS, hyp_lds_done);
+  if (rc != KFN_OK) return rc;
+  hipLaunchKernelGGL(pnp_cdf_kernel, dim3((unsigned)a.B), dim3(NT), 0, st, a, s.confidence_cap,
+                     (int)(s.mode == KFN_PNP_SAMPLE_CONFIDENCE_SQ), cum, ncand);
+  KFN_LAUNCH_CHECK("pnp_cdf_kernel");
+  const unsigned hb = (unsigned)kfn::ceil_div(a.H, NT);
+  hipLaunchKernelGGL(pnp_hyp_guided_kernel, dim3(hb, (unsigned)a.B), dim3(NT), 2 * a.h * a.w, st, a,
+                     (const unsigned long long*)cum, samples, hp, counts);
+  KFN_LAUNCH_CHECK("pnp_hyp_guided_kernel");
+  hipLaunchKernelGGL(pnp_score_kernel, dim3((unsigned)kfn::ceil_div(a.h * a.w, TILE), hb, (unsigned)a.B), dim3(NT), 0, st, a,
+                     (const float*)hp, counts);
+  KFN_LAUNCH_CHECK("pnp_score_kernel");
+  return KFN_OK;
+}
+
+}  // namespace
+
+extern "C" int kfn_pnp_guided_scratch_bytes(const kfn_pnp_desc* desc, const kfn_pnp_sample_desc* sample, size_t* bytes) {
+  kfn_pnp_desc d;
+  kfn_pnp_sample_desc s;
+  int rc = pnp_desc_in(desc, &d, "kfn_pnp_guided_scratch_bytes");
+  if (rc == KFN_OK) rc = pnp_sample_in(sample, d, &s, "kfn_pnp_guided_scratch_bytes");
+  if (rc != KFN_OK) return rc;
+  KFN_REQUIRE(bytes, "kfn_pnp_guided_scratch_bytes: null bytes");
+  *bytes = guided_scratch(d, nullptr).bytes;
+  return KFN_OK;
+}
+
+extern "C" int kfn_pnp_ransac_guided(const kfn_pnp_desc* desc, const kfn_pnp_sample_desc* sample, const kfn_pnp_unc_desc* unc,
+                                     const float* records, float* poses, float* cov, float* quality, int32_t* info,
+                                     void* scratch, void* stream) {
+  const char* who = "kfn_pnp_ransac_guided";
+  kfn_pnp_desc d;
+  kfn_pnp_sample_desc s;
+  int rc = pnp_desc_in(desc, &d, who);
+  if (rc == KFN_OK) rc = pnp_sample_in(sample, d, &s, who);
+  if (rc != KFN_OK) return rc;
+  kfn_pnp_unc_desc q = KFN_PNP_UNC_DESC_INIT;
+  if (unc != nullptr) {
+    if (unc->struct_size < (int32_t)sizeof(kfn_pnp_unc_desc) || (unc->struct_size & 3) != 0)
+      return kfn::fail(KFN_ERR_ARG, "%s: kfn_pnp_unc_desc.struct_size = %d (this library: %d bytes) -- use "
+                       "KFN_PNP_UNC_DESC_INIT", who, (int)unc->struct_size, (int)sizeof(kfn_pnp_unc_desc));
+    q = *unc;
+    KFN_REQUIRE(q.weighted == 0 || q.weighted == 1, "%s: weighted = %d (0 or 1)", who, q.weighted);
+    KFN_REQUIRE(q.pixel_sigma > 0.f && std::isfinite(q.pixel_sigma), "%s: pixel_sigma = %g, must be > 0", who,
+                (double)q.pixel_sigma);
+  } else {
+    KFN_REQUIRE(cov == nullptr && quality == nullptr, "%s: cov and quality need a kfn_pnp_unc_desc", who);
+  }
+  KFN_REQUIRE(records && poses && info && scratch, "%s: null argument", who);
+  KFN_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "%s: scratch not 16-byte aligned", who);
+  const PnPArgs a = pnp_args(&d, records);
+  const GuidedScratch g = guided_scratch(d, scratch);
+  const hipStream_t st = (hipStream_t)stream;
+  static std::atomic<uint64_t> lds_done[3];
+  const void* kernel = unc == nullptr ? (const void*)pnp_refine_kernel
+                       : (q.weighted ? (const void*)pnp_refine_unc_kernel<true> : (const void*)pnp_refine_unc_kernel<false>);
+  rc = kfn::set_max_dynamic_lds(kernel, 2 * MAX_CELLS, lds_done[unc == nullptr ? 2 : q.weighted]);
+  if (rc != KFN_OK) return rc;
+  rc = launch_guided_hyp_and_score(a, s, g.cum, g.ncand, nullptr, g.hp, g.counts, st);
+  if (rc != KFN_OK) return rc;
+  const double ps2 = (double)q.pixel_sigma * (double)q.pixel_sigma;
+  if (unc == nullptr)
+    hipLaunchKernelGGL(pnp_refine_kernel, dim3((unsigned)d.B), dim3(NT), 2 * d.h * d.w, st, a, (const float*)g.hp,
+                       (const int*)g.counts, poses, info);
+  else if (q.weighted)
+    hipLaunchKernelGGL(pnp_refine_unc_kernel<true>, dim3((unsigned)d.B), dim3(NT), 2 * d.h * d.w, st, a, ps2,
+                       (const float*)g.hp, (const int*)g.counts, poses, cov, quality, info);
+  else
+    hipLaunchKernelGGL(pnp_refine_unc_kernel<false>, dim3((unsigned)d.B), dim3(NT), 2 * d.h * d.w, st, a, ps2,
+                       (const float*)g.hp, (const int*)g.counts, poses, cov, quality, info);
+  KFN_LAUNCH_CHECK(unc == nullptr ? "pnp_refine_kernel" : "pnp_refine_unc_kernel");
+  return KFN_OK;
+}
+
+extern "C" int kfn_pnp_hypotheses_guided(const kfn_pnp_desc* desc, const kfn_pnp_sample_desc* sample, const float* records,
+                                         int32_t* samples, float* hyp_poses, int32_t* counts, uint64_t* cum, int32_t* n,
+                                         void* scratch, void* stream) {
+  const char* who = "kfn_pnp_hypotheses_guided";
+  kfn_pnp_desc d;
+  kfn_pnp_sample_desc s;
+  int rc = pnp_desc_in(desc, &d, who);
+  if (rc == KFN_OK) rc = pnp_sample_in(sample, d, &s, who);
+  if (rc != KFN_OK) return rc;
+  KFN_REQUIRE(records && samples && hyp_poses && counts && scratch, "%s: null argument", who);
+  KFN_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "%s: scratch not 16-byte aligned", who);
+  KFN_REQUIRE((reinterpret_cast<uintptr_t>(cum) & 7) == 0, "%s: cum not 8-byte aligned", who);
+  const GuidedScratch g = guided_scratch(d, scratch);
+  return launch_guided_hyp_and_score(pnp_args(&d, records), s, cum ? reinterpret_cast<unsigned long long*>(cum) : g.cum,
+                                     n ? n : g.ncand, samples, hyp_poses, counts, (hipStream_t)stream);
 }

@@ -151,12 +151,38 @@ def add_pose_flags(ap):
     ap.add_argument('--pose_sequence_length', type=int, default=None,
                     help='--pose_smooth: frames per tracked sequence (the run\'s Kalman reset period where the program '
                          'has one, otherwise the whole run)')
+    ap.add_argument('--pose_sampling', choices=['uniform', 'confidence', 'confidence2'], default=None,
+                    help='--pose: draw every hypothesis\' cells uniformly (the default), or in proportion to the records\' '
+                         'confidence above the threshold (confidence) or to its square (confidence2)')
+    ap.add_argument('--pose_confidence_cap', type=float, default=None,
+                    help='--pose_sampling confidence / confidence2: confidences above it weigh as it does (1000)')
+
+
+class PoseOptions(object):
+    """The run functions' `pose` for a --pose run with guided sampling: what pose_solver needs besides the grid."""
+
+    def __init__(self, weighted, sampling, confidence_cap):
+        self.weighted, self.sampling, self.confidence_cap = bool(weighted), sampling, float(confidence_cap)
 
 
 def pose_argument(a, ap=None):
     """The parsed flags -> the run functions' `pose`; --pose_smooth implies --pose_weighted, which implies --pose (a.pose
-    is set).  With the parser `ap`, --pose_motion / --pose_sequence_length without --pose_smooth are argparse errors."""
+    is set).  With the parser `ap`, --pose_motion / --pose_sequence_length without --pose_smooth, and --pose_sampling /
+    --pose_confidence_cap without --pose or one of its stronger forms, are argparse errors.  The sampling counter is the
+    global frame index, so the sharded runs take the two sampling flags unchanged."""
+    guided = getattr(a, 'pose_sampling', None) not in (None, 'uniform')
     if ap is not None:
+        for name in ('pose_sampling', 'pose_confidence_cap'):
+            if getattr(a, name) is not None and not (a.pose or a.pose_weighted or a.pose_smooth):
+                ap.error('--%s needs --pose' % name)
+        if a.pose_confidence_cap is not None and not guided:
+            ap.error('--pose_confidence_cap needs --pose_sampling confidence or confidence2')
+        if guided:
+            try:
+                pose_solver(1, 1, sampling=a.pose_sampling,
+                            confidence_cap=1000. if a.pose_confidence_cap is None else a.pose_confidence_cap)
+            except ValueError as e:
+                ap.error('--pose_confidence_cap: %s' % e)
         for name in ('pose_motion', 'pose_sequence_length'):
             if getattr(a, name) is not None and not a.pose_smooth:
                 ap.error('--%s needs --pose_smooth' % name)
@@ -166,6 +192,9 @@ def pose_argument(a, ap=None):
         a.pose_weighted = True
     if a.pose_weighted:
         a.pose = True
+    if guided and a.pose:
+        return PoseOptions(a.pose_weighted, a.pose_sampling,
+                           1000. if a.pose_confidence_cap is None else a.pose_confidence_cap)
     return POSE_WEIGHTED if a.pose_weighted else a.pose
 
 
@@ -177,12 +206,23 @@ def refuse_sharded_smooth(world):
     return 1
 
 
-def pose_solver(h, w, weighted=False):
+def pose_solver(h, w, weighted=False, sampling='uniform', confidence_cap=1000.):
     """--pose's RANSAC-PnP solver for an h x w record grid: the KFNetDataSpec intrinsics."""
     from .KFNet.KFNet import KFNetDataSpec
     from .KFNet.pnp import PnPSolver
     spec = KFNetDataSpec()
-    return PnPSolver(h, w, spec.focal_x, spec.focal_y, spec.u, spec.v, weighted=weighted)
+    return PnPSolver(h, w, spec.focal_x, spec.focal_y, spec.u, spec.v, weighted=weighted, sampling=sampling,
+                     confidence_cap=confidence_cap)
+
+
+def solver_of(pose, h, w):
+    """The run functions' `pose` -> its solver: True or POSE_WEIGHTED or a PoseOptions (pose_solver), a PnPSolver (itself),
+    anything false (None)."""
+    if isinstance(pose, PoseOptions):
+        return pose_solver(h, w, pose.weighted, pose.sampling, pose.confidence_cap)
+    if pose is True or pose == POSE_WEIGHTED:
+        return pose_solver(h, w, pose == POSE_WEIGHTED)
+    return pose or None
 
 
 def write_smoothed_poses(poses, cov, output_folder, motion=None, sequence_length=0):
@@ -204,7 +244,7 @@ def write_poses(records, output_folder, batch=POSE_BATCH, pose=True, smooth=None
     `smooth` (with POSE_WEIGHTED): write_smoothed_poses' keyword arguments for --pose_smooth.
     Returns (poses [T,4,4], info [T,4])."""
     from .KFNet.pnp import solve_in_batches, solve_unc_in_batches, write_covariance, write_pose
-    solver = pose_solver(records.shape[1], records.shape[2], pose == POSE_WEIGHTED)
+    solver = solver_of(pose, records.shape[1], records.shape[2])
     if solver.weighted:
         poses, cov, _, info = solve_unc_in_batches(solver, records, batch)
     else:
@@ -246,8 +286,7 @@ class ChunkOutputs(object):
         self.label_paths, self.labels, self.pairs_of = label_paths, labels, pairs_of
         self.has_metrics = label_paths is not None or labels is not None
         self.dm = M.DeviceMetrics(eng) if self.has_metrics else None
-        self.solver = (pose_solver(eng.h, eng.w, pose == POSE_WEIGHTED) if pose is True or pose == POSE_WEIGHTED
-                       else (pose or None))
+        self.solver = solver_of(pose, eng.h, eng.w)
         self.plan = {}      # slot -> (first, n, global pairs) of the launch it holds
 
     def _label_grid(self, i):

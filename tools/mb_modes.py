@@ -9,8 +9,9 @@ the record launch).  Several --batch values show where an engine stops scaling w
 
 `--engines pose` times the pose stage instead: ms per PnPSolver.solve of --frames records on a 60x80 grid (20 % outliers,
 per-cell sigma 0.5-4 cm) against solve_unc unweighted and weighted, in the same JSON line under "pose_ms"; and, under
-"pose_track_ms", ms per call of PoseFilter.run and of PoseTracker.run (both models, with and without the backward pass)
-at S x T = 1 x 1000, 8 x 500 and 64 x 64, the five taken in turns.
+"pose_sampling_ms", solve with uniform sampling at 256 hypotheses against guided sampling (both weights) at 256 and at 64,
+the five taken in turns; and, under "pose_track_ms", ms per call of PoseFilter.run and of PoseTracker.run (both models,
+with and without the backward pass) at S x T = 1 x 1000, 8 x 500 and 64 x 64, the five taken in turns.
 """
 import argparse
 import json
@@ -20,11 +21,10 @@ import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 
 
-def time_pose_stage(frames, reps, warmup, h=60, w=80):
-    """ms per call of solve / solve_unc (weighted 0, 1) on `frames` synthetic 60x80 records resident on the device."""
+def _pose_records(frames, h, w):
+    """`frames` synthetic h x w records on the device: 20 % outliers, per-cell sigma 0.5-4 cm, confidence 1 / sigma."""
     import numpy as np
     import torch
-    from kfnet_amd.KFNet.pnp import PnPSolver
     rng = np.random.default_rng(0)
     rr, cc = np.meshgrid(np.arange(h), np.arange(w), indexing='ij')
     z = rng.uniform(0.5, 5.0, size=(frames, h, w))
@@ -34,7 +34,38 @@ def time_pose_stage(frames, reps, warmup, h=60, w=80):
     out = rng.random((frames, h, w)) < 0.2
     rec[..., :3][out] = rng.uniform(-5, 5, size=(int(out.sum()), 3))
     rec[..., 3] = 1.0 / sigma
-    dev = torch.from_numpy(rec.astype(np.float32)).cuda()
+    return torch.from_numpy(rec.astype(np.float32)).cuda()
+
+
+def time_pose_sampling(frames, reps, warmup, h=60, w=80, hypotheses=256):
+    """ms per call of PnPSolver.solve with uniform sampling at `hypotheses` and with each guided sampling at `hypotheses`
+    and at a quarter of it, on _pose_records; the calls take turns, each timed with its own pair of events, and the mean
+    over `reps` turns is reported."""
+    import torch
+    from kfnet_amd.KFNet.pnp import PnPSolver
+    dev = _pose_records(frames, h, w)
+    calls = {'uniform_%d' % hypotheses: PnPSolver(h, w, hypotheses=hypotheses).solve}
+    for sampling in ('confidence', 'confidence2'):
+        for H in (hypotheses, max(1, hypotheses // 4)):
+            calls['%s_%d' % (sampling, H)] = PnPSolver(h, w, hypotheses=H, sampling=sampling).solve
+    total = {name: 0.0 for name in calls}
+    for turn in range(max(warmup, 1) + reps):
+        for name, call in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            call(dev)
+            e1.record()
+            e1.synchronize()
+            if turn >= max(warmup, 1):
+                total[name] += e0.elapsed_time(e1)
+    return {name: round(v / reps, 3) for name, v in total.items()}
+
+
+def time_pose_stage(frames, reps, warmup, h=60, w=80):
+    """ms per call of solve / solve_unc (weighted 0, 1) on `frames` synthetic 60x80 records resident on the device."""
+    import torch
+    from kfnet_amd.KFNet.pnp import PnPSolver
+    dev = _pose_records(frames, h, w)
     calls = {'solve': PnPSolver(h, w).solve, 'solve_unc': PnPSolver(h, w).solve_unc,
              'solve_unc_weighted': PnPSolver(h, w, weighted=True).solve_unc}
     ms = {}
@@ -116,6 +147,7 @@ def main():
     if 'pose' in a.engines:
         a.engines.remove('pose')
         out['pose_ms'] = time_pose_stage(a.frames, a.reps, a.warmup)
+        out['pose_sampling_ms'] = time_pose_sampling(a.frames, a.reps, a.warmup)
         out['pose_track_ms'] = time_pose_track(a.reps, a.warmup)
     for name in a.engines:
         out['fps'][name] = {}
