@@ -58,7 +58,8 @@ extern "C" {
  * kfn_pose_filter (uncertainty-aware poses: weighted refinement, pose covariance, pose filter), and kfn_reproj_loss_grad
  * and kfn_augment_pixel_map (the reprojection loss of KFNet/KFNet.py:405-428 for stages 1 and 3), and kfn_pose_track,
  * kfn_pose_track_state_bytes and kfn_pose_track_scratch_bytes (the pose tracker: motion models, backward pass, carried state),
- * and kfn_pnp_guided_scratch_bytes, kfn_pnp_ransac_guided and kfn_pnp_hypotheses_guided (hypotheses drawn by confidence). */
+ * and kfn_pnp_guided_scratch_bytes, kfn_pnp_ransac_guided and kfn_pnp_hypotheses_guided (hypotheses drawn by confidence),
+ * and kfn_render_scratch_bytes and kfn_render (labels, depth maps and frames rendered from a triangle mesh). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -1049,6 +1050,58 @@ typedef struct kfn_label_moments_desc {
   double pivot[3];
 } kfn_label_moments_desc;
 int kfn_label_moments(const kfn_label_moments_desc* desc, const float* labels, double* partial, void* stream);
+
+/* ---- labels, depth maps and frames rendered from a triangle mesh (added exports; the ABI number stays 13) -------------
+ * A scene that ships a model: vertices [V,3] float (world frame), colors [V,3] uint8 or NULL (white), triangles [N,3]
+ * int32, poses [B][12] float (the rows of [R|t], camera to world, as for kfn_depth_labels) -> at the samples (r, c) =
+ * image pixel (stride c, stride r) of a H x W pinhole camera, each output optional (NULL):
+ *   labels [B,H/stride,W/stride,ld_labels] float  (world x, y, z, mask); the columns beyond 3 are not written
+ *   depth  [B,H/stride,W/stride] uint16           raw units of `scale` metres, 0 where invalid
+ *   frames [B,H/stride,W/stride,3] uint8          the vertex colours, interpolated
+ *   stats  [B,5] int32                            covered samples, triangles that passed culling, triangles clipped at the
+ *                                                 near plane, 1 if the pose was non-finite, triangles skipped for an index
+ *                                                 outside [0, V)
+ * zbuf (required, kfn_render_scratch_bytes bytes, 8-byte aligned) holds one key per sample afterwards: all ones where no
+ * triangle covers it, else bits(z) << 32 | triangle index of the nearest triangle, the lower index among equal depths.
+ * The fp32 operations, in order (kfnet_amd/csrc/kfn_render.hip repeats them, tests/render_ref.py restates
+ * them in numpy float32 and gets the same bits); every quotient is an IEEE division:
+ *   transform  vertex p to the camera frame by the inverse of the pose as R^T (p - t): d = p - t, X = (P[0] d.x + P[4] d.y)
+ *              + P[8] d.z, Y = (P[1] d.x + P[5] d.y) + P[9] d.z, Z = (P[2] d.x + P[6] d.y) + P[10] d.z.
+ *   cull/clip  a triangle with a non-finite camera coordinate or all three Z < near is culled; one crossing Z = near is
+ *              clipped to a polygon of 3 or 4 vertices (crossing of the inside vertex I and the outside O at tt = (I.z - near)
+ *              / (I.z - O.z): I + tt (O - I), z = near); vertices project to sx = (x / z) fx + u, sy = (y / z) fy + v.
+ *   depth      1/z = pa x' + pb y' + pc with n = (c1 - c0) x (c2 - c0), d = n . c0, (pa, pb, pc) = n / d: the plane of the
+ *              UNCLIPPED triangle; at a sample w = (pa rx + pb ry) + pc with the ray rx = (px - u) inv_fx, ry = (py - v)
+ *              inv_fy; w > 0; z = 1 / w.
+ *   coverage   the polygon's edges, each taken in a canonical direction (from the endpoint with the lower sx, then sy), so
+ *              two triangles sharing an edge evaluate the same numbers: e = ex (py - A.y) - ey (px - A.x), signed so that the
+ *              polygon's next vertex is on the positive side; covered iff every edge has e > 0, or e == 0 on a left or top
+ *              edge (the top-left rule: a sample on a shared edge is covered exactly once).  Both windings are rendered.
+ *   visibility 64-bit integer atomic min of the key; nothing depends on the order of arrival.
+ *   resolve    hit = z (rx, ry, 1); q = rint(z / scale), ties to even; raw_min <= q <= raw_max: depth q, label (R hit + t, 1)
+ *              evaluated as kfn_depth_labels evaluates it; else depth 0 and label (0, 0, 0, 0).  Colour: barycentric
+ *              coordinates of the hit point in the original triangle, in 3-D in the camera frame; rint, clamped to 0..255.
+ * A frame whose pose has a non-finite entry gives all-zero outputs, all-ones keys and stats[b][3] = 1.  Three launches on
+ * `stream` (clear, rasterise, resolve), no allocation and no synchronisation.  KFN_ERR_ARG, and nothing launched: a wrong
+ * struct_size, a NULL vertices, triangles, poses or zbuf, a stride other than 1 or 8, H or W not a multiple of the stride,
+ * a non-positive size, B > 65535, B (H/stride) (W/stride) >= 2^31, ld_labels < 4, near <= 0, scale <= 0, a validity window
+ * outside 0..65535. */
+typedef struct kfn_render_desc {
+  int32_t struct_size;      /* = sizeof(kfn_render_desc) */
+  int32_t B, V, N;          /* frames, vertices, triangles */
+  int32_t H, W;             /* the image */
+  int32_t stride;           /* 1 or 8 */
+  int32_t ld_labels;        /* floats per label, >= 4 */
+  int32_t raw_min, raw_max; /* the depth PNG's validity window: 1, 65534 */
+  float u, v;               /* principal point */
+  float inv_fx, inv_fy;     /* float(1 / fx), float(1 / fy) */
+  float fx, fy;
+  float near;               /* metres, > 0: 0.05 */
+  float scale;              /* metres per raw unit: float(0.001) */
+} kfn_render_desc;
+int kfn_render_scratch_bytes(const kfn_render_desc* desc, size_t* bytes);
+int kfn_render(const kfn_render_desc* desc, const float* vertices, const uint8_t* colors, const int32_t* triangles,
+               const float* poses, void* zbuf, float* labels, uint16_t* depth, uint8_t* frames, int32_t* stats, void* stream);
 
 /* ---- fine-tuning SCoordNet through the Kalman filter, OFlowNet frozen (added exports; the ABI number stays 13) ---------
  * Stage 3 of the reference under --fix_flownet (KFNet/train.py:268-298, KFNet.GetKFCoordBatch KFNet/KFNet.py:102-146;

@@ -124,6 +124,12 @@ class LabelMomentsDesc(SizedStructure):
     _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'B', 'h', 'w', 'ld', 'reserved')] + [('pivot', C.c_double * 3)])
 
 
+class RenderDesc(SizedStructure):
+    """kfn_render_desc (include/kfnet_hip.h); `struct_size` is filled in here.  kfnet_amd.render.render_descriptor derives it."""
+    _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'B', 'V', 'N', 'H', 'W', 'stride', 'ld_labels', 'raw_min', 'raw_max')] +
+                [(n, C.c_float) for n in ('u', 'v', 'inv_fx', 'inv_fy', 'fx', 'fy', 'near', 'scale')])
+
+
 class FilterLossDesc(SizedStructure):
     """kfn_filter_loss_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
     _fields_ = [('struct_size', C.c_int32), ('B', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('ld_pred', C.c_int32),
@@ -293,6 +299,9 @@ SYMBOLS = {
     'kfn_pnp_guided_scratch_bytes': (_i, [C.POINTER(PnPDesc), C.POINTER(PnPSampleDesc), C.POINTER(_sz)]),
     'kfn_pnp_ransac_guided': (_i, [C.POINTER(PnPDesc), C.POINTER(PnPSampleDesc), C.POINTER(PnPUncDesc)] + [_vp] * 7),
     'kfn_pnp_hypotheses_guided': (_i, [C.POINTER(PnPDesc), C.POINTER(PnPSampleDesc)] + [_vp] * 8),
+    # labels, depth maps and frames rendered from a triangle mesh (added exports, ABI 13)
+    'kfn_render_scratch_bytes': (_i, [C.POINTER(RenderDesc), C.POINTER(_sz)]),
+    'kfn_render': (_i, [C.POINTER(RenderDesc)] + [_vp] * 10),
 }
 
 _lib = None

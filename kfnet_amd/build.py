@@ -47,6 +47,8 @@ EXTRA = {
     'kfn_pose_track.hip': ['-ffp-contract=off'],
     # the reprojection loss: per-cell terms as the other loss launches' 
     'kfn_reproj.hip': ['-ffp-contract=off'],
+    # the mesh renderer: transform, clipping, edge functions and depth as a list of rounded fp32 operations
+    'kfn_render.hip': ['-ffp-contract=off'],
 }
 
 
