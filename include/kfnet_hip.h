@@ -59,7 +59,9 @@ extern "C" {
  * and kfn_augment_pixel_map (the reprojection loss of KFNet/KFNet.py:405-428 for stages 1 and 3), and kfn_pose_track,
  * kfn_pose_track_state_bytes and kfn_pose_track_scratch_bytes (the pose tracker: motion models, backward pass, carried state),
  * and kfn_pnp_guided_scratch_bytes, kfn_pnp_ransac_guided and kfn_pnp_hypotheses_guided (hypotheses drawn by confidence),
- * and kfn_render_scratch_bytes and kfn_render (labels, depth maps and frames rendered from a triangle mesh). */
+ * and kfn_render_scratch_bytes and kfn_render (labels, depth maps and frames rendered from a triangle mesh), and
+ * kfn_fuse_scratch_bytes, kfn_fuse_integrate, kfn_fuse_extract_count and kfn_fuse_extract (depth maps fused into a truncated
+ * signed distance volume, and the scene mesh extracted from it). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -1102,6 +1104,75 @@ typedef struct kfn_render_desc {
 int kfn_render_scratch_bytes(const kfn_render_desc* desc, size_t* bytes);
 int kfn_render(const kfn_render_desc* desc, const float* vertices, const uint8_t* colors, const int32_t* triangles,
                const float* poses, void* zbuf, float* labels, uint16_t* depth, uint8_t* frames, int32_t* stats, void* stream);
+
+/* ---- depth maps fused into a TSDF volume, and the scene mesh extracted from it (added exports; the ABI number stays 13) ---
+ * What makes the model kfn_render draws.  The volume: lattice points (ix, iy, iz), 0 <= i < n, x fastest;
+ * tsdf [nz][ny][nx] pairs of float (D, W); color, optional, [nz][ny][nx] quadruples of float (r, g, b, wc).  All zeros is the
+ * empty volume.  The world position of a lattice point is p = (ox + float(ix) voxel, oy + float(iy) voxel, oz + float(iz)
+ * voxel): one product and one sum per component.  Every operation below is one rounded fp32 operation, every quotient an IEEE
+ * division (kfnet_amd/csrc/kfn_fuse.hip repeats them, tests/fuse_ref.py restates them in numpy float32 and gets the same bits).
+ *
+ * kfn_fuse_integrate: depth [B,H,W] uint16, frames [B,H,W,3] uint8 (NULL iff color is NULL), poses [B][12] float, the rows of
+ * [R|t] camera to world.  For each voxel the frames b = 0 .. B-1 are applied in this order:
+ *   1  a non-finite entry in poses[b] skips the frame.
+ *   2  d = p - t: dx = p.x - P[3], dy = p.y - P[7], dz = p.z - P[11];  X = (P[0] dx + P[4] dy) + P[8] dz, Y = (P[1] dx + P[5] dy)
+ *      + P[9] dz, Z = (P[2] dx + P[6] dy) + P[10] dz  (kfn_render's transform).
+ *   3  Z < near or a non-finite coordinate: skip.
+ *   4  the DEPTH camera: sx = (X / Z) dfx + du, sy = (Y / Z) dfy + dv, cf = rint(sx), rf = rint(sy), ties to even; skip unless
+ *      0 <= cf <= W-1 and 0 <= rf <= H-1, compared in float before converting.
+ *   5  raw = depth[b][r][c]; skip if it lies outside [raw_min, raw_max];  dm = float(raw) scale.
+ *   6  s = dm - Z (the z-distance, not the ray length);  skip if s < -trunc (behind the surface);  f = min(s / trunc, 1).
+ *   7  D = (W D + f) / (W + 1);  then W = min(W + 1, max_weight).
+ *   8  colour, when color is given and s <= trunc: the COLOUR camera, cx = rint((X / Z) fx + u), cy = rint((Y / Z) fy + v); if
+ *      that pixel lies inside the image, each channel ch = (wc ch + float(pixel)) / (wc + 1), then wc = min(wc + 1, max_weight).
+ * One launch: a thread keeps its voxel in registers across the B frames, so the volume crosses memory once a call; a voxel
+ * that no frame touched is not written.
+ *
+ * kfn_fuse_extract_count and kfn_fuse_extract: marching tetrahedra on the lattice.
+ *   validity   a lattice point is valid iff W >= min_weight, inside iff it is valid and D < 0.
+ *   cubes      the cube at (ix, iy, iz), i < n - 1, is cut into six tetrahedra {v, v + e_a, v + e_a + e_b, v + (1,1,1)}, one per
+ *              permutation (a, b, c) of the axes in the order xyz, xzy, yxz, yzx, zxy, zyx; neighbouring cubes agree on every
+ *              face diagonal.  A tetrahedron is emitted only if all four corners are valid.
+ *   vertices   lattice point v owns the seven edges to v + (1,0,0), (0,1,0), (0,0,1), (1,1,0), (1,0,1), (0,1,1), (1,1,1), in this
+ *              order.  An owned edge carries a vertex iff its far end is in the grid, both ends are valid and exactly one is
+ *              inside.  id = (the vertex counts of all lattice points with a lower linear index) + (rank among v's carrying
+ *              edges).  With a the owner end and b the far end: t = Da / (Da - Db), pos = pa + t (pb - pa) per component;
+ *              colour min(max(rint(ca + t (cb - ca)), 0), 255) per channel when color is given and both ends have wc > 0,
+ *              otherwise 255.  A vertex that no emitted tetrahedron uses may exist (a neighbour can be invalid).
+ *   triangles  with m inside corners a tetrahedron emits one triangle for m = 1 or 3, two for m = 2 (the quad split on a fixed
+ *              diagonal), none for 0 or 4, wound so that (v1 - v0) x (v2 - v0) points from inside to outside.  index = (the
+ *              triangle counts of all cubes with a lower linear index) + (position within the cube: tetrahedra 0..5, table
+ *              order within one).  Zero-area triangles (D == 0 at a corner) are kept.
+ * kfn_fuse_extract_count writes per-point and per-cube counts and their exclusive scans into scratch (kfn_fuse_scratch_bytes
+ * bytes, 8-byte aligned) and the two 64-bit totals (vertices, triangles) into totals[2] on the device.  The scan is plain
+ * launches (block sums, a scan of the block sums, an add): no workgroup waits for another.  kfn_fuse_extract then writes
+ * vertices [V,3] float, colors [V,3] uint8 (optional) and triangles [N,3] int32 and nothing at or past the capacities it
+ * is given; the host reads the totals between the two calls and refuses totals of 2^31 or more.  Everything runs on
+ * `stream` with no allocation and no synchronisation.  KFN_ERR_ARG, and nothing launched: a wrong struct_size, a NULL tsdf,
+ * depth or poses (scratch, totals, vertices, triangles), frames and color not both NULL or both given, a non-positive
+ * dimension, nx ny nz >= 2^31, B > 65535, voxel <= 0, trunc <= 0, near <= 0, scale <= 0, max_weight < 1, min_weight < 1 (the
+ * extract calls), a validity window outside 0..65535, a capacity outside 0 .. 2^31 - 1. */
+typedef struct kfn_fuse_desc {
+  int32_t struct_size;      /* = sizeof(kfn_fuse_desc) */
+  int32_t nx, ny, nz;       /* lattice points */
+  int32_t B, H, W;          /* frames of a call and their size (integrate) */
+  int32_t raw_min, raw_max; /* the depth PNG's validity window: 1, 65534 */
+  float ox, oy, oz;         /* world position of lattice point (0, 0, 0) */
+  float voxel;              /* metres, > 0 */
+  float trunc;              /* metres, > 0: 4 voxel */
+  float near;               /* metres, > 0: 0.05 */
+  float scale;              /* metres per raw unit: float(0.001) */
+  float max_weight;         /* >= 1: the cap of W and wc */
+  float min_weight;         /* >= 1: a point counts from this W on (extract) */
+  float dfx, dfy, du, dv;   /* the depth camera */
+  float fx, fy, u, v;       /* the colour camera */
+} kfn_fuse_desc;
+int kfn_fuse_scratch_bytes(const kfn_fuse_desc* desc, size_t* bytes);
+int kfn_fuse_integrate(const kfn_fuse_desc* desc, float* tsdf, float* color, const uint16_t* depth, const uint8_t* frames,
+                       const float* poses, void* stream);
+int kfn_fuse_extract_count(const kfn_fuse_desc* desc, const float* tsdf, void* scratch, uint64_t* totals, void* stream);
+int kfn_fuse_extract(const kfn_fuse_desc* desc, const float* tsdf, const float* color, const void* scratch, float* vertices,
+                     uint8_t* colors, int32_t* triangles, int64_t cap_vertices, int64_t cap_triangles, void* stream);
 
 /* ---- fine-tuning SCoordNet through the Kalman filter, OFlowNet frozen (added exports; the ABI number stays 13) ---------
  * Stage 3 of the reference under --fix_flownet (KFNet/train.py:268-298, KFNet.GetKFCoordBatch KFNet/KFNet.py:102-146;

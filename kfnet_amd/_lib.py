@@ -130,6 +130,13 @@ class RenderDesc(SizedStructure):
                 [(n, C.c_float) for n in ('u', 'v', 'inv_fx', 'inv_fy', 'fx', 'fy', 'near', 'scale')])
 
 
+class FuseDesc(SizedStructure):
+    """kfn_fuse_desc (include/kfnet_hip.h); `struct_size` is filled in here.  kfnet_amd.fuse.fuse_descriptor derives it."""
+    _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'nx', 'ny', 'nz', 'B', 'H', 'W', 'raw_min', 'raw_max')] +
+                [(n, C.c_float) for n in ('ox', 'oy', 'oz', 'voxel', 'trunc', 'near', 'scale', 'max_weight', 'min_weight',
+                                          'dfx', 'dfy', 'du', 'dv', 'fx', 'fy', 'u', 'v')])
+
+
 class FilterLossDesc(SizedStructure):
     """kfn_filter_loss_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
     _fields_ = [('struct_size', C.c_int32), ('B', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('ld_pred', C.c_int32),
@@ -302,6 +309,11 @@ SYMBOLS = {
     # labels, depth maps and frames rendered from a triangle mesh (added exports, ABI 13)
     'kfn_render_scratch_bytes': (_i, [C.POINTER(RenderDesc), C.POINTER(_sz)]),
     'kfn_render': (_i, [C.POINTER(RenderDesc)] + [_vp] * 10),
+    # depth maps fused into a TSDF volume, and the scene mesh extracted from it (added exports, ABI 13)
+    'kfn_fuse_scratch_bytes': (_i, [C.POINTER(FuseDesc), C.POINTER(_sz)]),
+    'kfn_fuse_integrate': (_i, [C.POINTER(FuseDesc)] + [_vp] * 6),
+    'kfn_fuse_extract_count': (_i, [C.POINTER(FuseDesc), _vp, _vp, _vp, _vp]),
+    'kfn_fuse_extract': (_i, [C.POINTER(FuseDesc)] + [_vp] * 6 + [C.c_int64, C.c_int64, _vp]),
 }
 
 _lib = None

@@ -49,6 +49,8 @@ EXTRA = {
     'kfn_reproj.hip': ['-ffp-contract=off'],
     # the mesh renderer: transform, clipping, edge functions and depth as a list of rounded fp32 operations
     'kfn_render.hip': ['-ffp-contract=off'],
+    # fusion and mesh extraction: projection, the running averages and the crossings as a list of rounded fp32 operations
+    'kfn_fuse.hip': ['-ffp-contract=off'],
 }
 
 
