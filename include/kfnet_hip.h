@@ -61,7 +61,8 @@ extern "C" {
  * and kfn_pnp_guided_scratch_bytes, kfn_pnp_ransac_guided and kfn_pnp_hypotheses_guided (hypotheses drawn by confidence),
  * and kfn_render_scratch_bytes and kfn_render (labels, depth maps and frames rendered from a triangle mesh), and
  * kfn_fuse_scratch_bytes, kfn_fuse_integrate, kfn_fuse_extract_count and kfn_fuse_extract (depth maps fused into a truncated
- * signed distance volume, and the scene mesh extracted from it). */
+ * signed distance volume, and the scene mesh extracted from it), and kfn_track_scratch_bytes, kfn_track_live_maps,
+ * kfn_track_raycast, kfn_track_icp_sums, kfn_track_update and kfn_track_commit (the camera tracked against that volume). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -1173,6 +1174,136 @@ int kfn_fuse_integrate(const kfn_fuse_desc* desc, float* tsdf, float* color, con
 int kfn_fuse_extract_count(const kfn_fuse_desc* desc, const float* tsdf, void* scratch, uint64_t* totals, void* stream);
 int kfn_fuse_extract(const kfn_fuse_desc* desc, const float* tsdf, const float* color, const void* scratch, float* vertices,
                      uint8_t* colors, int32_t* triangles, int64_t cap_vertices, int64_t cap_triangles, void* stream);
+
+/* ---- the camera tracked against the TSDF volume (added exports; the ABI number stays 13) ------------------------------------
+ * The other half of KinectFusion: the model's surface by ray casting from the last committed pose, the new depth
+ * map aligned to it by projective point-to-plane ICP, the frame integrated by kfn_fuse_integrate under the pose found.  The
+ * volume is kfn_fuse's.  Every fp32 line below is one rounded operation in the order written, quotients and square roots IEEE
+ * (kfnet_amd/csrc/kfn_track.hip repeats them, tests/track_ref.py restates them in numpy float32 and gets the same bits for the
+ * maps and the per-pixel rows).  Poses are 12 numbers [R|t] row-major, camera to world: P[0..2], P[4..6], P[8..10] the rows of
+ * R, P[3], P[7], P[11] the centre.
+ *
+ * Maps.  A map is [sum_l H_l W_l] quadruples of float; level l starts at quadruple sum_{k<l} H_k W_k and is row-major.  A valid
+ * entry is (x, y, z, 1), an invalid one (0, 0, 0, 0): every launch tests the fourth component against 0.  Level 0 is H x W with
+ * the depth camera (fx_0, fy_0, cu_0, cv_0) = (dfx, dfy, du, dv);  H_l = H_{l-1} / 2, W_l = W_{l-1} / 2 (floor), fx_l = fx_{l-1}
+ * 0.5, cu_l = (cu_{l-1} - 0.5) 0.5, likewise fy, cv (pixel centres at integers: a 2 x 2 block's centre is at 2 x + 0.5).
+ *
+ * kfn_track_live_maps: depth [H,W] uint16 -> live_v, live_n (camera frame), `levels` levels.
+ *   vertex 0   raw outside [raw_min, raw_max]: invalid.  z = float(raw) scale;  X = ((float(x) - cu_0) / fx_0) z, Y likewise.
+ *   vertex l   from the block (2x, 2y), (2x+1, 2y), (2x, 2y+1), (2x+1, 2y+1) of level l-1, in this order: zmin = the least valid z;
+ *              none valid: invalid.  sum = 0, cnt = 0; each valid z with z - zmin <= pyr_dist: sum = sum + z, cnt = cnt + 1.
+ *              z' = sum / cnt;  X = ((float(x) - cu_l) / fx_l) z', Y likewise.
+ *   normal     at (x, y) with v, r = the right neighbour, d = the lower one: invalid at the last row or column, where one of the
+ *              three is invalid, or where |r.z - v.z| > jump or |d.z - v.z| > jump.  a = d - v, b = r - v per component;
+ *              c = a x b: cx = ay bz - az by, cy = az bx - ax bz, cz = ax by - ay bx;  len = sqrt((cx cx + cy cy) + cz cz);
+ *              invalid unless len > 0;  n = c / len per component.  It points towards the camera.
+ *   There is no bilateral filter.
+ *
+ * kfn_track_raycast: level `level` of model_v, model_n (world frame) from tsdf and the record's COMMITTED pose, P[k] =
+ * float(committed[k]).  One thread per pixel (x, y):
+ *   1  qx = (float(x) - cu_l) / fx_l, qy likewise;  w = R (qx, qy, 1): wx = (P[0] qx + P[1] qy) + P[2], wy = (P[4] qx + P[5] qy)
+ *      + P[6], wz = (P[8] qx + P[9] qy) + P[10].  The ray is c + t w: t is the depth along the camera's axis.
+ *   2  len = sqrt((qx qx + qy qy) + 1);  dt = (trunc 0.5) / len: a step of half the truncation distance along the ray.
+ *   3  lattice coordinates: gc = (P[3] - ox) / voxel ..., gd = wx / voxel ...;  the sample at t is g = gc + t gd per component.
+ *   4  slab test against the box 0 .. n-1:  tmin = near, tmax = far; per axis x, y, z: i = 1 / gd, a = (0 - gc) i, b = (float(n-1) -
+ *      gc) i, tmin = fmax(tmin, fmin(a, b)), tmax = fmin(tmax, fmax(a, b)) (fmin / fmax return the other operand of a NaN).
+ *      Invalid unless every P[k] is finite, tmin < tmax and kf = floor((tmax - tmin) / dt) >= 0.  Samples k = 0 .. min(kf, 8191)
+ *      at t_k = tmin + float(k) dt.
+ *   5  a sample is usable iff floor(g) lies in 0 .. n-2 on every axis -- compared in float before the conversion -- and all
+ *      eight lattice points around it have W >= min_weight.  D there is trilinear, a = g - floor(g), d_xyz the D of the point
+ *      floor(g) + (x, y, z): along x first, c00 = d000 + a.x (d100 - d000), c10 = d010 + a.x (d110 - d010), c01 = d001 + a.x
+ *      (d101 - d001), c11 = d011 + a.x (d111 - d011), then c0 = c00 + a.y (c10 - c00), c1 = c01 + a.y (c11 - c01), D = c0 +
+ *      a.z (c1 - c0).
+ *   6  walk: an unusable sample, or a usable one with D == 0 or NaN, forgets the previous one.  A usable D > 0 is remembered
+ *      (Dp, tp).  The first usable D < 0 ends the walk: the surface iff the sample before it was a remembered D > 0; otherwise
+ *      (a back face, or a way in from unknown space) the pixel is invalid.  No D < 0 up to the last sample: invalid.
+ *   7  ts = tp + (Dp / (Dp - D)) (t - tp);  vertex = (P[3] + ts wx, P[7] + ts wy, P[11] + ts wz).
+ *   8  normal: g = gc + ts gd;  the six samples at g +- (1, 0, 0), (0, 1, 0), (0, 0, 1), each by rule 5; one unusable: the normal
+ *      is invalid (the vertex stays).  c = (D(+x) - D(-x), D(+y) - D(-y), D(+z) - D(-z)), len and n as for the live normal.
+ *   No read leaves the volume for any pose: every index passes rule 5.  A non-finite pose gives an all-invalid map.
+ *
+ * kfn_track_icp_sums: level `level`, E[k] = float(estimate[k]), C[k] = float(committed[k]).  For every pixel whose live vertex v
+ * and live normal nl are valid:
+ *   1  p = E v: px = ((E[0] v.x + E[1] v.y) + E[2] v.z) + E[3], py, pz likewise with rows 1, 2.
+ *   2  into the committed camera as kfn_fuse_integrate's step 2 (d = p - c; X = (C[0] dx + C[4] dy) + C[8] dz ...); a non-finite
+ *      coordinate or Z < near: rejected.  cf = rint((X / Z) fx_l + cu_l), rf = rint((Y / Z) fy_l + cv_l); rejected unless 0 <=
+ *      cf <= W_l - 1 and 0 <= rf <= H_l - 1, compared in float.  m, n = model vertex and normal there; either invalid: rejected.
+ *   3  e = m - p;  dist = sqrt((ex ex + ey ey) + ez ez);  rejected unless dist <= dist_max.
+ *   4  rn = R_E nl (three products, two sums a row, as step 1 without the centre);  rejected unless (rn.x n.x + rn.y n.y) + rn.z
+ *      n.z >= cos_min.
+ *   5  r = (n.x ex + n.y ey) + n.z ez;  J = (py n.z - pz n.y, pz n.x - px n.z, px n.y - py n.x, n.x, n.y, n.z): the row of the
+ *      left-multiplied twist xi = (omega, upsilon), P <- exp(xi^) P.
+ *   The 29 sums, fp64: J_a J_b for a <= b row-major (21), J_a r (6), r r, the count.  Each product of two floats is exact in fp64.
+ *   Order: a thread adds its 4 pixels (index block 1024 + j 256 + thread, j ascending); a butterfly over the 64 lanes of a wave
+ *   (xor 32, 16, .. 1); the four waves as (w0 + w1) + (w2 + w3); one row of 32 doubles per workgroup in scratch
+ *   (kfn_track_scratch_bytes); a second launch adds the rows in index order into sums[32] (29 used).  No floating-point atomics,
+ *   no workgroup waits for another: two launches give the same bits.
+ *
+ * kfn_track_update (one wave; fp64): writes last_pairs = count, last_share = count / (H_l W_l), last_rms = sqrt(sum r r / count)
+ * (0 without pairs) and iterations += 1 into the record.  Then the iteration is REFUSED, the estimate left as it is, when count <
+ * min_pairs; when the Cholesky factorisation A = L L^T of the 6 x 6 system meets a pivot d_j with not d_j > pivot_floor A_jj; or
+ * when the solution of A xi = b or the new pose is not finite.  Otherwise exp(xi^) by Rodrigues' formula, theta = |omega|, K =
+ * [omega]x: R = I + A K + B K^2, t = (I + B K + C K^2) upsilon, A = sin(theta) / theta, B = 2 sin^2(theta / 2) / theta^2, C = (1 -
+ * A) / theta^2, and below theta = 1e-4 their series to theta^2;  estimate = exp(xi^) estimate;  the rotation is re-orthonormalised
+ * by Gram-Schmidt on its columns (column 0 normalised, column 1 less its part along it, normalised, column 2 their cross product);
+ * accepted += 1.
+ *
+ * kfn_track_commit (one wave), after the last iteration of a frame.  LOST when last_share < min_share, last_rms > max_rms,
+ * accepted == 0, |centre - committed centre| > max_step_m, the angle acos((tr(R_E R_C^T) - 1) / 2) > max_step_rad, or the
+ * estimate is not finite.  Tracked: committed = estimate; pose_rows[slot][0..11] = float(estimate) -- the row kfn_fuse_integrate
+ * reads.  Lost: pose_rows[slot] = NaN, so integration skips the frame by its rule 1; lost += 1; estimate = committed.  Either way
+ * row `frame` of trajectory [traj_rows][20] doubles (when frame < traj_rows) receives (pose[12] or NaN, lost 0 / 1, last_pairs,
+ * last_share, last_rms, accepted, iterations, the step in metres, the step in radians); then frame += 1, accepted = iterations = 0.
+ *
+ * Everything runs on `stream`, allocates nothing and synchronises nothing; nothing is read back between the launches of a
+ * frame.  KFN_ERR_ARG, and nothing launched: a wrong struct_size, a NULL or misaligned buffer, a non-positive image size, levels
+ * outside 1 .. 4 or a coarsest level below 2 x 2, level outside 0 .. levels-1, a non-positive focal length or near; live maps:
+ * scale <= 0, a window outside 0 .. 65535, a negative pyr_dist or jump; raycast: a lattice axis below 2 points, nx ny nz >= 2^31,
+ * voxel <= 0, trunc <= 0, far <= near, min_weight < 1; icp_sums: dist_max <= 0, cos_min outside -1 .. 1; update: min_pairs < 6,
+ * pivot_floor outside 0 .. 1; commit: slot outside 0 .. 65534, traj_rows < 1, min_share outside 0 .. 1, a non-positive limit. */
+typedef struct kfn_track_state {
+  double committed[12];     /* the last committed pose */
+  double estimate[12];      /* the current estimate */
+  double last_share, last_rms, last_pairs;   /* of the last iteration's sums */
+  int32_t frame;            /* the trajectory row the next commit writes */
+  int32_t lost;             /* frames lost so far */
+  int32_t accepted;         /* iterations accepted since the last commit */
+  int32_t iterations;       /* iterations run since the last commit */
+} kfn_track_state;
+typedef struct kfn_track_desc {
+  int32_t struct_size;      /* = sizeof(kfn_track_desc) */
+  int32_t nx, ny, nz;       /* the volume's lattice points (raycast) */
+  int32_t H, W;             /* level 0 */
+  int32_t levels;           /* 1 .. 4: 3 */
+  int32_t level;            /* the level a raycast, icp_sums or update call works on */
+  int32_t raw_min, raw_max; /* the depth PNG's validity window: 1, 65534 */
+  int32_t min_pairs;        /* >= 6: 50 */
+  int32_t traj_rows;        /* rows of the trajectory buffer (commit) */
+  int32_t slot;             /* the pose row the commit writes */
+  float ox, oy, oz;         /* world position of lattice point (0, 0, 0) */
+  float voxel, trunc;       /* metres */
+  float near, far;          /* the ray's limits in metres of depth: 0.05, 8 */
+  float scale;              /* metres per raw unit: float(0.001) */
+  float min_weight;         /* >= 1: a lattice point counts from this W on */
+  float dfx, dfy, du, dv;   /* the depth camera at level 0 */
+  float pyr_dist;           /* metres: 0.1 */
+  float jump;               /* metres: 0.1 */
+  float dist_max;           /* metres: 0.1 */
+  float cos_min;            /* float(cos(20 degrees)) */
+  float pivot_floor;        /* relative to the diagonal entry: 1e-10 */
+  float min_share;          /* 0.1 */
+  float max_rms;            /* metres: 0.04 */
+  float max_step_m;         /* metres: 0.3 */
+  float max_step_rad;       /* 0.35 */
+} kfn_track_desc;
+int kfn_track_scratch_bytes(const kfn_track_desc* desc, size_t* bytes);
+int kfn_track_live_maps(const kfn_track_desc* desc, const uint16_t* depth, float* live_v, float* live_n, void* stream);
+int kfn_track_raycast(const kfn_track_desc* desc, const float* tsdf, const kfn_track_state* state, float* model_v, float* model_n,
+                      void* stream);
+int kfn_track_icp_sums(const kfn_track_desc* desc, const float* live_v, const float* live_n, const float* model_v,
+                       const float* model_n, const kfn_track_state* state, void* scratch, double* sums, void* stream);
+int kfn_track_update(const kfn_track_desc* desc, const double* sums, kfn_track_state* state, void* stream);
+int kfn_track_commit(const kfn_track_desc* desc, kfn_track_state* state, float* pose_rows, double* trajectory, void* stream);
 
 /* ---- fine-tuning SCoordNet through the Kalman filter, OFlowNet frozen (added exports; the ABI number stays 13) ---------
  * Stage 3 of the reference under --fix_flownet (KFNet/train.py:268-298, KFNet.GetKFCoordBatch KFNet/KFNet.py:102-146;

@@ -137,6 +137,25 @@ class FuseDesc(SizedStructure):
                                           'dfx', 'dfy', 'du', 'dv', 'fx', 'fy', 'u', 'v')])
 
 
+class TrackDesc(SizedStructure):
+    """kfn_track_desc (include/kfnet_hip.h); `struct_size` is filled in here.  kfnet_amd.track.track_descriptor derives it."""
+    _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'nx', 'ny', 'nz', 'H', 'W', 'levels', 'level', 'raw_min', 'raw_max',
+                                          'min_pairs', 'traj_rows', 'slot')] +
+                [(n, C.c_float) for n in ('ox', 'oy', 'oz', 'voxel', 'trunc', 'near', 'far', 'scale', 'min_weight', 'dfx', 'dfy', 'du',
+                                          'dv', 'pyr_dist', 'jump', 'dist_max', 'cos_min', 'pivot_floor', 'min_share', 'max_rms',
+                                          'max_step_m', 'max_step_rad')])
+
+
+class TrackState(C.Structure):
+    """kfn_track_state (include/kfnet_hip.h): the record in device memory that carries the tracker from frame to frame."""
+    _fields_ = [('committed', C.c_double * 12), ('estimate', C.c_double * 12), ('last_share', C.c_double), ('last_rms', C.c_double),
+                ('last_pairs', C.c_double), ('frame', C.c_int32), ('lost', C.c_int32), ('accepted', C.c_int32),
+                ('iterations', C.c_int32)]
+
+
+TRACK_SUMS, TRACK_SUMS_LD, TRACK_TRAJ_LD, TRACK_ICP_BLOCK = 29, 32, 20, 1024
+
+
 class FilterLossDesc(SizedStructure):
     """kfn_filter_loss_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
     _fields_ = [('struct_size', C.c_int32), ('B', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('ld_pred', C.c_int32),
@@ -314,6 +333,13 @@ SYMBOLS = {
     'kfn_fuse_integrate': (_i, [C.POINTER(FuseDesc)] + [_vp] * 6),
     'kfn_fuse_extract_count': (_i, [C.POINTER(FuseDesc), _vp, _vp, _vp, _vp]),
     'kfn_fuse_extract': (_i, [C.POINTER(FuseDesc)] + [_vp] * 6 + [C.c_int64, C.c_int64, _vp]),
+    # the camera tracked against the TSDF volume: live maps, ray cast, ICP sums, solve, commit (added exports, ABI 13)
+    'kfn_track_scratch_bytes': (_i, [C.POINTER(TrackDesc), C.POINTER(_sz)]),
+    'kfn_track_live_maps': (_i, [C.POINTER(TrackDesc)] + [_vp] * 4),
+    'kfn_track_raycast': (_i, [C.POINTER(TrackDesc)] + [_vp] * 5),
+    'kfn_track_icp_sums': (_i, [C.POINTER(TrackDesc)] + [_vp] * 8),
+    'kfn_track_update': (_i, [C.POINTER(TrackDesc)] + [_vp] * 3),
+    'kfn_track_commit': (_i, [C.POINTER(TrackDesc)] + [_vp] * 4),
 }
 
 _lib = None

@@ -51,6 +51,8 @@ EXTRA = {
     'kfn_render.hip': ['-ffp-contract=off'],
     # fusion and mesh extraction: projection, the running averages and the crossings as a list of rounded fp32 operations
     'kfn_fuse.hip': ['-ffp-contract=off'],
+    # tracking against the volume: maps, ray cast and ICP rows as a list of rounded fp32 operations, the solve in unfused fp64
+    'kfn_track.hip': ['-ffp-contract=off'],
 }
 
 

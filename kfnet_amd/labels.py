@@ -269,6 +269,24 @@ def read_sequence(folder):
     return triples
 
 
+def read_frames(folder):
+    """The sorted (colour, depth) path pairs of a folder of frame-*.color.png and frame-*.depth.png, with or without pose
+    files (`kfnet_amd.track make` finds the poses).  ValueError, naming it, when there is no depth map or a member is missing."""
+    if not os.path.isdir(folder):
+        raise ValueError('%s is not a folder' % folder)
+    depth = sorted(glob.glob(os.path.join(glob.escape(folder), 'frame-*.depth.png')))
+    if not depth:
+        raise ValueError('%s holds no frame-*.depth.png' % folder)
+    pairs = [(d[:-len('depth.png')] + 'color.png', d) for d in depth]
+    for colour, _ in pairs:
+        if not os.path.exists(colour):
+            raise ValueError('%s is missing' % colour)
+    colour = glob.glob(os.path.join(glob.escape(folder), 'frame-*.color.png'))
+    if len(colour) != len(depth):
+        raise ValueError('%s holds %d colour images and %d depth maps' % (folder, len(colour), len(depth)))
+    return pairs
+
+
 def add_camera_flags(ap):
     ap.add_argument('--focal_x', type=float, default=525.)
     ap.add_argument('--focal_y', type=float, default=525.)
