@@ -62,7 +62,8 @@ extern "C" {
  * and kfn_render_scratch_bytes and kfn_render (labels, depth maps and frames rendered from a triangle mesh), and
  * kfn_fuse_scratch_bytes, kfn_fuse_integrate, kfn_fuse_extract_count and kfn_fuse_extract (depth maps fused into a truncated
  * signed distance volume, and the scene mesh extracted from it), and kfn_track_scratch_bytes, kfn_track_live_maps,
- * kfn_track_raycast, kfn_track_icp_sums, kfn_track_update and kfn_track_commit (the camera tracked against that volume). */
+ * kfn_track_raycast, kfn_track_icp_sums, kfn_track_update and kfn_track_commit (the camera tracked against that volume), and kfn_reloc_encode,
+ * kfn_reloc_search, kfn_reloc_seed and kfn_reloc_settle (a lost tracker relocalised from fern-coded keyframes). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -1304,6 +1305,99 @@ int kfn_track_icp_sums(const kfn_track_desc* desc, const float* live_v, const fl
                        const float* model_n, const kfn_track_state* state, void* scratch, double* sums, void* stream);
 int kfn_track_update(const kfn_track_desc* desc, const double* sums, kfn_track_state* state, void* stream);
 int kfn_track_commit(const kfn_track_desc* desc, kfn_track_state* state, float* pose_rows, double* trajectory, void* stream);
+
+/* ---- a lost tracker relocalised from fern-coded keyframes (added exports; the ABI number stays 13) ---------------------------
+ * Keyframe relocalisation with randomised ferns (Glocker et al., TVCG 2015): every frame is coded by `ferns`
+ * binary tests, the tracked frames whose code differs enough from those kept become keyframes with their pose, and after a loss
+ * ICP restarts from the poses of the nearest codes and its own gates decide.  Four launches a frame beside the kfn_track_* ones,
+ * in the order  live maps, ENCODE, SEARCH, SEED, ray casts, iterations, commit, SETTLE, integrate.  Each is launched every frame
+ * and decides from the records on the device what to do; the arithmetic is integer or a copy of fp64 poses
+ * (kfnet_amd/csrc/kfn_reloc.hip; tests/reloc_ref.py restates the rules below in numpy and gets the same bits).
+ *
+ * Buffers.  table [ferns][4] int32: (x, y, the bits of a float depth threshold in metres, R + 256 G + 65536 B thresholds 0 ..
+ * 255);  code [ferns] uint8, the frame's code;  codes [capacity][ferns] uint8 and key_poses [capacity][12] double, the keyframes;
+ * dist [capacity] int32, scratch of the search;  reloc_rows [rows][8] int32;  live_v, pose_rows, trajectory and the
+ * kfn_track_state as in the kfn_track_* block.  Level sizes as there: H_l = H_{l-1} / 2, W_l = W_{l-1} / 2 (floor).
+ *
+ * kfn_reloc_encode: one byte per fern f from live_v at level reloc_level and, iff colour = 1, the staged frame [H,W,3] uint8.
+ *   range    unless 0 <= x <= W_l - 1 and 0 <= y <= H_l - 1 the byte is 0 and nothing is read: the kernel tests it before any use.
+ *   bit 0    v = the live vertex at (x, y) of the level: 1 iff v is valid (fourth component != 0) and v.z > threshold (float).
+ *   bits 1-3 (colour = 1) for channel c = R, G, B: s = the int32 sum of the channel over the full-resolution pixels (x 2^l + i,
+ *            y 2^l + j), 0 <= i, j < 2^l, l = reloc_level (they lie inside the frame because the sizes halve by floor); bit
+ *            1 + c is 1 iff s > threshold_c 4^l.  With colour = 0 bits 1-3 are 0.
+ *
+ * kfn_reloc_search: n = min(max(state.n, 0), capacity).  For every keyframe i < n, d_i = the number of ferns f with code[f] !=
+ * codes[i][f] (one wave per slot into dist; slots >= n exit, nothing is read beyond).  Then one workgroup writes into the state
+ * cand_d[r], cand_index[r], r = 0 .. 3: the r-th least pair (d_i, i), ascending in d and, for equal d, in i, for r < min(tries,
+ * n); (ferns + 1, -1) for every other r.  candidates = min(tries, n); min_d = cand_d[0] (ferns + 1 when n = 0).
+ *
+ * kfn_reloc_seed (one wave), before the ray casts.  n as above, c = min(max(state.candidates, 0), min(tries, n)).  It acts only
+ * when streak > 0, c > 0 and i = cand_index[(streak - 1) mod c] lies in 0 .. n-1:  the tracker's committed = estimate =
+ * key_poses[i];  seeded = 1;  seed_key = i.  Otherwise it writes nothing.
+ *
+ * kfn_reloc_settle (one wave), after kfn_track_commit and before kfn_fuse_integrate.  row = track.frame - 1, the trajectory row
+ * the commit just wrote; TRACKED iff 0 <= row < traj_rows and trajectory[row][12] == 0;  n, c as above, streak = max(streak, 0),
+ * SEEDED iff state.seeded == 1.  With first = 1 (the settle of frame 0, no commit before it) the frame is TRACKED and not
+ * SEEDED, and the trajectory is not read.
+ *   tracked, not seeded   streak = 0.  Harvest iff (n == 0 or min_d > harvest) and n < capacity:  codes[n] = code, key_poses[n]
+ *                         = the tracker's committed pose, n += 1.
+ *   tracked and seeded    verified iff last_share >= reloc_min_share and last_rms <= reloc_max_rms (as doubles).  Verified:
+ *                         streak = 0, recovered += 1, no harvest.  Not verified: DEMOTED -- pose_rows[slot] = NaN (integration
+ *                         skips the frame), trajectory[row][0..11] = NaN and [12] = 1, track.lost += 1, and the frame goes on
+ *                         as a lost one.
+ *   lost (or demoted)     if streak == 0 and not seeded: anchor = the tracker's committed pose, the last one truly tracked.
+ *                         streak += 1.  If seeded: the tracker's committed = estimate = anchor.
+ *   either way            seeded = 0, and reloc_rows[row] (when 0 <= row < rows) = (min_d, cand_index[0] or -1 when c == 0, seed_key
+ *                         or -1 when not seeded, the keyframe added or -1, streak after, c, demoted 0 / 1, 0).
+ *   So while streak > 0 the committed pose is the anchor on entry to the seed launch, and a keyframe's pose never outlives the
+ *   frame it was tried on unless ICP's gates and the verification accepted it.
+ *
+ * Every index taken from a record is compared against its bound before use (n against capacity, a keyframe index against n, a
+ * candidate against c, a row against rows and traj_rows): a record of garbage cannot cause an access out of range.  Everything
+ * runs on `stream`, allocates nothing and synchronises nothing; no floating-point atomics, no workgroup waits for another: two
+ * launches give the same bits.  KFN_ERR_ARG, and nothing launched: a wrong struct_size, a NULL or misaligned buffer (table,
+ * live_v 16 bytes; state, track, key_poses, trajectory 8; dist, pose_rows, reloc_rows 4), a non-positive image size, levels
+ * outside 1 .. 4 or a coarsest level below 2 x 2, reloc_level outside 0 .. levels-1, ferns outside 1 .. 4096, capacity outside
+ * 1 .. 65536, tries outside 1 .. 4, rows < 1, harvest outside 0 .. ferns, colour not 0 / 1; encode: colour = 1 without a frame
+ * or a frame with colour = 0; settle: slot outside 0 .. 65534, traj_rows < 1, first not 0 / 1, reloc_min_share outside 0 .. 1,
+ * reloc_max_rms not positive and finite. */
+typedef struct kfn_reloc_state {
+  double anchor[12];        /* the last truly tracked pose, captured when a streak begins */
+  int32_t n;                /* keyframes stored */
+  int32_t streak;           /* lost frames in a row */
+  int32_t seeded;           /* 1 between a seed that acted and the settle of its frame */
+  int32_t seed_key;         /* the keyframe the last seed took */
+  int32_t candidates;       /* min(tries, n) of the last search */
+  int32_t min_d;            /* the least distance of the last search, ferns + 1 without keyframes */
+  int32_t recovered;        /* seeded frames verified so far */
+  int32_t reserved;         /* 0 */
+  int32_t cand_d[4];        /* the nearest keyframes' distances, ascending */
+  int32_t cand_index[4];    /* and their indices, -1 where there is none */
+} kfn_reloc_state;
+typedef struct kfn_reloc_desc {
+  int32_t struct_size;      /* = sizeof(kfn_reloc_desc) */
+  int32_t H, W;             /* level 0, as kfn_track_desc's */
+  int32_t levels;           /* of the live maps, as kfn_track_desc's */
+  int32_t reloc_level;      /* the level the ferns sit on: levels - 1 */
+  int32_t ferns;            /* 1 .. 4096: 500 */
+  int32_t capacity;         /* keyframe slots, 1 .. 65536: 1024 */
+  int32_t tries;            /* 1 .. 4: 3 */
+  int32_t harvest;          /* 0 .. ferns: floor(0.2 ferns) */
+  int32_t rows;             /* rows of reloc_rows */
+  int32_t traj_rows;        /* rows of the trajectory buffer (settle) */
+  int32_t slot;             /* the pose row a demotion overwrites (settle) */
+  int32_t first;            /* 1 for the settle of frame 0 */
+  int32_t colour;           /* 1: the table's colour thresholds are used and a frame is given */
+  float reloc_min_share;    /* the verification gates: the tracker's min_share and max_rms */
+  float reloc_max_rms;
+} kfn_reloc_desc;
+int kfn_reloc_encode(const kfn_reloc_desc* desc, const int32_t* table, const float* live_v, const uint8_t* frame, uint8_t* code,
+                     void* stream);
+int kfn_reloc_search(const kfn_reloc_desc* desc, const uint8_t* code, const uint8_t* codes, kfn_reloc_state* state, int32_t* dist,
+                     void* stream);
+int kfn_reloc_seed(const kfn_reloc_desc* desc, kfn_reloc_state* state, kfn_track_state* track, const double* key_poses, void* stream);
+int kfn_reloc_settle(const kfn_reloc_desc* desc, kfn_reloc_state* state, kfn_track_state* track, const uint8_t* code, uint8_t* codes,
+                     double* key_poses, float* pose_rows, double* trajectory, int32_t* reloc_rows, void* stream);
 
 /* ---- fine-tuning SCoordNet through the Kalman filter, OFlowNet frozen (added exports; the ABI number stays 13) ---------
  * Stage 3 of the reference under --fix_flownet (KFNet/train.py:268-298, KFNet.GetKFCoordBatch KFNet/KFNet.py:102-146;

@@ -156,6 +156,23 @@ class TrackState(C.Structure):
 TRACK_SUMS, TRACK_SUMS_LD, TRACK_TRAJ_LD, TRACK_ICP_BLOCK = 29, 32, 20, 1024
 
 
+class RelocDesc(SizedStructure):
+    """kfn_reloc_desc (include/kfnet_hip.h); `struct_size` is filled in here.  kfnet_amd.track.Relocaliser derives it."""
+    _fields_ = ([(n, C.c_int32) for n in ('struct_size', 'H', 'W', 'levels', 'reloc_level', 'ferns', 'capacity', 'tries', 'harvest',
+                                          'rows', 'traj_rows', 'slot', 'first', 'colour')] +
+                [(n, C.c_float) for n in ('reloc_min_share', 'reloc_max_rms')])
+
+
+class RelocState(C.Structure):
+    """kfn_reloc_state (include/kfnet_hip.h): the record in device memory that carries the relocaliser from frame to frame."""
+    _fields_ = ([('anchor', C.c_double * 12)] +
+                [(n, C.c_int32) for n in ('n', 'streak', 'seeded', 'seed_key', 'candidates', 'min_d', 'recovered', 'reserved')] +
+                [('cand_d', C.c_int32 * 4), ('cand_index', C.c_int32 * 4)])
+
+
+RELOC_ROW_LD, RELOC_MAX_FERNS, RELOC_MAX_CAPACITY, RELOC_MAX_TRIES = 8, 4096, 65536, 4
+
+
 class FilterLossDesc(SizedStructure):
     """kfn_filter_loss_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
     _fields_ = [('struct_size', C.c_int32), ('B', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('ld_pred', C.c_int32),
@@ -340,6 +357,11 @@ SYMBOLS = {
     'kfn_track_icp_sums': (_i, [C.POINTER(TrackDesc)] + [_vp] * 8),
     'kfn_track_update': (_i, [C.POINTER(TrackDesc)] + [_vp] * 3),
     'kfn_track_commit': (_i, [C.POINTER(TrackDesc)] + [_vp] * 4),
+    # a lost tracker relocalised from fern-coded keyframes: encode, search, seed, settle (added exports, ABI 13)
+    'kfn_reloc_encode': (_i, [C.POINTER(RelocDesc)] + [_vp] * 5),
+    'kfn_reloc_search': (_i, [C.POINTER(RelocDesc)] + [_vp] * 5),
+    'kfn_reloc_seed': (_i, [C.POINTER(RelocDesc)] + [_vp] * 4),
+    'kfn_reloc_settle': (_i, [C.POINTER(RelocDesc)] + [_vp] * 9),
 }
 
 _lib = None

@@ -53,6 +53,8 @@ EXTRA = {
     'kfn_fuse.hip': ['-ffp-contract=off'],
     # tracking against the volume: maps, ray cast and ICP rows as a list of rounded fp32 operations, the solve in unfused fp64
     'kfn_track.hip': ['-ffp-contract=off'],
+    # relocalisation from fern-coded keyframes: integer tests and copies of fp64 poses, built like the tracker it sits in
+    'kfn_reloc.hip': ['-ffp-contract=off'],
 }
 
 

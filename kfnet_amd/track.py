@@ -11,14 +11,20 @@ found -- KinectFusion's loop, every step a launch of csrc/kfn_track.hip or kfn_f
                                    [--depth_focal_x F --depth_focal_y F --depth_u U --depth_v V]
                                    [--height 480 --width 640] [--gpu 0]
                                    [--dist_max 0.1] [--angle_max 20] [--levels 3] [--iterations 10 5 4]
+                                   [--reloc [--reloc_ferns 500 --reloc_keyframes 1024 --reloc_harvest 0.2 --reloc_tries 3
+                                             --reloc_seed 1 --reloc_min_share S --reloc_max_rms M]]
 
 writes frame-<i>.pose.txt for every tracked frame, image_list.txt, depth_list.txt and pose_list.txt naming the tracked frames
 (so O is a --sequence for `fuse make`, `labels make` and `render make`), track_report.txt and, with --mesh, the volume's mesh.
+With --reloc a lost tracker is relocalised from fern-coded keyframes (csrc/kfn_reloc.hip): track_report.txt names a recovered
+frame `relocalised`, reloc_report.txt lists every frame's nearest keyframe, and the summary line counts keyframes and recoveries.
 
     trk = Tracker(volume, levels=3, iterations=(10, 5, 4))     iterations finest to coarsest; the coarsest level runs first
     trk.start(first_pose, depth_u16, frame_u8)                 the committed pose, and frame 0 integrated under it
     trk.push(depth_u16, frame_u8)                              one frame: maps, ray casts, 19 iterations, commit, integrate
     poses, lost, diagnostics = trk.trajectory()                the one read
+    trk = Tracker(volume, reloc=True)                          or reloc=dict(ferns=500, ...): Relocaliser's keywords
+    rows, keyframes, key_poses = trk.relocalisation()          the relocaliser's one read
 
 There is no fallback: a missing entry point or an unsupported shape raises.
 """
@@ -93,14 +99,119 @@ def pose_record(committed, estimate=None, frame=1):
     return st
 
 
+def fern_table(seed, ferns, level_size, colour=False, depth_lo=0.5, depth_hi=4.0):
+    """The fern table of kfn_reloc_encode, int32 [ferns, 4], from a seeded numpy Generator: a position (x, y) on the level of
+    `level_size` = (H_l, W_l), the bits of a float32 depth threshold uniform in [depth_lo, depth_hi] metres, and -- with
+    `colour` -- three uint8 thresholds packed R + 256 G + 65536 B (0 without)."""
+    Hl, Wl = level_size
+    if not 1 <= ferns <= _lib.RELOC_MAX_FERNS:
+        raise ValueError('ferns must lie in 1 .. %d, got %r' % (_lib.RELOC_MAX_FERNS, ferns))
+    if Hl < 1 or Wl < 1:
+        raise ValueError('the level must hold a pixel, got %dx%d' % (Hl, Wl))
+    if not 0.0 < depth_lo <= depth_hi < float('inf'):
+        raise ValueError('the depth thresholds need 0 < depth_lo <= depth_hi, got %r .. %r' % (depth_lo, depth_hi))
+    rng = np.random.default_rng([int(seed), 0xfe525])
+    table = np.zeros((ferns, 4), dtype=np.int32)
+    table[:, 0] = rng.integers(0, Wl, size=ferns)
+    table[:, 1] = rng.integers(0, Hl, size=ferns)
+    table[:, 2] = rng.uniform(depth_lo, depth_hi, size=ferns).astype(np.float32).view(np.int32)
+    rgb = rng.integers(0, 256, size=(ferns, 3))
+    if colour:
+        table[:, 3] = rgb[:, 0] + 256 * rgb[:, 1] + 65536 * rgb[:, 2]
+    return table
+
+
+class Relocaliser(object):
+    """The kfn_reloc_* launches with their buffers, attached to `tracker` (before its start()): the fern `table` [ferns, 4] int32,
+    `code` [ferns] and `codes` [keyframes, ferns] uint8, `key_poses` [keyframes, 12] fp64, `dist` [keyframes] int32, `record`
+    (kfn_reloc_state) and `rows` [max_frames, 8] int32 are device tensors.  `level` None is the tracker's coarsest; `min_share`
+    and `max_rms` None are the tracker's own gates, so that verification adds no strictness."""
+
+    def __init__(self, tracker, ferns=500, keyframes=1024, harvest_share=0.2, tries=3, seed=1, level=None, depth_range=(0.5, 4.0),
+                 min_share=None, max_rms=None):
+        torch = tracker.torch
+        if tracker.first is not None:
+            raise ValueError('the relocaliser must be attached before start(): frame 0 is keyframe 0')
+        level = tracker.levels - 1 if level is None else level
+        min_share = tracker.desc[0].min_share if min_share is None else min_share
+        max_rms = tracker.desc[0].max_rms if max_rms is None else max_rms
+        if not 1 <= ferns <= _lib.RELOC_MAX_FERNS:
+            raise ValueError('ferns must lie in 1 .. %d, got %r' % (_lib.RELOC_MAX_FERNS, ferns))
+        if not 1 <= keyframes <= _lib.RELOC_MAX_CAPACITY:
+            raise ValueError('keyframes must lie in 1 .. %d, got %r' % (_lib.RELOC_MAX_CAPACITY, keyframes))
+        if not 1 <= tries <= _lib.RELOC_MAX_TRIES:
+            raise ValueError('tries must lie in 1 .. %d, got %r' % (_lib.RELOC_MAX_TRIES, tries))
+        if not 0 <= level < tracker.levels:
+            raise ValueError('level %r outside 0 .. %d' % (level, tracker.levels - 1))
+        if not 0.0 <= harvest_share <= 1.0:
+            raise ValueError('harvest_share must lie in 0 .. 1, got %r' % (harvest_share,))
+        if not 0.0 <= min_share <= 1.0:
+            raise ValueError('min_share must lie in 0 .. 1, got %r' % (min_share,))
+        if not 0.0 < max_rms < float('inf'):
+            raise ValueError('max_rms must be positive and finite, got %r' % (max_rms,))
+        self.trk, self.lib, self.torch, self.device = tracker, tracker.lib, torch, tracker.device
+        self.ferns, self.capacity, self.tries, self.level = int(ferns), int(keyframes), int(tries), int(level)
+        self.harvest = int(math.floor(harvest_share * ferns))
+        self.colour = tracker.vol.color_volume is not None
+        Hl, Wl, _ = tracker.sizes[self.level]
+        self.table_host = fern_table(seed, self.ferns, (Hl, Wl), self.colour, depth_range[0], depth_range[1])
+        B, H, W = tracker.vol.shape
+        self.desc = _lib.RelocDesc(H=H, W=W, levels=tracker.levels, reloc_level=self.level, ferns=self.ferns, capacity=self.capacity,
+                                   tries=self.tries, harvest=self.harvest, rows=tracker.max_frames, traj_rows=tracker.max_frames, slot=0,
+                                   first=0, colour=int(self.colour))
+        self.desc.reloc_min_share, self.desc.reloc_max_rms = min_share, max_rms
+        self.desc_first = _lib.RelocDesc.from_buffer_copy(bytes(self.desc))
+        self.desc_first.first = 1
+        with torch.cuda.device(self.device):
+            self.table = torch.from_numpy(self.table_host).to(self.device)
+            self.code = torch.zeros(self.ferns, dtype=torch.uint8, device=self.device)
+            self.codes = torch.zeros((self.capacity, self.ferns), dtype=torch.uint8, device=self.device)
+            self.key_poses = torch.zeros((self.capacity, 12), dtype=torch.float64, device=self.device)
+            self.dist = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
+            self.record = torch.zeros(C.sizeof(_lib.RelocState) // 8, dtype=torch.int64, device=self.device)
+            self.rows = torch.zeros((tracker.max_frames, _lib.RELOC_ROW_LD), dtype=torch.int32, device=self.device)
+        tracker.reloc = self
+
+    def set_state(self, state):
+        """Writes a _lib.RelocState into the record."""
+        host = self.torch.frombuffer(bytearray(bytes(state)), dtype=self.torch.int64)
+        self.record.copy_(host, non_blocking=False)
+
+    def state(self):
+        """The record read back (a wait): _lib.RelocState."""
+        return _lib.RelocState.from_buffer_copy(self.record.cpu().numpy().tobytes())
+
+    def encode(self):
+        vol = self.trk.vol
+        _lib.check(self.lib.kfn_reloc_encode(C.byref(self.desc), self.table.data_ptr(), self.trk.live_v.data_ptr(),
+                                             vol.frames.data_ptr() if self.colour else None, self.code.data_ptr(),
+                                             current_stream(self.device)), 'kfn_reloc_encode')
+
+    def search(self):
+        _lib.check(self.lib.kfn_reloc_search(C.byref(self.desc), self.code.data_ptr(), self.codes.data_ptr(), self.record.data_ptr(),
+                                             self.dist.data_ptr(), current_stream(self.device)), 'kfn_reloc_search')
+
+    def seed(self):
+        _lib.check(self.lib.kfn_reloc_seed(C.byref(self.desc), self.record.data_ptr(), self.trk.record.data_ptr(),
+                                           self.key_poses.data_ptr(), current_stream(self.device)), 'kfn_reloc_seed')
+
+    def settle(self, first=False):
+        trk = self.trk
+        _lib.check(self.lib.kfn_reloc_settle(C.byref(self.desc_first if first else self.desc), self.record.data_ptr(),
+                                             trk.record.data_ptr(), self.code.data_ptr(), self.codes.data_ptr(),
+                                             self.key_poses.data_ptr(), trk.vol.poses.data_ptr(), trk.trajectory_rows.data_ptr(),
+                                             self.rows.data_ptr(), current_stream(self.device)), 'kfn_reloc_settle')
+
+
 class Tracker(object):
     """The kfn_track_* launches with their buffers around a `fuse.Volume` (its slot 0 carries the frame).  `live_v`, `live_n`,
     `model_v`, `model_n` [sum H_l W_l, 4], `sums` [32] fp64, `record` (kfn_track_state) and `trajectory_rows` [max_frames, 20]
-    are device tensors."""
+    are device tensors.  `reloc` = True, or a dict of Relocaliser's keywords, attaches a Relocaliser; None leaves every launch
+    as it is without one."""
 
     def __init__(self, volume, levels=3, iterations=(10, 5, 4), far=8.0, min_weight=1.0, pyr_dist=0.1, jump=0.1, dist_max=0.1,
                  angle_max=20.0, min_pairs=50, pivot_floor=1e-10, min_share=0.1, max_rms=0.04, max_step_m=0.3, max_step_rad=0.35,
-                 max_frames=4096):
+                 max_frames=4096, reloc=None):
         torch = volume.torch
         B, H, W = volume.shape
         self.iterations = check_levels((H, W), levels, iterations)
@@ -135,6 +246,9 @@ class Tracker(object):
             self.record = torch.zeros(C.sizeof(_lib.TrackState) // 8, dtype=torch.int64, device=self.device)
             self.trajectory_rows = torch.zeros((max_frames, _lib.TRACK_TRAJ_LD), dtype=torch.float64, device=self.device)
         self.first, self.pushed = None, 0
+        self.reloc = None
+        if reloc is not None and reloc is not False:
+            Relocaliser(self, **(dict() if reloc is True else dict(reloc)))
 
     # -- the record -----------------------------------------------------------------------------------------------------------
     def set_state(self, committed, estimate=None, frame=1):
@@ -212,6 +326,11 @@ class Tracker(object):
             self.set_state(first)
             self._stage(depth_u16, frame_u8)
             self.vol.poses[:1].copy_(self.torch.from_numpy(pose_rows(first[None])), non_blocking=True)
+            if self.reloc is not None:                                   # frame 0 becomes keyframe 0
+                self.live_maps()
+                self.reloc.encode()
+                self.reloc.search()
+                self.reloc.settle(first=True)
             self.integrate()
         self.first, self.pushed = first.copy(), 0
 
@@ -224,6 +343,10 @@ class Tracker(object):
         with self.torch.cuda.device(self.device):
             self._stage(depth_u16, frame_u8)
             self.live_maps()
+            if self.reloc is not None:
+                self.reloc.encode()
+                self.reloc.search()
+                self.reloc.seed()
             for l in range(self.levels):
                 self.raycast(l)
             for l in range(self.levels - 1, -1, -1):
@@ -231,6 +354,8 @@ class Tracker(object):
                     self.icp_sums(l)
                     self.update(l)
             self.commit()
+            if self.reloc is not None:
+                self.reloc.settle()
             self.integrate()
         self.pushed += 1
 
@@ -247,6 +372,28 @@ class Tracker(object):
         diag[0] = 0.0
         return poses, diag[:, 0] != 0, diag
 
+    def relocalisation(self):
+        """The relocaliser's one read: (rows int32 [N, 8] in the order of RELOC_ROW, the keyframe count, the keyframes' poses
+        [count, 4, 4] fp64)."""
+        if self.reloc is None:
+            raise ValueError('relocalisation() needs a tracker made with reloc')
+        n = self.pushed + 1
+        rc = self.reloc
+        packed = self.torch.cat([rc.record.view(self.torch.uint8), rc.rows[:n].reshape(-1).view(self.torch.uint8),
+                                 rc.key_poses.reshape(-1).view(self.torch.uint8)]).cpu().numpy()
+        size, rows_bytes = C.sizeof(_lib.RelocState), n * _lib.RELOC_ROW_LD * 4
+        st = _lib.RelocState.from_buffer_copy(packed[:size].tobytes())
+        count = min(max(st.n, 0), rc.capacity)
+        rows = packed[size:size + rows_bytes].copy().view(np.int32).reshape(n, _lib.RELOC_ROW_LD)
+        rows12 = packed[size + rows_bytes:].copy().view(np.float64).reshape(rc.capacity, 12)[:count]
+        poses = np.zeros((count, 4, 4), dtype=np.float64)
+        poses[:, 3, 3] = 1.0
+        poses[:, :3, :] = rows12.reshape(count, 3, 4)
+        return rows, count, poses
+
+
+RELOC_ROW = ('min_d', 'nearest', 'seed_key', 'added', 'streak', 'candidates', 'demoted', 'reserved')
+
 
 def box_in_front(first_pose, extent):
     """The default box: an axis-aligned cube of `extent` metres whose centre lies extent / 2 in front of the first camera."""
@@ -255,16 +402,28 @@ def box_in_front(first_pose, extent):
     return centre - 0.5 * extent, centre + 0.5 * extent
 
 
-def write_report(path, names, lost, diag):
+def write_report(path, names, lost, diag, rows=None):
+    """track_report.txt; with the relocaliser's `rows` a tracked frame that was seeded from a keyframe is named `relocalised`."""
     with open(path, 'w') as f:
         f.write('# frame state ' + ' '.join(DIAGNOSTICS[1:]) + '\n')
         for k, name in enumerate(names):
-            f.write('%s %s %d %.6f %.6e %d %d %.6e %.6e\n' % ((name, 'lost' if lost[k] else 'tracked', int(diag[k, 1]), diag[k, 2], diag[k, 3],
+            state = 'lost' if lost[k] else ('relocalised' if rows is not None and rows[k, 2] >= 0 else 'tracked')
+            f.write('%s %s %d %.6f %.6e %d %d %.6e %.6e\n' % ((name, state, int(diag[k, 1]), diag[k, 2], diag[k, 3],
                                                                int(diag[k, 4]), int(diag[k, 5]), diag[k, 6], diag[k, 7])))
 
 
-def write_outputs(folder, pairs, poses, lost, diag):
-    """The pose files of the tracked frames, the three lists naming them, and track_report.txt."""
+def write_reloc_report(path, names, rows):
+    """reloc_report.txt: per frame the nearest keyframe and its distance in ferns, the keyframe ICP was seeded from, the keyframe
+    the frame became, and the lost frames in a row after it (-1: none)."""
+    with open(path, 'w') as f:
+        f.write('# frame nearest distance seeded_key keyframe_added streak\n')
+        for k, name in enumerate(names):
+            f.write('%s %d %d %d %d %d\n' % (name, rows[k, 1], rows[k, 0], rows[k, 2], rows[k, 3], rows[k, 4]))
+
+
+def write_outputs(folder, pairs, poses, lost, diag, reloc_rows=None):
+    """The pose files of the tracked frames, the three lists naming them, and track_report.txt; with `reloc_rows` (the rows of
+    Tracker.relocalisation()) also reloc_report.txt."""
     from .KFNet.pnp import write_pose
     os.makedirs(folder, exist_ok=True)
     cols = ([], [], [])
@@ -280,7 +439,10 @@ def write_outputs(folder, pairs, poses, lost, diag):
     for name, col in zip(('image_list.txt', 'depth_list.txt', 'pose_list.txt'), cols):
         with open(os.path.join(folder, name), 'w') as f:
             f.write(''.join(x + '\n' for x in col))
-    write_report(os.path.join(folder, 'track_report.txt'), [os.path.basename(p[1]) for p in pairs], lost, diag)
+    names = [os.path.basename(p[1]) for p in pairs]
+    write_report(os.path.join(folder, 'track_report.txt'), names, lost, diag, reloc_rows)
+    if reloc_rows is not None:
+        write_reloc_report(os.path.join(folder, 'reloc_report.txt'), names, reloc_rows)
 
 
 # ---- the program --------------------------------------------------------------------------------------------------------
@@ -307,6 +469,15 @@ def build_parser():
     mk.add_argument('--angle_max', type=float, default=20.0, help='degrees between a pair\'s normals at most')
     mk.add_argument('--levels', type=int, default=3)
     mk.add_argument('--iterations', type=int, nargs='+', default=None, help='per level, finest first (10 5 4)')
+    mk.add_argument('--reloc', action='store_true', help='relocalise after a loss from fern-coded keyframes; writes reloc_report.txt')
+    mk.add_argument('--reloc_ferns', type=int, default=500, help='binary tests a frame\'s code holds (1 .. 4096)')
+    mk.add_argument('--reloc_keyframes', type=int, default=1024, help='keyframes kept at most (1 .. 65536)')
+    mk.add_argument('--reloc_harvest', type=float, default=0.2, help='a tracked frame becomes a keyframe when more than this share of '
+                    'its ferns differs from every keyframe\'s')
+    mk.add_argument('--reloc_tries', type=int, default=3, help='nearest keyframes tried in turn after a loss (1 .. 4)')
+    mk.add_argument('--reloc_seed', type=int, default=1, help='seed of the fern table')
+    mk.add_argument('--reloc_min_share', type=float, default=None, help='share of pixels a relocalised frame must pair (the tracker\'s 0.1)')
+    mk.add_argument('--reloc_max_rms', type=float, default=None, help='residual in metres a relocalised frame may leave (the tracker\'s 0.04)')
     return ap
 
 
@@ -356,7 +527,11 @@ def make(a):
     device = 'cuda:%d' % a.gpu
     try:
         vol = Volume(dims, origin, a.voxel, trunc, camera, size, 1, not a.no_color, device=device)
-        trk = Tracker(vol, a.levels, iterations, dist_max=a.dist_max, angle_max=a.angle_max, max_frames=max(len(pairs), 2))
+        reloc = None
+        if a.reloc:
+            reloc = dict(ferns=a.reloc_ferns, keyframes=a.reloc_keyframes, harvest_share=a.reloc_harvest, tries=a.reloc_tries,
+                         seed=a.reloc_seed, min_share=a.reloc_min_share, max_rms=a.reloc_max_rms)
+        trk = Tracker(vol, a.levels, iterations, dist_max=a.dist_max, angle_max=a.angle_max, max_frames=max(len(pairs), 2), reloc=reloc)
         for k, (colour, depth) in enumerate(pairs):
             dp = load_depth([depth], size)[0]
             fr = None if a.no_color else load_images([colour], size)[0]
@@ -365,7 +540,8 @@ def make(a):
             else:
                 trk.push(dp, fr)
         poses, lost, diag = trk.trajectory()
-        write_outputs(a.output_folder, pairs, poses, lost, diag)
+        rows, keyframes, _ = trk.relocalisation() if a.reloc else (None, 0, None)
+        write_outputs(a.output_folder, pairs, poses, lost, diag, rows)
         if a.mesh:
             from .render import write_ply
             vertices, colors, triangles = vol.mesh(a.min_weight)
@@ -374,8 +550,11 @@ def make(a):
             write_ply(a.mesh, vertices, triangles, colors)
     except ValueError as e:
         return refuse(str(e))
-    print('%d frames, %d tracked, %d lost; %d x %d x %d voxels of %g m from (%g, %g, %g)' %
-          ((len(pairs), int((~lost).sum()), int(lost.sum())) + tuple(dims) + (a.voxel,) + tuple(origin)))
+    extra = ''
+    if a.reloc:
+        extra = '; %d keyframes, %d relocalised' % (keyframes, int(((rows[:, 2] >= 0) & ~lost).sum()))
+    print('%d frames, %d tracked, %d lost; %d x %d x %d voxels of %g m from (%g, %g, %g)%s' %
+          ((len(pairs), int((~lost).sum()), int(lost.sum())) + tuple(dims) + (a.voxel,) + tuple(origin) + (extra,)))
     return 0
 
 

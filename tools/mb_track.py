@@ -2,7 +2,9 @@
 maps, the ray casts of the levels, the iterations (sums, reduce, update), the commit, the integration -- on depth rendered
 from synthetic_scene, with the volume fused from 16 frames under their true poses.
 
-    python tools/mb_track.py [--dim 256 --voxel 0.02 --height 480 --width 640 --cells 32 --reps 50 --blocks 5]
+    python tools/mb_track.py [--dim 256 --voxel 0.02 --height 480 --width 640 --cells 32 --reps 50 --blocks 5] [--reloc]
+
+With --reloc: ms per push with the relocaliser (kfn_reloc_*) off and on, window by window in turns, and its four launches alone.
 
 Every figure is the median of `blocks` timed windows of `reps` calls, with the lowest and highest window beside it.  Beside
 the ray cast stand two floors at 8 TB/s: the maps it must write (32 bytes a pixel), and those plus the whole tsdf read once,
@@ -51,6 +53,55 @@ def slow_trajectory(count, step=0.03):
     return out
 
 
+def reloc_timings(a, torch, track, vol, plain, poses, depth, line):
+    """Two trackers on one volume, one with the relocaliser (defaults: 500 ferns, 1024 keyframe slots, 16 of them filled with the
+    fused frames' codes): a window of pushes of the one, then of the other, `blocks` times; then the four launches alone."""
+    B = len(poses)
+    frames = (a.reps + 2) * (a.blocks + 2) * 2 + 8
+    plain = track.Tracker(vol, max_frames=frames)
+    with_reloc = track.Tracker(vol, max_frames=frames, reloc=True)
+    rc = with_reloc.reloc
+    for trk in (plain, with_reloc):
+        trk.set_state(poses[B - 2])
+        trk.first, trk.pushed = poses[B - 2].copy(), 0
+        trk.vol.poses[:1].copy_(torch.from_numpy(track.pose_rows(poses[B - 2:B - 1])))
+    for k in range(B - 1):                                             # a store of keyframes: the fused frames, harvested or not
+        with_reloc._stage(depth[k], None)
+        with_reloc.live_maps()
+        rc.encode()
+        rc.codes[k].copy_(rc.code)
+        rc.key_poses[k].copy_(torch.from_numpy(poses[k][:3].reshape(12)))
+    st = rc.state()
+    st.n = B - 1
+    rc.set_state(st)
+    plain._stage(depth[B - 1], None)
+
+    def window(trk):
+        a0, b0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a0.record()
+        for _ in range(a.reps):
+            trk.push(depth[B - 1])
+        b0.record()
+        torch.cuda.synchronize()
+        return a0.elapsed_time(b0) / a.reps
+    for trk in (plain, with_reloc):
+        trk.push(depth[B - 1])
+    torch.cuda.synchronize()
+    off, on = [], []
+    for _ in range(a.blocks):
+        off.append(window(plain))
+        on.append(window(with_reloc))
+    print(line % ('Tracker.push, relocaliser off', float(np.median(off)), min(off), max(off)), ' lost %d' % int(plain.trajectory()[1].sum()))
+    print(line % ('Tracker.push, relocaliser on', float(np.median(on)), min(on), max(on)),
+          ' lost %d, %d keyframes; +%.1f %% of the push' % (int(with_reloc.trajectory()[1].sum()), with_reloc.relocalisation()[1],
+                                                            100.0 * (np.median(on) / np.median(off) - 1.0)))
+    print(line % (('kfn_reloc_encode, %d ferns' % rc.ferns,) + timed(torch, rc.encode, a.reps, a.blocks)))
+    print(line % (('kfn_reloc_search, %d slots' % rc.capacity,) + timed(torch, rc.search, a.reps, a.blocks)))
+    print(line % (('kfn_reloc_seed',) + timed(torch, rc.seed, a.reps, a.blocks)))
+    print(line % (('kfn_reloc_settle',) + timed(torch, rc.settle, a.reps, a.blocks)))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--dim', type=int, default=256)
@@ -60,6 +111,7 @@ def main(argv=None):
     ap.add_argument('--cells', type=int, default=32)
     ap.add_argument('--reps', type=int, default=50)
     ap.add_argument('--blocks', type=int, default=5)
+    ap.add_argument('--reloc', action='store_true', help='instead: the push with and without the relocaliser in turns, and its four launches alone')
     a = ap.parse_args(argv)
     import torch
     from kfnet_amd import fuse, render, synth, track
@@ -92,6 +144,8 @@ def main(argv=None):
     def casts():
         for l in range(trk.levels):
             trk.raycast(l)
+    if a.reloc:
+        return reloc_timings(a, torch, track, vol, trk, poses, depth, line)
     reset()
     trk._stage(depth[B - 1], None)
     ms = timed(torch, lambda: trk.push(depth[B - 1]), a.reps, a.blocks)
