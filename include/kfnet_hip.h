@@ -63,7 +63,8 @@ extern "C" {
  * kfn_fuse_scratch_bytes, kfn_fuse_integrate, kfn_fuse_extract_count and kfn_fuse_extract (depth maps fused into a truncated
  * signed distance volume, and the scene mesh extracted from it), and kfn_track_scratch_bytes, kfn_track_live_maps,
  * kfn_track_raycast, kfn_track_icp_sums, kfn_track_update and kfn_track_commit (the camera tracked against that volume), and kfn_reloc_encode,
- * kfn_reloc_search, kfn_reloc_seed and kfn_reloc_settle (a lost tracker relocalised from fern-coded keyframes). */
+ * kfn_reloc_search, kfn_reloc_seed and kfn_reloc_settle (a lost tracker relocalised from fern-coded keyframes), and
+ * kfn_kalman_scan_plan (which of the scan's instantiations a grid launches; host only). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -141,7 +142,8 @@ typedef struct kfn_conv_desc {
   int32_t ldy;          /* output pixel stride (floats), >= Cout */
   int32_t kh, kw;       /* kernel size (kh*kw <= 32) */
   int32_t stride;       /* 1 or 2 */
-  int32_t transposed;   /* 0 = conv2d SAME, 1 = conv2d_transpose SAME (stride 2) */
+  int32_t transposed;   /* 0 = conv2d SAME, 1 = conv2d_transpose SAME (stride 2; 3x3 kernels only: any other kh x kw with
+                         * transposed = 1 is KFN_ERR_ARG -- kh*kw <= 32 above is the promise of the forward convolution) */
   int32_t relu;         /* fuse tf.nn.relu */
   int32_t epilogue;     /* KFN_EPI_* applied after bias(+relu).  Forward convolutions only: a transposed call with an
                          * epilogue, and any value outside KFN_EPI_NONE .. KFN_EPI_EXP_1E2, is KFN_ERR_ARG (both used to
@@ -480,6 +482,18 @@ typedef struct kfn_kalman_desc {
 } kfn_kalman_desc;
 
 int kfn_kalman_scan_scratch_bytes(const kfn_kalman_desc* desc, size_t* bytes);
+/* Which kernel instantiation kfn_kalman_scan[_ex] will launch for `desc` (cf. kfn_conv2d_plan); the launcher decides by the
+ * same function.  No device access.  Only H and W decide (S > 0, H > 1, W > 1 as for the scan); with_optional_outputs != 0
+ * describes a call that passes opt_temp, opt_nis or opt_kf, which gets the instantiation with those stores compiled in.
+ *   form 1: H*W <= 5120, both state copies in the LDS          production 1024 threads x 5 pixels, optional outputs 768 x 7
+ *   form 2: H*W <= 6144, one LDS copy, mid-frame barrier        1024 x 6  / 512 x 12
+ *   form 3: H*W <= 8192, likewise                               1024 x 8  / 512 x 16
+ *   form 4: H*W <= 10240, likewise                              1024 x 10 / 512 x 20
+ *   form 5: above, one launch per frame, state through `scratch` (kfn_kalman_scan_scratch_bytes != 0 exactly here);
+ *           threads = 256, pixels_per_thread = 1
+ * threads * pixels_per_thread >= H*W in forms 1-4 (one workgroup per sequence). */
+int kfn_kalman_scan_plan(const kfn_kalman_desc* desc, int with_optional_outputs, int* form, int* threads,
+                         int* pixels_per_thread);
 int kfn_kalman_scan(const kfn_kalman_desc* desc,
                     const float* flow_xy,     /* [S,T,H*W,2] */
                     const float* sigma_trans, /* [S,T,H*W]   */

@@ -269,6 +269,7 @@ SYMBOLS = {
     'kfn_oflow_tail2': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'kfn_oflow_tail2_f16': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'kfn_kalman_scan_scratch_bytes': (_i, [C.POINTER(KalmanDesc), C.POINTER(_sz)]),
+    'kfn_kalman_scan_plan': (_i, [C.POINTER(KalmanDesc), _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     'kfn_kalman_scan': (_i, [C.POINTER(KalmanDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'kfn_kalman_scan_ex': (_i, [C.POINTER(KalmanDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'kfn_eval_metrics': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, _vp, _vp, _vp]),

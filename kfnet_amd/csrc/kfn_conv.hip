@@ -389,7 +389,9 @@ __global__ __launch_bounds__(64 * WM * WN, (TM * TN > 8 ? 1 : 2)) void conv_mfma
         // valid taps = [ky_lo, ky_hi) x [kx_lo, kx_hi)
         const int ky_lo = iy0 < 0 ? -iy0 : 0, ky_hi = (p.H - iy0 < p.kh) ? p.H - iy0 : p.kh;
         const int kx_lo = ix0 < 0 ? -ix0 : 0, kx_hi = (p.W - ix0 < p.kw) ? p.W - ix0 : p.kw;
-        const unsigned colmask = (kx_hi > kx_lo) ? (((1u << (kx_hi - kx_lo)) - 1u) << kx_lo) : 0u;
+        // kx_hi - kx_lo live columns, 1 ... 32: a 1x32 kernel has all 32 at interior pixels, where (1u << 32) - 1u would be
+        // undefined (the hardware takes the count mod 32: mask 0, every tap dropped), so the ones are shifted DOWN into place
+        const unsigned colmask = (kx_hi > kx_lo) ? ((0xFFFFFFFFu >> (32 - (kx_hi - kx_lo))) << kx_lo) : 0u;
         for (int ky = ky_lo; ky < ky_hi; ++ky) msk |= colmask << (ky * p.kw);
       }
       a_msk[i] = msk;
@@ -1107,6 +1109,10 @@ int validate(const kfn_conv_desc* d) {
   KFN_REQUIRE(d->kh > 0 && d->kw > 0 && d->kh * d->kw <= 32, "kfn_conv2d_nhwc: bad kernel %dx%d", d->kh, d->kw);
   KFN_REQUIRE(d->stride == 1 || d->stride == 2, "kfn_conv2d_nhwc: stride %d unsupported", d->stride);
   KFN_REQUIRE(!d->transposed || d->stride == 2, "kfn_conv2d_nhwc: transposed conv needs stride 2");
+  // the transposed path (parity-class row order, its tap masks) has only ever been run and checked with the networks' 3x3
+  // kernels: any other size is refused, not computed unchecked
+  KFN_REQUIRE(!d->transposed || (d->kh == 3 && d->kw == 3),
+              "kfn_conv2d_nhwc: transposed conv is implemented for 3x3 kernels only (got %dx%d)", d->kh, d->kw);
   // an epilogue the kernel would not apply is refused, not dropped: the head epilogues are compiled into the forward
   // 32-column instantiations only (HEAD_EPI), and their switch has no case for an unknown value
   KFN_REQUIRE(d->epilogue >= KFN_EPI_NONE && d->epilogue <= KFN_EPI_EXP_1E2, "kfn_conv2d_nhwc: unknown epilogue %d", d->epilogue);

@@ -482,12 +482,35 @@ int launch_scan_dbg(const KalmanArgs& a, hipStream_t stream) {
   return KFN_OK;
 }
 
+// The decision: which of the scan's five forms a grid runs in, and with which thread mapping.  kfn_kalman_scan_ex launches by
+// it, kfn_kalman_scan_plan and kfn_kalman_scan_scratch_bytes report it: one function, so the three cannot drift apart.
+//   form 1: both state copies in the LDS (H*W <= 5120); 2 / 3 / 4: one LDS copy, new states waiting in registers for the
+//   mid-frame barrier (H*W <= 6144 / 8192 / 10240); 5: per-frame launches, state ping-pong through the caller's scratch copy.
+// `with_opt`: the call asks for temp / NIS / raw-KF maps and gets the instantiation that has them compiled in.
+struct ScanPlan { int form, threads, ppt; };
+constexpr int SCAN_LDS_BYTES = 160 * 1024;
+inline ScanPlan scan_plan(int H, int W, bool with_opt) {
+  const size_t hw = (size_t)H * W;
+  if (hw * 16 > (size_t)SCAN_LDS_BYTES) return {5, 256, 1};   // state larger than the LDS
+  // 768 threads (12 wavefronts, 170-VGPR budget) x 7 pixels cover the 60x80 grid without
+  // register spills; larger grids fall back to 1024 threads and the single-buffer form.
+  const bool dbl = hw * 32 <= (size_t)SCAN_LDS_BYTES;  // two LDS copies of the state fit
+  if (dbl && hw <= (size_t)SCAN_KT * SCAN_PPT) return with_opt ? ScanPlan{1, 768, 7} : ScanPlan{1, SCAN_KT, SCAN_PPT};
+  if (hw <= 1024 * 6) return with_opt ? ScanPlan{2, 512, 12} : ScanPlan{2, 1024, 6};
+  if (hw <= 1024 * 8) return with_opt ? ScanPlan{3, 512, 16} : ScanPlan{3, 1024, 8};
+  return with_opt ? ScanPlan{4, 512, 20} : ScanPlan{4, 1024, 10};
+}
+
 // the production instantiation has no optional outputs compiled in; a call that asks for temp / NIS / raw-KF maps
 // (eval metrics, debug) gets the instantiation that has them -- DD = its ring depth (the three optional stores per pixel
 // cost registers: a full ring would spill)
 template <int KT, int PPT, bool DBL, int D, bool NT, int KT_DBG = KT, int PPT_DBG = PPT, int DD = 1>
-int launch_scan(const KalmanArgs& a, hipStream_t stream) {
-  if (a.opt_temp || a.opt_nis || a.opt_kf) return launch_scan_dbg<KT_DBG, PPT_DBG, DBL, DD, NT, true, false>(a, stream);
+int launch_scan(const KalmanArgs& a, hipStream_t stream, const ScanPlan& plan) {
+  const bool dbg = a.opt_temp || a.opt_nis || a.opt_kf;
+  // the instantiation launched is the one the plan names: a plan that drifts from these template arguments is refused here
+  KFN_REQUIRE(plan.threads == (dbg ? KT_DBG : KT) && plan.ppt == (dbg ? PPT_DBG : PPT),
+              "kfn_kalman_scan: plan %d x %d names no instantiation of form %d", plan.threads, plan.ppt, plan.form);
+  if (dbg) return launch_scan_dbg<KT_DBG, PPT_DBG, DBL, DD, NT, true, false>(a, stream);
   return launch_scan_dbg<KT, PPT, DBL, D, NT, false, /*PTR=*/DBL>(a, stream);
 }
 
@@ -512,7 +535,18 @@ extern "C" int kfn_kalman_scan_scratch_bytes(const kfn_kalman_desc* d, size_t* b
   KFN_REQUIRE(d && bytes, "kfn_kalman_scan_scratch_bytes: null argument");
   KFN_REQUIRE(d->S > 0 && d->H > 1 && d->W > 1, "kfn_kalman_scan_scratch_bytes: bad shape S=%d H=%d W=%d", d->S, d->H, d->W);
   const size_t hw = (size_t)d->H * d->W;
-  *bytes = hw * 16 > 160 * 1024 ? (size_t)d->S * hw * 16 : 0;   // a second copy of the state, only when it cannot live in LDS
+  *bytes = scan_plan(d->H, d->W, false).form == 5 ? (size_t)d->S * hw * 16 : 0;   // a second copy of the state, only when it cannot live in LDS
+  return KFN_OK;
+}
+
+extern "C" int kfn_kalman_scan_plan(const kfn_kalman_desc* d, int with_optional_outputs, int* form, int* threads,
+                                    int* pixels_per_thread) {
+  KFN_REQUIRE(d && form && threads && pixels_per_thread, "kfn_kalman_scan_plan: null argument");
+  KFN_REQUIRE(d->S > 0 && d->H > 1 && d->W > 1, "kfn_kalman_scan_plan: bad shape S=%d H=%d W=%d", d->S, d->H, d->W);
+  const ScanPlan p = scan_plan(d->H, d->W, with_optional_outputs != 0);
+  *form = p.form;
+  *threads = p.threads;
+  *pixels_per_thread = p.ppt;
   return KFN_OK;
 }
 
@@ -541,7 +575,8 @@ extern "C" int kfn_kalman_scan_ex(const kfn_kalman_desc* d, const float* flow_xy
   a.eps2 = floor_variance(d->min_uncertainty);
   a.d = *d;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if ((size_t)HW * 16 > 160 * 1024) {
+  const ScanPlan plan = scan_plan(d->H, d->W, opt_temp || opt_nis || opt_kf);
+  if (plan.form == 5) {
     // state larger than the LDS: per-frame launches, state ping-pong between `state` and the CALLER's scratch copy
     // (kfn_kalman_scan_scratch_bytes): nothing is allocated here, the T launches are stream-ordered and capturable.
     // (A single cooperative launch with a grid barrier per frame was the alternative: ~4 us per barrier against ~1.5 us
@@ -552,10 +587,10 @@ extern "C" int kfn_kalman_scan_ex(const kfn_kalman_desc* d, const float* flow_xy
                 "kfn_kalman_scan_scratch_bytes() = %zu bytes", d->H, d->W, bytes);
     f32x4* scratch = reinterpret_cast<f32x4*>(scratch_buf);
     f32x4* buf[2] = {a.state, scratch};
-    const dim3 grid((unsigned)((HW + 255) / 256), (unsigned)d->S);
+    const dim3 grid((unsigned)((HW + plan.threads - 1) / plan.threads), (unsigned)d->S);
     int rc = KFN_OK;
     for (int t = 0; t < d->T && rc == KFN_OK; ++t) {
-      hipLaunchKernelGGL(kalman_step_kernel, grid, dim3(256), 0, s, a, buf[t & 1], buf[(t + 1) & 1], t);
+      hipLaunchKernelGGL(kalman_step_kernel, grid, dim3(plan.threads), 0, s, a, buf[t & 1], buf[(t + 1) & 1], t);
       rc = kfn::check_hip(hipGetLastError(), "kalman_step_kernel");
     }
     if (rc == KFN_OK && (d->T & 1))
@@ -565,19 +600,18 @@ extern "C" int kfn_kalman_scan_ex(const kfn_kalman_desc* d, const float* flow_xy
   KFN_REQUIRE((long)d->T * HW * 16L < (1L << 31),
               "kfn_kalman_scan: T * H * W = %ld pixel-frames per sequence exceed the 32-bit offsets of one launch (at most %ld frames "
               "of this grid): scan the sequence in chunks", (long)d->T * HW, ((1L << 31) - 1) / (16L * HW));
-  // 768 threads (12 wavefronts, 170-VGPR budget) x 7 pixels cover the 60x80 grid without
-  // register spills; larger grids fall back to 1024 threads and the single-buffer form.
-  const bool dbl = (size_t)HW * 32 <= 160 * 1024;  // two LDS copies of the state fit
   constexpr bool NT = SCAN_NT;
-  if (dbl && HW <= SCAN_KT * SCAN_PPT)
-    return launch_scan<SCAN_KT, SCAN_PPT, true, SCAN_DEPTH, NT, 768, 7, 1>(a, s);
-  // single LDS copy (config 5's 68x120 = 8160-pixel grid takes the second line): the new states of a frame wait in
+  // launch_scan<production KT, PPT, .., KT_DBG, PPT_DBG, ..>: the pairs scan_plan reports for the form (checked inside)
+  // single LDS copy (config 5's 68x120 = 8160-pixel grid takes form 3): the new states of a frame wait in
   // registers for the mid-frame barrier -- 1024 threads keep that to PPT <= 10 float4 per thread beside a two-deep input
   // ring.  Measured (tools/mb/kalman_mb, 68x120, S = 256 x T = 32 / S = 4 x T = 64): rounds 1-4's 512 x 16 with the loads at
   // the frame start 0.867 / 1.011 ms; 1024 x 8 with D = 2 0.793 / 0.914; D = 4 0.796 / 0.968; 768 x 11 D = 1 0.787 / 1.064.
-  if (HW <= 1024 * 6) return launch_scan<1024, 6, false, 2, NT, 512, 12, 1>(a, s);
-  if (HW <= 1024 * 8) return launch_scan<1024, 8, false, SCAN_BIG_DEPTH, NT, 512, 16, 1>(a, s);
-  return launch_scan<1024, 10, false, 1, NT, 512, 20, 1>(a, s);
+  switch (plan.form) {
+    case 1: return launch_scan<SCAN_KT, SCAN_PPT, true, SCAN_DEPTH, NT, 768, 7, 1>(a, s, plan);
+    case 2: return launch_scan<1024, 6, false, 2, NT, 512, 12, 1>(a, s, plan);
+    case 3: return launch_scan<1024, 8, false, SCAN_BIG_DEPTH, NT, 512, 16, 1>(a, s, plan);
+    default: return launch_scan<1024, 10, false, 1, NT, 512, 20, 1>(a, s, plan);
+  }
 }
 
 extern "C" int kfn_kalman_scan(const kfn_kalman_desc* d, const float* flow_xy,

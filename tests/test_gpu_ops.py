@@ -333,10 +333,11 @@ def test_kalman_scan_variance_floor_is_the_double_product_rounded_once(grid):
     assert np.allclose(g_tmp, r_tmp, rtol=2e-6, atol=2e-6) and np.allclose(g_rec, r_rec, rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize('grid', [(60, 80), (68, 120)])
+@pytest.mark.parametrize('grid', [(60, 80), (68, 120), (72, 80), (80, 120)])
 def test_kalman_scan_is_reproducible_under_memory_load(grid):
     """The production instantiations (no optional outputs; 60x80: double-buffered state, 68x120: single-buffer form whose
-    records leave through 16-byte buffer stores with scalar descriptors) beside a loaded memory system: 20 launches, records
+    records leave through 16-byte buffer stores with scalar descriptors; 72x80 and 80x120: the single-buffer forms of 6 and
+    10 pixels per thread, tests/branches.py) beside a loaded memory system: 20 launches, records
     and final state bit-identical to an unloaded launch and to the instantiation WITH the optional outputs.  (The first
     scalar-descriptor build of round 5 returned wrong records here: the store hazard of kfn_common.h buffer_store_b128.)"""
     import torch
