@@ -64,7 +64,8 @@ extern "C" {
  * signed distance volume, and the scene mesh extracted from it), and kfn_track_scratch_bytes, kfn_track_live_maps,
  * kfn_track_raycast, kfn_track_icp_sums, kfn_track_update and kfn_track_commit (the camera tracked against that volume), and kfn_reloc_encode,
  * kfn_reloc_search, kfn_reloc_seed and kfn_reloc_settle (a lost tracker relocalised from fern-coded keyframes), and
- * kfn_kalman_scan_plan (which of the scan's instantiations a grid launches; host only). */
+ * kfn_kalman_scan_plan (which of the scan's instantiations a grid launches; host only), and kfn_conv2d_grad_weights_plan
+ * (tiles and runs of pixels of a weight-gradient launch; host only). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -820,6 +821,15 @@ int kfn_recv_state(kfn_comm* comm, int peer, float* state /* [H,W,4] */, int H, 
  * results go to planes of `workspace` (kfn_conv2d_grad_weights_workspace_bytes) and are added in a fixed order by a second
  * launch: no atomics, bit-identical from launch to launch, and the split depends on the shapes only. */
 int kfn_conv2d_grad_weights_workspace_bytes(const kfn_conv_desc* desc, size_t* bytes);
+/* What kfn_conv2d_grad_weights will launch for `desc` (cf. kfn_kalman_scan_plan); the launcher and the workspace size are
+ * decided by the same function, every refusal of the launcher that the descriptor alone decides is returned here too.  No
+ * device access.
+ *   tn       1 (Cout <= 64: workgroup tiles of 128 k x 64 co) or 2 (128 x 128)
+ *   tiles_m  ceil((kh*kw*Cin + 1) / 128), the + 1 being the bias row;  tiles_n  ceil(Cout / (64 tn))
+ *   splits   runs of pixels = planes of the workspace;  chunk  pixels per run, a multiple of the stage (16 pixels with fp32
+ *            operands, 32 with KFN_OPERAND_F16); the last run holds N*Ho*Wo - (splits - 1) * chunk pixels
+ * workspace bytes = splits * (kh*kw*Cin + 1) * Cout * 4. */
+int kfn_conv2d_grad_weights_plan(const kfn_conv_desc* desc, int* tn, int* tiles_m, int* tiles_n, int* splits, long* chunk);
 int kfn_conv2d_grad_weights(const kfn_conv_desc* desc, const float* x, const float* dz, float* dw, float* db,
                             float* workspace, void* stream);
 /* The same for SCoordNet.preprocess + conv1a (cnn_wrapper/SCoordNet.py:20-21,34-37) as kfn_first_conv_u8 evaluates them:
@@ -840,7 +850,10 @@ int kfn_relu_grad(const float* y, int ldy, float* dz, int ldz, long P, int C, vo
  *   KFN_PACK_INPUT_GRAD_S2  [cin_pad][kh*kw*cout16]          ... as the transposed convolution: w[a][b][ci][co]
  * cout_pad / cin_pad = the count rounded up to a multiple of 32 (zero rows), cout16 = Cout rounded up to a multiple of
  * 16 (zero columns: 'prediction' has 4 output channels, its dz lives in a 16-channel buffer whose other channels are 0).
- * conv1a's forward matrix [27][C1] is the master copy itself.  kfn_pack_conv_weights_floats: the size of `out`. */
+ * conv1a's forward matrix [27][C1] is the master copy itself.  kfn_pack_conv_weights_floats: the size of `out`.
+ * KFN_PACK_INPUT_GRAD_S1 takes odd kh and kw only (KFN_ERR_ARG otherwise, from all three entry points): SAME padding of an
+ * even kernel puts (k - 1) / 2 pixels in front and one more behind, the convolution with the rotated kernel would need the
+ * larger share in front, so kfn_conv2d_nhwc on such a pack would return the input gradient shifted by one pixel. */
 #define KFN_PACK_FORWARD 0
 #define KFN_PACK_INPUT_GRAD_S1 1
 #define KFN_PACK_INPUT_GRAD_S2 2

@@ -296,6 +296,8 @@ SYMBOLS = {
     'kfn_recv_state': (_i, [_vp, _i, _vp, _i, _i, _vp]),
     # training SCoordNet (added exports, ABI 12)
     'kfn_conv2d_grad_weights_workspace_bytes': (_i, [C.POINTER(ConvDesc), C.POINTER(_sz)]),
+    'kfn_conv2d_grad_weights_plan': (_i, [C.POINTER(ConvDesc), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
+                                          C.POINTER(C.c_long)]),
     'kfn_conv2d_grad_weights': (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
     'kfn_first_conv_u8_grad_weights_workspace_bytes': (_i, [_i, _i, _i, _i, C.POINTER(_sz)]),
     'kfn_first_conv_u8_grad_weights': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -306,6 +306,13 @@ int pack_dims(int kh, int kw, int Cin, int Cout, int kind, int* rows_pad, int* c
               kh, kw, Cin, Cout);
   KFN_REQUIRE(kind == KFN_PACK_FORWARD || kind == KFN_PACK_INPUT_GRAD_S1 || kind == KFN_PACK_INPUT_GRAD_S2,
               "kfn_pack_conv_weights: unknown kind %d", kind);
+  // The input gradient is the SAME convolution of dz with the rotated kernel only when SAME pads both sides alike.  An even
+  // kernel pads (k - 1) / 2 in front and one more behind, the rotated one needs the larger share in front: kfn_conv2d_nhwc
+  // on such a pack would return the gradient shifted by one pixel.
+  KFN_REQUIRE(kind != KFN_PACK_INPUT_GRAD_S1 || (kh % 2 == 1 && kw % 2 == 1),
+              "kfn_pack_conv_weights: KFN_PACK_INPUT_GRAD_S1 needs an odd kernel (%dx%d): SAME padding of an even kernel is "
+              "asymmetric, so the stride-1 convolution of dz with the rotated kernel is the input gradient shifted by one pixel",
+              kh, kw);
   const int rows = kind == KFN_PACK_FORWARD ? Cout : Cin, cols = kind == KFN_PACK_FORWARD ? Cin : Cout;
   *rows_pad = (rows + 31) / 32 * 32;
   *cols_pad = (cols + 15) / 16 * 16;
@@ -326,6 +333,22 @@ extern "C" int kfn_conv2d_grad_weights_workspace_bytes(const kfn_conv_desc* d, s
   int rc = wgrad_plan(d, &pl, "kfn_conv2d_grad_weights_workspace_bytes");
   if (rc != KFN_OK) return rc;
   *bytes = (size_t)pl.splits * (pl.Ktot + 1) * d->Cout * sizeof(float);
+  return KFN_OK;
+}
+
+// What kfn_conv2d_grad_weights will launch for `d`: wgrad_plan is the one function that decides, for the launcher, for the
+// workspace size and for this report.  No device access.
+extern "C" int kfn_conv2d_grad_weights_plan(const kfn_conv_desc* d, int* tn, int* tiles_m, int* tiles_n, int* splits, long* chunk) {
+  KFN_REQUIRE(d && tn && tiles_m && tiles_n && splits && chunk, "kfn_conv2d_grad_weights_plan: null argument");
+  KFN_CONV_DESC_IN(d, "kfn_conv2d_grad_weights_plan");
+  WgradPlan pl;
+  int rc = wgrad_plan(d, &pl, "kfn_conv2d_grad_weights_plan");
+  if (rc != KFN_OK) return rc;
+  *tn = pl.tn;
+  *tiles_m = pl.tiles_m;
+  *tiles_n = pl.tiles_n;
+  *splits = pl.splits;
+  *chunk = pl.chunk;
   return KFN_OK;
 }
 
