@@ -180,9 +180,10 @@ class KFNet():
         net_ops = self.oflownet.ops
         if not g.fuse_oflow_window:
             return
-        # kfn_oflow_tail2 needs 4 x 32 560 B of dynamic LDS per workgroup: gfx950's 160 KiB.  On a part with less the
-        # round-2 launches (gather + conv1a, upconv0 + kfn_oflow_tail) stay in place.
-        if getattr(g, 'lds_bytes_per_cu', 160 * 1024) < 4 * 32560:
+        # kfn_oflow_tail2 needs 4 x 31 280 B of images + 18 432 B of upconv0 fragments of dynamic LDS per workgroup (fp16 form:
+        # 4 x 32 560 B): gfx950's 160 KiB.  On a part with less the round-2 launches (gather + conv1a, upconv0 +
+        # kfn_oflow_tail) stay in place.
+        if getattr(g, 'lds_bytes_per_cu', 160 * 1024) < 4 * 31280 + 18432:
             return
         y0 = conv0.y
         tails = [op for op in net_ops if isinstance(op, OFlowTailOp)]

@@ -13,14 +13,21 @@
 // (the class convolutions of the factored cost volume, see kfn_cost_volume_gather in include/kfnet_hip.h) straight
 // into an LDS image, neighbouring windows share 7/8 of their G reads through the L2; upconv0 is 72 MFMAs on the 4x4
 // conv5 patch (one 16x16x32 product per (output parity class, live tap)); nothing but conv1a's [P,4,4,32] and the
-// flow leaves the chip.  All MFMAs are v_mfma_f32_16x16x4_f32 (exact fp32; kfn_oflow_tail2_f16: 16x16x16 f16 for config 5); every layer's weights live in registers
-// for the whole kernel (conv1a 144, upconv0 72, conv6 108 per lane).
+// flow leaves the chip.  All MFMAs are v_mfma_f32_16x16x4_f32 (exact fp32; kfn_oflow_tail2_f16: 16x16x16 f16 for config 5); the
+// weights stay on the chip for the whole kernel: conv1a 144 registers per lane; fp32 tail: conv6 as its Winograd F(2x2,3x3)
+// operand U = G w G^T, 192 accumulation registers per lane, and upconv0's 72 fragments in LDS (one copy per workgroup);
+// fp16 tail: conv6 27 and upconv0 18 register pairs.
+//
+// conv6 in the fp32 tail is F(2x2,3x3), lane-local on both sides of the MFMAs: the window's 8x8 cells are 16 tiles of 2x2,
+// one 16-row M-block; a lane reads its tile's 4x4 patch, forms B^T d B in registers and feeds the 16 positions' MFMAs
+// (192 per window instead of the nine-tap form's 432); the accumulators of a lane hold four whole tiles, so A^T M A is
+// lane-local too.  Per window and SIMD at 2.31 GHz: 23.3 K cycles with nine taps (16.1 K of MFMAs), 17.2 K now (8.4 K).
 //
 // LDS images (per wave; zero borders written once, interiors rewritten per window):
-//   tail2: concat0 10x10 cells x 56 floats (cell (cy+1, cx+1); channels [0,16) upconv0, [16,48) conv0),
+//   tail2: concat0 10x10 cells (cell (cy+1, cx+1); channels [0,16) upconv0, [16,48) conv0); fp32: 52 floats per cell in rows
+//          of 528 (the patch reads' pitch, LD1W below); fp16: 56 floats per cell -- an M-block of its conv6 is 8 rows x 2
+//          columns of the window, and with 56 floats the A-fragment ds_read_b128s are bank-conflict free;
 //          conv6 10 rows x (10 cells x 16 + 4 pad), conv5 patch 5x5 x 36 (zero row 0 / column 0: the transposed conv's i-1, j-1 taps).
-//          An M-block of conv6 is 8 rows x 2 columns of the window: with 56 floats per cell the A-fragment
-//          ds_read_b128s are bank-conflict free (the 2x8 blocks of kfn_oflow_tail.hip cannot be).
 //   head:  conv0 9x9 cells x 36 floats (TF SAME for stride 2 on an even size pads bottom / right only).
 #include "kfn_common.h"
 
@@ -46,6 +53,18 @@ constexpr int T1_BYTES = 100 * LD1 * 4;
 constexpr int T2_BYTES = 10 * ROW2 * 4;
 constexpr int T3_BYTES = 25 * LD3 * 4;
 constexpr int TAIL_WAVE_BYTES = T1_BYTES + T2_BYTES + T3_BYTES;
+// tail2, fp32 (conv6 by F(2x2,3x3)): a lane reads its tile's 4x4 patch of concat0, cells (2ty + i, 2tx + j) of lane
+// (tile = l % 16 = ty*4 + tx, kq = l / 16) at channel quad 3 kq + s.  In 16-byte slots the address is
+// (2ty + i) R + (2tx + j) L + 3 kq + s; a ds_read_b128 group holds eight tiles of an even kq (ty in {0,3} or {1,2}) and the
+// other eight of the odd kq next to it, so the even kq takes the even slots of the 256-byte bank row and the odd one the
+// odd slots, and within a kq the eight (ty R + tx L) mod 8 must differ: L odd, R = 4 mod 8.  L = 13 (52 floats per cell),
+// R = 132 (rows of 10 cells + 8 floats).  The 56-float pitch of the nine-tap reads is 4-way on these reads.
+constexpr int LD1W = 52;
+constexpr int ROW1W = 10 * LD1W + 8;
+constexpr int T1W_BYTES = 10 * ROW1W * 4;
+constexpr int TAILW_WAVE_BYTES = T1W_BYTES + T2_BYTES + T3_BYTES;
+constexpr int WU_BYTES = 72 * 64 * 4;   // upconv0's fragments, one copy for the four waves (behind their images)
+constexpr int TAILW_BYTES = 4 * TAILW_WAVE_BYTES + WU_BYTES;
 constexpr int HEAD_WAVE_BYTES = 81 * LDA * 4;
 
 __device__ __forceinline__ f32x4 buf_load(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
@@ -231,35 +250,62 @@ __global__ __launch_bounds__(256, 1) void oflow_tail2_kernel(FusedArgs a, const 
                                                              const float* __restrict__ wp, const float* __restrict__ bp,
                                                              float* __restrict__ flow, float* __restrict__ logits_out) {
   extern __shared__ __attribute__((aligned(16))) char smem_of[];
+  constexpr int LDC = H16 ? LD1 : LD1W;            // concat0 image: floats per cell and per row of 10 cells
+  constexpr int ROWC = H16 ? 10 * LD1 : ROW1W;
+  constexpr int WAVE_BYTES = H16 ? TAIL_WAVE_BYTES : TAILW_WAVE_BYTES;
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
-  char* const t1 = smem_of + wv * TAIL_WAVE_BYTES;
-  char* const t2 = t1 + T1_BYTES;
+  char* const t1 = smem_of + wv * WAVE_BYTES;
+  char* const t2 = t1 + (H16 ? T1_BYTES : T1W_BYTES);
   char* const t3 = t2 + T2_BYTES;
-  for (int i = lane; i < TAIL_WAVE_BYTES / 16; i += 64) reinterpret_cast<f32x4*>(t1)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int i = lane; i < WAVE_BYTES / 16; i += 64) reinterpret_cast<f32x4*>(t1)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   __builtin_amdgcn_wave_barrier();   // the zero fill is ordered before the first interior stores (same wave; pins the compiler)
 
-  // conv6: fragment t = tap*12 + j of lane (n, kq) = w6[tap][kq*12 + j][n]   (graph.pack_oflow_tail_kernel)
-  // H16: fragment t = tap*3 + s, four halfs j = w6[tap][kq*12 + 4s + j][n]    (graph.pack_oflow_tail_kernel_f16)
-  float w6r[H16 ? 1 : 108];
+  // conv6, H16: fragment t = tap*3 + s, four halfs j = w6[tap][kq*12 + 4s + j][n]    (graph.pack_oflow_tail_kernel_f16)
+  // fp32: fragment t = tap*12 + j of lane (n, kq) = w6[tap][kq*12 + j][n] (graph.pack_oflow_tail_kernel) is transformed here,
+  // once per wave, into the F(2x2,3x3) operand U = G w G^T: u6[pos = i*4 + l][j], the B value of transform position (i, l)
+  // at k-step j.  G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1]: a sum and a halving per axis, two roundings per weight.
+  float u6[H16 ? 1 : 16][H16 ? 1 : 12];
   f16x4 w6h[H16 ? 27 : 1];
   if constexpr (H16) {
 #pragma unroll
     for (int t = 0; t < 27; ++t) w6h[t] = static_cast<const f16x4*>(w6p_)[t * 64 + lane];
   } else {
 #pragma unroll
-    for (int t = 0; t < 108; ++t) w6r[t] = static_cast<const float*>(w6p_)[t * 64 + lane];
+    for (int j = 0; j < 12; ++j) {
+      float g[4][3];
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const float g0 = static_cast<const float*>(w6p_)[((0 * 3 + kx) * 12 + j) * 64 + lane];
+        const float g1 = static_cast<const float*>(w6p_)[((1 * 3 + kx) * 12 + j) * 64 + lane];
+        const float g2 = static_cast<const float*>(w6p_)[((2 * 3 + kx) * 12 + j) * 64 + lane];
+        g[0][kx] = g0;
+        g[1][kx] = 0.5f * ((g0 + g2) + g1);
+        g[2][kx] = 0.5f * ((g0 + g2) - g1);
+        g[3][kx] = g2;
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float u[4] = {g[i][0], 0.5f * ((g[i][0] + g[i][2]) + g[i][1]), 0.5f * ((g[i][0] + g[i][2]) - g[i][1]), g[i][2]};
+        // U is 192 of the wave's 512 registers and only ever an MFMA's B operand: defined as accumulation registers, which
+        // the MFMAs read in place (left to the allocator they become VGPRs spilled there: a v_accvgpr_read per MFMA)
+#pragma unroll
+        for (int l = 0; l < 4; ++l) asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(u6[i * 4 + l][j]) : "v"(u[l]));
+      }
+    }
   }
-  // upconv0: fragment t = tap*8 + j = wu[ky][kx][n][kq*8 + j]                  (graph.pack_oflow_upconv_kernel)
-  // H16: fragment t = tap*2 + s, four halfs j = wu[ky][kx][n][kq*8 + 4s + j]  (graph.pack_oflow_upconv_kernel_f16)
-  float wur[H16 ? 1 : 72];
+  // upconv0, H16: fragment t = tap*2 + s, four halfs j = wu[ky][kx][n][kq*8 + 4s + j]  (graph.pack_oflow_upconv_kernel_f16)
+  // fp32: fragment t = tap*8 + j = wu[ky][kx][n][kq*8 + j] (graph.pack_oflow_upconv_kernel).  U takes 192 registers, so the 72
+  // fragments live in LDS, one copy for the four waves, and are read per window as B operands (word t*64 + lane: no conflicts).
   f16x4 wuh[H16 ? 18 : 1];
+  const float* const wus = reinterpret_cast<const float*>(smem_of + 4 * WAVE_BYTES) + lane;
   if constexpr (H16) {
 #pragma unroll
     for (int t = 0; t < 18; ++t) wuh[t] = static_cast<const f16x4*>(wup_)[t * 64 + lane];
   } else {
-#pragma unroll
-    for (int t = 0; t < 72; ++t) wur[t] = static_cast<const float*>(wup_)[t * 64 + lane];
+    float* const dst = reinterpret_cast<float*>(smem_of + 4 * WAVE_BYTES);
+    for (int i = threadIdx.x; i < WU_BYTES / 4; i += 256) dst[i] = static_cast<const float*>(wup_)[i];
+    __syncthreads();   // every wave reaches it: the window loop starts below
   }
   const int li = lane & 15, kq = lane >> 4;
   const float bias6 = b6 ? b6[li] : 0.f;
@@ -272,7 +318,7 @@ __global__ __launch_bounds__(256, 1) void oflow_tail2_kernel(FusedArgs a, const 
 #pragma unroll
   for (int it = 0; it < 8; ++it) {
     const int k = it * 64 + lane, cell = k >> 3, q = k & 7;
-    st_off[it] = (((cell >> 3) + 1) * 10 + (cell & 7) + 1) * (LD1 * 4) + (CU + q * 4) * 4;
+    st_off[it] = (((cell >> 3) + 1) * ROWC + ((cell & 7) + 1) * LDC) * 4 + (CU + q * 4) * 4;
   }
   int s5_off[2];   // conv5 patch item k = it*64 + lane -> (cell = k/8 of the 4x4 patch, quad k%8), padded cell (i+1, j+1)
 #pragma unroll
@@ -283,10 +329,13 @@ __global__ __launch_bounds__(256, 1) void oflow_tail2_kernel(FusedArgs a, const 
   // upconv0 A fragments: row r = input cell (i, j) = (r>>2, r&3); shift (di,dj) reads padded cell (i+1-di, j+1-dj)
   const int u_base = (((li >> 2) + 1) * 5 + (li & 3) + 1) * (LD3 * 4) + kq * 32;
   // upconv0 result: element e of lane (n, kq), class (pa,pb) = output cell (2 kq + pa, 2 e + pb), channel n
-  const int uo_base = ((2 * kq + 1) * 10 + 1) * (LD1 * 4) + li * 4;
-  // conv6 A fragments: M-block mb = window columns 2mb, 2mb+1; row r = cell (r>>1, 2mb + (r&1))
-  const int a_base = ((li >> 1) * 10 + (li & 1)) * (LD1 * 4) + kq * 48;
-  // conv6 result: element e of block mb = cell (2 kq + (e>>1), 2 mb + (e&1)), channel n
+  const int uo_base = ((2 * kq + 1) * ROWC + LDC) * 4 + li * 4;
+  // conv6 A fragments, H16: M-block mb = window columns 2mb, 2mb+1; row r = cell (r>>1, 2mb + (r&1))
+  // fp32: row r = tile (ty, tx) = (r>>2, r&3) of 2x2 cells; its 4x4 patch starts at padded cell (2ty, 2tx)
+  const int a_base = H16 ? ((li >> 1) * 10 + (li & 1)) * (LD1 * 4) + kq * 48
+                         : (2 * (li >> 2) * ROWC + 2 * (li & 3) * LDC) * 4 + kq * 48;
+  // conv6 result, H16: element e of block mb = cell (2 kq + (e>>1), 2 mb + (e&1)), channel n
+  // fp32: element e of every position's accumulator = tile (kq, e), cells (2 kq + a, 2 e + b), channel n
   const int o_base = ((2 * kq + 1) * ROW2 + LD2) * 4 + li * 4;
   // prediction: lane = window cell (ci, cj)
   const int ci = lane >> 3, cj = lane & 7;
@@ -312,12 +361,16 @@ __global__ __launch_bounds__(256, 1) void oflow_tail2_kernel(FusedArgs a, const 
     *reinterpret_cast<f32x4*>(t3 + s5_off[0]) = v5[0];
     *reinterpret_cast<f32x4*>(t3 + s5_off[1]) = v5[1];
     const int pn = p + pstride;
-    if (pn < a.P) {   // wave-uniform
-      conv0_issue(a, st, rsT, rsG, pn, tv, gv);
-      const f32x4* src = reinterpret_cast<const f32x4*>(x5 + (size_t)pn * (16 * C0));
-      v5[0] = src[lane];
-      v5[1] = src[64 + lane];
-    }
+    auto issue_next = [&]() __attribute__((always_inline)) {
+      if (pn < a.P) {   // wave-uniform
+        conv0_issue(a, st, rsT, rsG, pn, tv, gv);
+        const f32x4* src = reinterpret_cast<const f32x4*>(x5 + (size_t)pn * (16 * C0));
+        v5[0] = src[lane];
+        v5[1] = src[64 + lane];
+      }
+    };
+    // (fp32: the 72 registers of the next window's loads are free only from conv6's last channel quad on -- issued there)
+    if constexpr (H16) issue_next();
     __builtin_amdgcn_wave_barrier();
 
     // ---- upconv0: y[2i+pa, 2j+pb] = b + sum over the live taps of class (pa,pb) of x[i-di, j-dj] . w[ky][kx] --------
@@ -331,7 +384,14 @@ __global__ __launch_bounds__(256, 1) void oflow_tail2_kernel(FusedArgs a, const 
 #pragma unroll
         for (int s = 0; s < 2; ++s)
           ua[di][dj][s] = *reinterpret_cast<const f32x4*>(t3 + u_base - (di * 5 + dj) * (LD3 * 4) + s * 16);
-    if constexpr (H16) __builtin_amdgcn_sched_barrier(0);   // the eight reads as one group (4-pass MFMAs hide no LDS latency)
+    // fp32: the 72 B fragments come from LDS, all reads ahead of the MFMAs (the registers are conv6's, idle here): read by
+    // read in front of its MFMA, each pair of MFMAs waited for an LDS latency
+    float wur[H16 ? 1 : 72];
+    if constexpr (!H16) {
+#pragma unroll
+      for (int t = 0; t < 72; ++t) wur[t] = wus[t * 64];
+    }
+    __builtin_amdgcn_sched_barrier(0);   // the reads as one group (H16: 4-pass MFMAs hide no LDS latency)
     f32x4 ud[2][2];
 #pragma unroll
     for (int pa = 0; pa < 2; ++pa)
@@ -360,14 +420,15 @@ __global__ __launch_bounds__(256, 1) void oflow_tail2_kernel(FusedArgs a, const 
       for (int pb = 0; pb < 2; ++pb)
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          *reinterpret_cast<float*>(t1 + uo_base + (pa * 10 + 2 * e + pb) * (LD1 * 4)) = fmaxf(ud[pa][pb][e], 0.f);
+          *reinterpret_cast<float*>(t1 + uo_base + (pa * ROWC + (2 * e + pb) * LDC) * 4) = fmaxf(ud[pa][pb][e], 0.f);
     __builtin_amdgcn_wave_barrier();
 
-    // ---- conv6: 4 M-blocks x 9 taps x 12 k-steps of 16x16x4, two M-blocks interleaved ----------
+    if constexpr (H16) {
+    // ---- conv6, H16: 4 M-blocks x 9 taps x 3 k-steps of 16x16x16 ---------------------------------
     f32x4 acc[4];
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) acc[mb] = f32x4{bias6, bias6, bias6, bias6};
-    if constexpr (H16) {
+    {
       // (four independent accumulators per tap: a 16x16x16 MFMA is 4 passes, its result is needed again 3 MFMAs later)
       // and the 12 A reads of tap + 1 are issued as one group before the 12 MFMAs of tap: left to itself the compiler
       // emits read - wait - MFMA triples, 108 LDS latencies per window
@@ -394,30 +455,97 @@ __global__ __launch_bounds__(256, 1) void oflow_tail2_kernel(FusedArgs a, const 
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-#pragma unroll
-    for (int mp = 0; mp < (H16 ? 0 : 2); ++mp) {
-#pragma unroll
-      for (int tap = 0; tap < 9; ++tap) {
-        const int toff = ((tap / 3) * 10 + (tap % 3)) * (LD1 * 4);
-        f32x4 af[2][3];
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int s = 0; s < 3; ++s)
-            af[m][s] = *reinterpret_cast<const f32x4*>(t1 + a_base + (mp * 2 + m) * (2 * LD1 * 4) + toff + s * 16);
-#pragma unroll
-        for (int j = 0; j < 12; ++j)
-#pragma unroll
-          for (int m = 0; m < 2; ++m)
-            acc[mp * 2 + m] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[m][j >> 2][j & 3], w6r[tap * 12 + j], acc[mp * 2 + m], 0, 0, 0);
-      }
-    }
     // ---- ReLU, conv6 image -------------------------------------------------------------------
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
       for (int e = 0; e < 4; ++e)
         *reinterpret_cast<float*>(t2 + o_base + ((e >> 1) * ROW2 + (2 * mb + (e & 1)) * LD2) * 4) = fmaxf(acc[mb][e], 0.f);
+    } else {
+    // ---- conv6, fp32, by F(2x2,3x3): the 8x8 cells are 16 tiles of 2x2 = ONE 16-row M-block.  Per transform position
+    // (i, l) one 16 tiles x 16 channels product over K = 48: 16 positions x 12 k-steps = 192 MFMAs of 16x16x4 instead of
+    // the 4 x 9 x 12 = 432 of the nine-tap form, 16 independent accumulators.  Lane (tile, kq) reads its tile's 4x4 patch
+    // one channel quad at a time (16 ds_read_b128), forms V = B^T d B on the four channels in place (B^T = [1 0 -1 0;
+    // 0 1 1 0; 0 -1 1 0; 0 1 0 -1]: 32 additions per channel) and feeds V[pos][c] straight to the MFMAs of k-step 4 s + c:
+    // nothing goes through LDS again.  The transform of quad s + 1 is slotted under the MFMAs of quad s (the sched_group
+    // masks below: 0x8 MFMA, 0x2 VALU); only quad 0's reads and transform are exposed.  The MFMA phase is no longer free
+    // of VALU work: per MFMA (32 cycles of the pipe) two transform operations issue beside it.
+    f32x4 acc[16];
+#pragma unroll
+    for (int pos = 0; pos < 16; ++pos) acc[pos] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 da[16], db[16];
+    auto reads = [&](int s, f32x4 (&d)[16]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int c = 0; c < 16; ++c)
+        d[c] = *reinterpret_cast<const f32x4*>(t1 + a_base + ((c >> 2) * ROWC + (c & 3) * LDC) * 4 + s * 16);
+    };
+    auto bt4 = [](f32x4& d0, f32x4& d1, f32x4& d2, f32x4& d3) __attribute__((always_inline)) {
+      const f32x4 r0 = d0 - d2, r1 = d1 + d2, r2 = d2 - d1, r3 = d1 - d3;
+      d0 = r0; d1 = r1; d2 = r2; d3 = r3;
+    };
+    // a quarter of the transform: B^T d along the patch rows (parts 0, 1: two patch columns each), then (.) B along its
+    // columns (parts 2, 3: two rows each)
+    auto xpart = [&](int part, f32x4 (&d)[16]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int j = (part & 1) * 2 + h;
+        if (part < 2) bt4(d[j], d[4 + j], d[8 + j], d[12 + j]);
+        else bt4(d[4 * j], d[4 * j + 1], d[4 * j + 2], d[4 * j + 3]);
+      }
+    };
+    // one channel quad: k-step by k-step the 16 positions' MFMAs (16 different accumulators: a result is needed again 16
+    // MFMAs later), and under each k-step a quarter of the next quad's transform, two VALU operations per MFMA.  The
+    // barriers keep the k-steps apart: left free, the scheduler strings an accumulator's four MFMAs together.
+    auto quad = [&](int s, const f32x4 (&v)[16], f32x4 (&dn)[16], bool next) __attribute__((always_inline)) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+#pragma unroll
+        for (int pos = 0; pos < 16; ++pos)
+          acc[pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[pos][c], u6[pos][s * 4 + c], acc[pos], 0, 0, 0);
+        if (next) {
+          xpart(c, dn);
+#pragma unroll
+          for (int g = 0; g < 16; ++g) {
+            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x2, 2, 0);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    reads(0, da);
+#pragma unroll
+    for (int part = 0; part < 4; ++part) xpart(part, da);
+    reads(1, db);
+    __builtin_amdgcn_sched_barrier(0);
+    quad(0, da, db, true);
+    reads(2, da);
+    __builtin_amdgcn_sched_barrier(0);
+    quad(1, db, da, true);
+    // (pinned: the loads below branch on the window count, and what is used only after them sinks behind that branch)
+#pragma unroll
+    for (int c = 0; c < 16; ++c) asm volatile("" : "+v"(da[c]));
+    issue_next();
+    __builtin_amdgcn_sched_barrier(0);
+    quad(2, da, db, false);
+    // ---- Y = A^T M A per tile (A^T = [1 1 1 0; 0 1 -1 -1]), on the four tiles of a lane at once; bias, ReLU, conv6 image
+    f32x4 tr[2][4];
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+      tr[0][l] = (acc[l] + acc[4 + l]) + acc[8 + l];
+      tr[1][l] = (acc[4 + l] - acc[8 + l]) - acc[12 + l];
+    }
+#pragma unroll
+    for (int ya = 0; ya < 2; ++ya) {
+      const f32x4 y0 = (tr[ya][0] + tr[ya][1]) + tr[ya][2];
+      const f32x4 y1 = (tr[ya][1] - tr[ya][2]) - tr[ya][3];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        *reinterpret_cast<float*>(t2 + o_base + (ya * ROW2 + (2 * e + 0) * LD2) * 4) = fmaxf(y0[e] + bias6, 0.f);
+        *reinterpret_cast<float*>(t2 + o_base + (ya * ROW2 + (2 * e + 1) * LD2) * 4) = fmaxf(y1[e] + bias6, 0.f);
+      }
+    }
+    }
     __builtin_amdgcn_wave_barrier();
 
     // ---- prediction conv: one window cell per lane, wave-uniform weights -------------------------
@@ -435,8 +563,10 @@ __global__ __launch_bounds__(256, 1) void oflow_tail2_kernel(FusedArgs a, const 
     for (int q = 0; q < C2 / 4; ++q) lq[q] = 0.f;
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
-      // (wave-uniform scalar loads; hipcc hoists the 144 of them out of the window loop and spills the SGPRs to VGPR
-      //  lanes: 156 v_readlane per window.  Per-lane copies end up in AGPRs and cost a v_accvgpr_read each: no better.)
+      // (wave-uniform scalar loads.  H16: hipcc hoists the 144 of them out of the window loop and spills the SGPRs to VGPR
+      //  lanes: 156 v_readlane per window; per-lane copies end up in AGPRs and cost a v_accvgpr_read each: no better.
+      //  fp32: with U in the accumulation registers they stay in the loop, nine s_load_dwordx16 per window from the scalar
+      //  cache and no spill; a copy in LDS read by uniform-address ds_read_b128 was 6 % slower: tools/experiments/README.md)
       const float* wt = wp + tap * C2;
 #pragma unroll
       for (int q = 0; q < C2 / 4; ++q) {
@@ -522,11 +652,12 @@ int launch_tail2(const char* who, const float* T, const float* Gp, int N, int H,
   int rc = fill_args(a, T, Gp, N, H, W, relu0, who);
   if (rc != KFN_OK) return rc;
   static std::atomic<uint64_t> attr_done{0};   // (one per instantiation)
-  rc = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(oflow_tail2_kernel<H16>), 4 * TAIL_WAVE_BYTES, attr_done);
+  constexpr int lds_bytes = H16 ? 4 * TAIL_WAVE_BYTES : TAILW_BYTES;
+  rc = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(oflow_tail2_kernel<H16>), lds_bytes, attr_done);
   if (rc != KFN_OK) return rc;
   int blocks = kfn::ceil_div(a.P, 4);
   if (blocks > 256) blocks = 256;      // one workgroup of four waves per CU
-  hipLaunchKernelGGL(oflow_tail2_kernel<H16>, dim3(blocks), dim3(256), 4 * TAIL_WAVE_BYTES, (hipStream_t)stream, a, x5,
+  hipLaunchKernelGGL(oflow_tail2_kernel<H16>, dim3(blocks), dim3(256), lds_bytes, (hipStream_t)stream, a, x5,
                      wu_packed, bu, w6_packed, b6, wp, bp, flow_xy, opt_logits);
   KFN_LAUNCH_CHECK("oflow_tail2_kernel");
   return KFN_OK;

@@ -1294,8 +1294,11 @@ class OFlowTail2Op(Op):
         return 2.0 * n * h * w * (16 * 9 * 32 * 16 + 64 * 9 * (48 * 16 + 16))
 
     def mfma_flops(self):
+        """What the MFMAs execute: upconv0's nine (class, tap) products of 16 x 16 over K = 32; conv6 in fp32 by
+        F(2x2,3x3) -- 16 transform positions of 16 tiles x 16 channels over K = 48 -- and in fp16 at its nine taps."""
         n, h, w, _ = self.t.shape
-        return 2.0 * n * h * w * (9 * 16 * 32 * 16 + 64 * 9 * 48 * 16)
+        conv6 = 64 * 9 * 48 * 16 if self.operands_f16 else 16 * 16 * 48 * 16
+        return 2.0 * n * h * w * (9 * 16 * 32 * 16 + conv6)
 
     def launch(self, lib, stream):
         n, h, w, c9 = self.t.shape
