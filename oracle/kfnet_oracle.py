@@ -7,7 +7,10 @@ ships no tests, golden vectors, weights or sample data.  This 
 therefore restates the algorithm from the cited reference lines + documented TF-1.x op
 semantics, and is pinned only by (1) the analytic known-answer tests
 in tests/test_oracle_kat.py, (2) agreement with the independent torch-CPU restatement
-in oracle/kfnet_oracle_torch.py, (3) the committed fixtures in tests/golden/.
+in oracle/kfnet_oracle_torch.py, (3) the committed fixtures in tests/golden/, (4) the reference's
+own model code run over the eager stand-in of oracle/tf_standin (oracle/run_reference.py,
+tests/golden/ref_*.npz, tests/test_reference_pins.py): TensorFlow's op semantics as that stand-in
+reads them are what stays unpinned.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this.
 
@@ -235,7 +238,10 @@ def get_pixel_map(h, w, dtype=np.float64):
 def bilinear_sampler(imgs, coords):
     """tools/util.py:3-94: clamped corner indices AND weights computed
     from the clamped corners; add_n order w00*im00 + w01*im01 + w10*im10 + w11*im11.
-    imgs [1,H,W,C], coords [1,h,w,2] (x,y) -> [1,h,w,C]."""
+    imgs [1,H,W,C], coords [1,h,w,2] (x,y) -> [1,h,w,C].  Batch 1 ONLY: the reference's sampler adds b H W to the flat
+    index of batch element b; this one has no such offset (the eval loop never needs it) and refuses a batch."""
+    if imgs.shape[0] != 1 or coords.shape[0] != 1:
+        raise ValueError('bilinear_sampler restates the reference at batch 1 only, got %s and %s' % (imgs.shape, coords.shape))
     dt = imgs.dtype
     _, H, Wd, C = imgs.shape
     x = coords[..., 0:1].astype(dt)

@@ -164,9 +164,11 @@ def oflownet(vol, W, chunk=1200):
 
 
 def bilinear_sampler(imgs, coords):
-    """tools/util.py:36-93 in fp32 torch."""
+    """tools/util.py:36-93 in fp32 torch, at batch 1 only (no per-element offset of the flat index)."""
     imgs = _t(imgs).float()
     coords = _t(coords).float()
+    if imgs.shape[0] != 1 or coords.shape[0] != 1:
+        raise ValueError('bilinear_sampler restates the reference at batch 1 only')
     _, H, Wd, C = imgs.shape
     x = coords[..., 0:1]
     y = coords[..., 1:2]

@@ -1,6 +1,7 @@
 """Known-answer tests for the CPU oracle, derived analytically from the cited reference
-code.  These are the only pins the oracle has: the reference cannot
-run here (no TensorFlow) and ships no golden vectors."""
+code.  The reference cannot run here under TensorFlow and ships no golden
+vectors; tests/test_reference_pins.py holds the oracle to the reference's model code run over
+an eager stand-in, these tests to what the cited lines say."""
 import os
 
 import numpy as np
