@@ -65,7 +65,8 @@ extern "C" {
  * kfn_track_raycast, kfn_track_icp_sums, kfn_track_update and kfn_track_commit (the camera tracked against that volume), and kfn_reloc_encode,
  * kfn_reloc_search, kfn_reloc_seed and kfn_reloc_settle (a lost tracker relocalised from fern-coded keyframes), and
  * kfn_kalman_scan_plan (which of the scan's instantiations a grid launches; host only), and kfn_conv2d_grad_weights_plan
- * (tiles and runs of pixels of a weight-gradient launch; host only). */
+ * (tiles and runs of pixels of a weight-gradient launch; host only), and kfn_winograd_launch_plan (kfn_wino_plan: what a
+ * Winograd entry point launches for a descriptor, the struct its launcher launches from; host only). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -338,11 +339,52 @@ int kfn_conv2d_winograd_s2_splitk(const kfn_conv_desc* desc, const float* x, con
  * below 1 GiB, fp32 operands and activations, no fused head epilogue (kfn_winograd_f43_supported() == 1);
  * KFN_ERR_UNSUPPORTED otherwise. */
 int kfn_winograd_f43_supported(const kfn_conv_desc* desc);
-/* Dynamic LDS (bytes per workgroup) of the kernel the matching Winograd entry point launches for `desc`: stride 2 ->
- * kfn_conv2d_winograd_s2 (wino_form AUTO / KFN_WINO_FORM_S2_EIGHT_WAVE), stride 1 with wino_form KFN_WINO_FORM_F43_* ->
- * kfn_conv2d_winograd_f43, any other stride-1 descriptor -> the form kfn_conv2d_winograd_fused routes it to.  A host
- * compares it with kfn_device_info()'s lds_bytes_per_cu and routes around kernels the device cannot hold (147-157 KB for
- * the F(4x4,3x3) and four-wave F(2x2,3x3) forms) instead of failing in the first launch.  No device access.  (ABI 6) */
+/* What a Winograd entry point will launch for `desc` -- the launch plan.  Every launcher above computes exactly this struct
+ * first (one function per kernel family, csrc/kfn_wino*.hip) and launches from it; the *_supported functions answer "the plan
+ * succeeds", kfn_winograd_lds_bytes answers its lds_bytes: nothing states a condition a second time.
+ *   family     stride 2 -> kfn_conv2d_winograd_s2; stride 1 with wino_form KFN_WINO_FORM_F43_* -> kfn_conv2d_winograd_f43; any
+ *              other stride-1 descriptor -> kfn_conv2d_winograd_fused.
+ *   k_split    0: the plain entry point.  >= 1: the family's split-K entry point with that split (kfn_conv2d_winograd_f43_splitk /
+ *              _s2_splitk; the fused family has none); k_split == 1 is the unsplit eight-wave launch.
+ *   cu_count   compute units of the device (kfn_device_info); <= 0: 256.  Only the F(4,2) form reads it (its persistent kernel
+ *              runs launches of at least two workgroups per CU).
+ *   y_low_bits the low four bits of the output address (0 = 16-byte aligned) -- the one pointer fact that selects a path (the
+ *              16-byte or the dword store epilogue) or, for the kernels without a dword epilogue, refuses the layer.  For a
+ *              tensor window: 4 * (channel offset % 4).
+ * plan->struct_size = sizeof(kfn_wino_plan) as the caller compiled it; the library writes that many bytes.  Returns KFN_OK, or
+ * the launcher's own refusal (code and kfn_last_error text).  What a launcher checks beyond the plan is the alignment of the
+ * other pointers (x, the packed weights, bias, the split-K workspace).  Host only: no device access. */
+#define KFN_WINO_KERNEL_WINO2_WIDE 1   /* wino2_kernel<true>: 16-byte stores */
+#define KFN_WINO_KERNEL_WINO2_DWORD 2  /* wino2_kernel<false> */
+#define KFN_WINO_KERNEL_WINO3 3        /* wino3_kernel<false> */
+#define KFN_WINO_KERNEL_WINO3_F16 4    /* wino3_kernel<true>: fp16 operands */
+#define KFN_WINO_KERNEL_WINO3_PAIR 5   /* wino3_pair_kernel */
+#define KFN_WINO_KERNEL_WINO4 6        /* wino4_kernel */
+#define KFN_WINO_KERNEL_WINO4B 7       /* wino4b_kernel */
+#define KFN_WINO_KERNEL_S2 8           /* wino_s2_kernel<false> */
+#define KFN_WINO_KERNEL_S2_F16 9       /* wino_s2_kernel<true>: fp16 operands */
+#define KFN_WINO_KERNEL_S2B 10         /* wino_s2b_kernel */
+#define KFN_WINO_KERNEL_S2C 11         /* wino_s2c_kernel */
+#define KFN_WINO_KERNEL_S2C_PERSISTENT 12 /* wino_s2c_pkernel */
+typedef struct kfn_wino_plan {
+  int32_t struct_size;
+  int32_t kernel;              /* KFN_WINO_KERNEL_* */
+  int32_t threads;             /* per workgroup */
+  int32_t lds_bytes;           /* dynamic LDS per workgroup */
+  int32_t workgroups;          /* launched: tiles_m * tiles_n * k_split, or cu_count for the persistent kernel */
+  int32_t tiles_m, tiles_n;    /* tile blocks (the batch's tile rows packed) x output-channel groups */
+  int32_t tiles_per_block;     /* Winograd tiles of a tile block: what tiles_m pads the image to */
+  int32_t channels_per_group;  /* output channels of a workgroup: what tiles_n pads Cout to */
+  int32_t n_group;             /* channel groups of one tile block adjacent in the grid (1 = tile blocks fastest) */
+  int32_t wide_store;          /* 1: 16-byte store epilogue, 0: the dword one */
+  int32_t k_split;             /* copies of the tile grid (1 = unsplit) */
+  int32_t ss_per_split;        /* super-steps of 16 input channels per copy (fused family: of its own super-step) */
+} kfn_wino_plan;
+int kfn_winograd_launch_plan(const kfn_conv_desc* desc, int k_split, int cu_count, unsigned y_low_bits, kfn_wino_plan* plan);
+/* Dynamic LDS (bytes per workgroup) of the kernel the matching Winograd entry point launches for `desc`: the lds_bytes of
+ * kfn_winograd_launch_plan(desc, 0, 0, 0, ..).  A host compares it with kfn_device_info()'s lds_bytes_per_cu and routes around
+ * kernels the device cannot hold (147-157 KB for the F(4x4,3x3) and four-wave F(2x2,3x3) forms) instead of failing in the
+ * first launch.  No device access.  (ABI 6) */
 int kfn_winograd_lds_bytes(const kfn_conv_desc* desc, int* bytes);
 /* Split-K form of the eight-wave kernel for launches that would leave the chip idle (BASELINE configs[1], one 480x640 frame:
  * SCoordNet conv4b / conv5 / conv6 at batch 1 are 160 / 80 / 40 workgroups on 256 CUs, cnn_wrapper/SCoordNet.py:27-30): the

@@ -57,6 +57,31 @@ class ConvDesc(SizedStructure):
         'x_dtype', 'y_dtype', 'k_step', 'weights_path', 'x_layout', 'y_layout')]
 
 
+class WinoPlan(SizedStructure):
+    """kfn_wino_plan (include/kfnet_hip.h): what a Winograd entry point launches for a descriptor.  `kernel` is a
+    KFN_WINO_KERNEL_* value, WINO_KERNEL_NAMES[kernel] the name the ops report for it (the fp32 / 16-byte-store instantiations
+    without their template argument)."""
+    _fields_ = [(n, C.c_int32) for n in (
+        'struct_size', 'kernel', 'threads', 'lds_bytes', 'workgroups', 'tiles_m', 'tiles_n', 'tiles_per_block',
+        'channels_per_group', 'n_group', 'wide_store', 'k_split', 'ss_per_split')]
+
+
+(WINO_KERNEL_WINO2_WIDE, WINO_KERNEL_WINO2_DWORD, WINO_KERNEL_WINO3, WINO_KERNEL_WINO3_F16, WINO_KERNEL_WINO3_PAIR, WINO_KERNEL_WINO4,
+ WINO_KERNEL_WINO4B, WINO_KERNEL_S2, WINO_KERNEL_S2_F16, WINO_KERNEL_S2B, WINO_KERNEL_S2C, WINO_KERNEL_S2C_PERSISTENT) = range(1, 13)
+WINO_KERNEL_NAMES = (None, 'wino2_kernel', 'wino2_kernel', 'wino3_kernel', 'wino3_kernel<true>', 'wino3_pair_kernel',
+                     'wino4_kernel', 'wino4b_kernel', 'wino_s2_kernel', 'wino_s2_kernel<true>', 'wino_s2b_kernel',
+                     'wino_s2c_kernel', 'wino_s2c_pkernel')
+
+
+def winograd_launch_plan(desc, k_split=0, cu_count=0, y_low_bits=0):
+    """kfn_winograd_launch_plan: the WinoPlan of the launch the Winograd entry points make for `desc` (k_split 0: the plain
+    one, >= 1: the split-K one), or None when they refuse it (kfn_last_error says why)."""
+    plan = WinoPlan()
+    if load().kfn_winograd_launch_plan(C.byref(desc), k_split, cu_count, y_low_bits, C.byref(plan)) != KFN_OK:
+        return None
+    return plan
+
+
 class KalmanDesc(C.Structure):
     _fields_ = [('S', C.c_int32), ('T', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
                 ('t0', C.c_int32), ('reset_period', C.c_int32),
@@ -251,6 +276,7 @@ SYMBOLS = {
     'kfn_conv2d_winograd_f43': (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp]),
     'kfn_winograd_f43_supported': (_i, [C.POINTER(ConvDesc)]),
     'kfn_winograd_lds_bytes': (_i, [C.POINTER(ConvDesc), C.POINTER(_i)]),
+    'kfn_winograd_launch_plan': (_i, [C.POINTER(ConvDesc), _i, _i, C.c_uint, C.POINTER(WinoPlan)]),
     'kfn_winograd_f43_splitk_workspace_bytes': (_i, [C.POINTER(ConvDesc), _i, C.POINTER(_sz)]),
     'kfn_conv2d_winograd_f43_splitk': (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     'kfn_conv3x3_c64_f16': (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp]),

@@ -72,14 +72,30 @@ inline int set_max_dynamic_lds(const void* kernel, int bytes, std::atomic<uint64
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-// Dynamic LDS (bytes per workgroup) of the kernels behind the Winograd entry points -- what kfn_winograd_lds_bytes()
-// answers; each is defined beside the kernel it describes.  < 0: no such form in that file.
-int wino_f43_lds_bytes(int wino_form);     // kfn_wino4.hip: KFN_WINO_FORM_F43_FOUR_WAVE / _EIGHT_WAVE
-int wino_s2_lds_bytes(int wino_form, int operand_dtype);   // kfn_wino_s2.hip: AUTO (four waves) / KFN_WINO_FORM_S2_EIGHT_WAVE
-int wino_s2c_lds_bytes();                  // kfn_wino_s2c.hip: KFN_WINO_FORM_S2_F42
-int wino_s2c_supported(const kfn_conv_desc* d);   // (normalised descriptor)
+// The launch plan of a Winograd kernel family (kfn_wino_plan, include/kfnet_hip.h): every condition that needs no pointer,
+// with the launcher's message, and everything the launch derives from the shape -- which kernel, the grid, the LDS, n_group,
+// the store path.  The family's launchers launch from it; kfn_winograd_*_supported, kfn_winograd_lds_bytes and
+// kfn_winograd_launch_plan report it.  `d` normalised; k_split 0 = the plain entry point, >= 1 = the split-K entry point;
+// cu_count > 0; y_low4 = the output address & 15.
+int wino_fused_plan(const kfn_conv_desc* d, unsigned y_low4, kfn_wino_plan* p);                       // kfn_wino3.hip
+int wino_f43_plan(const kfn_conv_desc* d, int k_split, unsigned y_low4, kfn_wino_plan* p);            // kfn_wino4.hip
+int wino_s2_plan(const kfn_conv_desc* d, int k_split, int cu_count, unsigned y_low4, kfn_wino_plan* p);   // kfn_wino_s2.hip
+int wino_s2c_plan(const kfn_conv_desc* d, int cu_count, unsigned y_low4, kfn_wino_plan* p);           // kfn_wino_s2c.hip
+// ... of whichever family takes `d` (kfn_winograd_launch_plan's rule, kfn_wino4.hip)
+int wino_plan(const kfn_conv_desc* d, int k_split, int cu_count, unsigned y_low4, kfn_wino_plan* p);
+inline unsigned low4(const void* ptr) { return (unsigned)(reinterpret_cast<uintptr_t>(ptr) & 15); }
+// n_group as kfn_conv_desc.wino_order asks for it: `auto_groups` for AUTO, 1 / tiles_n for M_FAST / N_FAST, n for
+// KFN_WINO_ORDER_GROUPS(n); a request that does not divide tiles_n becomes `fallback`
+inline int wino_n_group(int wino_order, int tiles_n, int auto_groups, int fallback) {
+  int ng = auto_groups;
+  if (wino_order == KFN_WINO_ORDER_N_FAST) ng = tiles_n;
+  else if (wino_order == KFN_WINO_ORDER_M_FAST) ng = 1;
+  else if (wino_order >= KFN_WINO_ORDER_GROUPS(1)) ng = wino_order - KFN_WINO_ORDER_GROUPS(0);
+  return (ng < 1 || ng > tiles_n || tiles_n % ng != 0) ? fallback : ng;
+}
 int launch_wino_s2c(const kfn_conv_desc* d, const float* x, const void* u_packed, const float* bias, float* y, void* stream);
-int wino_fused_lds_bytes(const kfn_conv_desc* d);   // kfn_wino3.hip: the form kfn_conv2d_winograd_fused routes `d` to
+int launch_wino3(const kfn_conv_desc* d, const kfn_wino_plan& p, const float* x, const void* u2_packed, const float* bias, float* y,
+                 hipStream_t stream);   // kfn_wino3.hip: the four- and two-wave forms of kfn_conv2d_winograd_fused
 // y[pix][c] = relu(bias[c] + sum_s ws[s][pix][c]), s ascending (kfn_wino4.hip): the second launch of the split-K forms
 int launch_splitk_reduce(const float* ws, int k_split, long pixels, const float* bias, int relu, float* y, int Cout, int ldy,
                          hipStream_t stream);

@@ -442,96 +442,44 @@ __global__ __launch_bounds__(64, 1) void wino2_kernel(Wino2Args p) {
 
 }  // namespace
 
-namespace kfn {
-int launch_wino3(const kfn_conv_desc* d, const float* x, const void* u2_packed, const float* bias, float* y,
-                 hipStream_t stream);   // kfn_wino3.hip: four waves share one input transform (fp32 or fp16 operands)
-}
+static_assert(BW == 8 && BH == 4 && KS == 16, "kfn::wino_fused_plan (kfn_wino3.hip) plans this kernel's tile block and stage too");
 
-// Can the single-kernel path take this layer?  (host-side routing; no device access)
+// Can the single-kernel path take this layer?  = "kfn_conv2d_winograd_fused's plan succeeds for a 16-byte aligned output"
+// (an unaligned one only selects the dword store path).  Host only; no device access.
 extern "C" int kfn_winograd_fused_supported(const kfn_conv_desc* d) {
   kfn_conv_desc d_full;
-  if (!d || kfn::conv_desc_in(d, &d_full, "kfn_winograd_fused_supported") != KFN_OK) return 0;
-  d = &d_full;
-  if (d->x_dtype != KFN_ACT_F32 || d->y_dtype != KFN_ACT_F32) return 0;
-  if (d->kh != 3 || d->kw != 3 || d->stride != 1 || d->transposed) return 0;
-  if (d->Cin <= 0 || d->Cin % KS != 0) return 0;
-  if ((d->H + 1) / 2 < BH) return 0;   // a 4-row tile block may straddle at most two images
-  if (d->epilogue != KFN_EPI_NONE) return 0;
-  if (d->cout_pad % 32 != 0) return 0;
-  // fp16 operands (BASELINE config 5): the four-wave form only
-  if (d->operand_dtype == KFN_OPERAND_F16) return d->Cout >= 128 && d->Cin % 64 == 0;   // two super-steps per loop trip
-  if (d->operand_dtype != KFN_OPERAND_F32) return 0;
-  return 1;
+  kfn_wino_plan p;
+  return d && kfn::conv_desc_in(d, &d_full, "kfn_winograd_fused_supported") == KFN_OK && kfn::wino_fused_plan(&d_full, 0, &p) == KFN_OK;
 }
 
 extern "C" int kfn_conv2d_winograd_fused(const kfn_conv_desc* d, const float* x, const void* u2_packed,
                                          const float* bias, float* y, void* stream) {
   KFN_REQUIRE(d && x && u2_packed && y, "kfn_conv2d_winograd_fused: null argument");
   KFN_CONV_DESC_IN(d, "kfn_conv2d_winograd_fused");
-  KFN_REQUIRE(d->x_dtype == KFN_ACT_F32 && d->y_dtype == KFN_ACT_F32,
-              "kfn_conv2d_winograd_fused: fp32 activations in memory only (x_dtype / y_dtype = KFN_ACT_F16 is implemented by kfn_conv2d_nhwc)");
-  KFN_REQUIRE(d->kh == 3 && d->kw == 3 && d->stride == 1 && !d->transposed,
-              "kfn_conv2d_winograd_fused: only 3x3 stride-1 SAME convolutions");
-  KFN_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0, "kfn_conv2d_winograd_fused: bad shape %dx%dx%d", d->N, d->H, d->W);
-  if (d->Cin <= 0 || d->Cin % KS != 0)
-    return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_fused: Cin=%d must be a multiple of %d", d->Cin, KS);
-  if ((d->H + 1) / 2 < BH)
-    return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_fused: H=%d is below %d rows", d->H, 2 * BH - 1);
-  KFN_REQUIRE(d->ldx >= d->Cin && d->ldx % 4 == 0 && d->Cout > 0 && d->ldy >= d->Cout &&
-                  d->cout_pad >= d->Cout && d->cout_pad % 32 == 0,
-              "kfn_conv2d_winograd_fused: bad strides / channel counts");
-  KFN_REQUIRE(d->epilogue == KFN_EPI_NONE && (d->operand_dtype == KFN_OPERAND_F32 || d->operand_dtype == KFN_OPERAND_F16),
-              "kfn_conv2d_winograd_fused: fp32 or fp16 operands, no fused head epilogue");
-  const bool h16 = d->operand_dtype == KFN_OPERAND_F16;
-  if (h16 && !(d->Cout >= 128 && d->Cin % 64 == 0))
-    return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_fused: fp16 operands need Cout >= 128 and Cin %% 64 == 0");
+  kfn_wino_plan p;
+  int rc = kfn::wino_fused_plan(d, kfn::low4(y), &p);
+  if (rc != KFN_OK) return rc;
   KFN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(u2_packed)) & 15) == 0,
               "kfn_conv2d_winograd_fused: buffers must be 16-byte aligned");
-  {
-    // >= 128 output channels and whole 32-channel super-steps: the 4-wave form (one transform per 128 output
-    // channels, input read Cout/128 times); kfn_conv_desc.wino_form = KFN_WINO_FORM_ONE_WAVE forces the one-wave form for A/B measurements
-    const int form = d->wino_form == KFN_WINO_FORM_ONE_WAVE ? 2 : 0;
-    const long img_b = (long)d->H * d->W * d->ldx * 4L;
-    if ((form != 2 || h16) && d->Cout >= 128 && d->Cin % 32 == 0 && 2 * img_b < (1L << 31) &&
-        2L * d->H * d->W * d->ldy * 4L < (1L << 31) && 16L * d->cout_pad * d->Cin * 4L < (1L << 31))
-      return kfn::launch_wino3(d, x, u2_packed, bias, y, (hipStream_t)stream);
-    // 33 .. 64 output channels (conv1b): the two-wave form of the same kernel -- one transform and one read of the
-    // input for all 64 channels, two workgroups per CU
-    if (form != 2 && !h16 && d->cout_pad == 64 && d->Cin % 16 == 0 && 2 * img_b < (1L << 30) &&
-        2L * d->H * d->W * d->ldy * 4L < (1L << 31) && 16L * d->cout_pad * d->Cin * 4L < (1L << 31))
-      return kfn::launch_wino3(d, x, u2_packed, bias, y, (hipStream_t)stream);
-    if (h16) return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_fused: image or kernel beyond 2 GiB of 32-bit offsets");
-  }
+  if (p.threads != 64) return kfn::launch_wino3(d, p, x, u2_packed, bias, y, (hipStream_t)stream);   // kfn_wino3.hip
   Wino2Args a;
   a.x = x; a.u2 = static_cast<const float*>(u2_packed); a.bias = bias; a.y = y;
   a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.ldx = d->ldx;
   a.Cout = d->Cout; a.cout_pad = d->cout_pad; a.ldy = d->ldy;
   a.Th = (d->H + 1) / 2; a.Tw = (d->W + 1) / 2;
-  const long vrows = (long)d->N * a.Th;
-  const long in_pix = (long)d->N * d->H * d->W;
-  const long x_bytes = ((in_pix - 1) * d->ldx + d->Cin) * 4L;
-  const long u_bytes = 16L * d->cout_pad * d->Cin * 4L;
-  const long img_bytes = (long)d->H * d->W * d->ldx * 4L;
-  KFN_REQUIRE(vrows < (1L << 30) && u_bytes < (1L << 31) && 2 * img_bytes < (1L << 31) &&
-                  2L * d->H * d->W * d->ldy * 4L < (1L << 31),
-              "kfn_conv2d_winograd_fused: tensor too large for 32-bit buffer addressing");
-  a.vrows = (int)vrows;
+  a.vrows = d->N * a.Th;
   a.bw = kfn::ceil_div(a.Tw, BW);
-  const long tiles_m = (long)a.bw * kfn::ceil_div(a.vrows, BH);
-  a.tiles_n = d->cout_pad / 32;
-  KFN_REQUIRE(tiles_m * a.tiles_n < (1L << 31), "kfn_conv2d_winograd_fused: grid too large");
-  a.tiles_m = (int)tiles_m;
+  a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n;
   a.relu = d->relu;
-  a.wide_store = (d->Cout % 4 == 0 && d->ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) ? 1 : 0;
-  a.x_bytes = (unsigned long long)x_bytes;
+  a.wide_store = p.wide_store;
+  const long in_pix = (long)d->N * d->H * d->W;
+  a.x_bytes = (unsigned long long)(((in_pix - 1) * d->ldx + d->Cin) * 4L);
   a.y_bytes = (unsigned long long)(((in_pix - 1) * d->ldy + d->Cout) * 4L);
-  a.u_bytes = (unsigned)u_bytes;
-  if (a.wide_store)
-    hipLaunchKernelGGL(wino2_kernel<true>, dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(64), 2 * BUF_BYTES,
-                       (hipStream_t)stream, a);
+  a.u_bytes = (unsigned)(16L * d->cout_pad * d->Cin * 4L);
+  if (p.kernel == KFN_WINO_KERNEL_WINO2_WIDE)
+    hipLaunchKernelGGL(wino2_kernel<true>, dim3((unsigned)p.workgroups), dim3(64), p.lds_bytes, (hipStream_t)stream, a);
   else
-    hipLaunchKernelGGL(wino2_kernel<false>, dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(64), 2 * BUF_BYTES,
-                       (hipStream_t)stream, a);
+    hipLaunchKernelGGL(wino2_kernel<false>, dim3((unsigned)p.workgroups), dim3(64), p.lds_bytes, (hipStream_t)stream, a);
   KFN_LAUNCH_CHECK("wino2_kernel");
   return KFN_OK;
 }

@@ -454,66 +454,102 @@ __global__ __launch_bounds__(128, 1) void wino3_pair_kernel(Wino3Args p) { wino3
 
 namespace kfn {
 
-// (the routing rule of kfn_conv2d_winograd_fused, kfn_wino2.hip, without its byte-range conditions)
-int wino_fused_lds_bytes(const kfn_conv_desc* d) {
+// The plan of kfn_conv2d_winograd_fused (kfn_wino2.hip): wino3_kernel -- >= 128 output channels in whole 32-channel
+// super-steps, one transform per 128 output channels, the input read Cout/128 times -- else wino3_pair_kernel -- 33 .. 64
+// output channels (conv1b): one transform and one read of the input for all 64 channels, two workgroups per CU -- else
+// wino2_kernel (kfn_conv_desc.wino_form = KFN_WINO_FORM_ONE_WAVE forces it on fp32 operands, for A/B measurements).
+int wino_fused_plan(const kfn_conv_desc* d, unsigned y_low4, kfn_wino_plan* p) {
+  KFN_REQUIRE(d->x_dtype == KFN_ACT_F32 && d->y_dtype == KFN_ACT_F32,
+              "kfn_conv2d_winograd_fused: fp32 activations in memory only (x_dtype / y_dtype = KFN_ACT_F16 is implemented by kfn_conv2d_nhwc)");
+  KFN_REQUIRE(d->kh == 3 && d->kw == 3 && d->stride == 1 && !d->transposed,
+              "kfn_conv2d_winograd_fused: only 3x3 stride-1 SAME convolutions");
+  KFN_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0, "kfn_conv2d_winograd_fused: bad shape %dx%dx%d", d->N, d->H, d->W);
+  if (d->Cin <= 0 || d->Cin % 16 != 0)
+    return fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_fused: Cin=%d must be a multiple of %d", d->Cin, 16);
+  if ((d->H + 1) / 2 < BH)   // a 4-row tile block may straddle at most two images
+    return fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_fused: H=%d is below %d rows", d->H, 2 * BH - 1);
+  KFN_REQUIRE(d->ldx >= d->Cin && d->ldx % 4 == 0 && d->Cout > 0 && d->ldy >= d->Cout &&
+                  d->cout_pad >= d->Cout && d->cout_pad % 32 == 0,
+              "kfn_conv2d_winograd_fused: bad strides / channel counts");
+  KFN_REQUIRE(d->epilogue == KFN_EPI_NONE && (d->operand_dtype == KFN_OPERAND_F32 || d->operand_dtype == KFN_OPERAND_F16),
+              "kfn_conv2d_winograd_fused: fp32 or fp16 operands, no fused head epilogue");
   const bool h16 = d->operand_dtype == KFN_OPERAND_F16;
-  const bool one = d->wino_form == KFN_WINO_FORM_ONE_WAVE;
-  if ((!one || h16) && d->Cout >= 128 && d->Cin % 32 == 0) return 8 * (h16 ? VLayout<true>::VBUF : VLayout<false>::VBUF);
-  if (!one && !h16 && d->cout_pad == 64 && d->Cin % 16 == 0) return 4 * VLayout<false>::VBUF;
-  return h16 ? -1 : WINO2_LDS_BYTES;
+  if (h16 && !(d->Cout >= 128 && d->Cin % 64 == 0))   // the four-wave form only, two super-steps per loop trip
+    return fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_fused: fp16 operands need Cout >= 128 and Cin %% 64 == 0");
+  const bool one = d->wino_form == KFN_WINO_FORM_ONE_WAVE && !h16;
+  const long two_img = 2L * d->H * d->W * d->ldx * 4L;
+  const bool fits = two_img < (1L << 31) && 2L * d->H * d->W * d->ldy * 4L < (1L << 31) && 16L * d->cout_pad * d->Cin * 4L < (1L << 31);
+  const long vrows = (long)d->N * ((d->H + 1) / 2);
+  std::memset(p, 0, sizeof(*p));
+  p->wide_store = (d->Cout % 4 == 0 && d->ldy % 4 == 0 && y_low4 == 0) ? 1 : 0;
+  p->tiles_per_block = BW * BH;
+  p->k_split = 1;
+  if (!one && d->Cout >= 128 && d->Cin % 32 == 0 && fits) {
+    p->kernel = h16 ? KFN_WINO_KERNEL_WINO3_F16 : KFN_WINO_KERNEL_WINO3;
+    p->threads = 256; p->channels_per_group = 128; p->ss_per_split = d->Cin / 32;
+    p->lds_bytes = 8 * (h16 ? VLayout<true>::VBUF : VLayout<false>::VBUF);
+  } else if (!one && !h16 && d->cout_pad == 64 && fits && two_img < (1L << 30)) {
+    // (per-lane patch offsets carry their out-of-image marks in bits 30 and 31: two images stay below 1 GiB)
+    p->kernel = KFN_WINO_KERNEL_WINO3_PAIR;
+    p->threads = 128; p->channels_per_group = 64; p->ss_per_split = d->Cin / 16;
+    p->lds_bytes = 4 * VLayout<false>::VBUF;
+  } else {
+    if (h16) return fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_fused: image or kernel beyond 2 GiB of 32-bit offsets");
+    KFN_REQUIRE(vrows < (1L << 30) && fits, "kfn_conv2d_winograd_fused: tensor too large for 32-bit buffer addressing");
+    p->kernel = p->wide_store ? KFN_WINO_KERNEL_WINO2_WIDE : KFN_WINO_KERNEL_WINO2_DWORD;
+    p->threads = 64; p->channels_per_group = 32; p->ss_per_split = d->Cin / 16;
+    p->lds_bytes = WINO2_LDS_BYTES;
+  }
+  // (the batch-wide row count: a very large N must not overflow vrows and the img0 / ty0 arithmetic derived from it)
+  KFN_REQUIRE(vrows < (1L << 30), "kfn_conv2d_winograd_fused: N*ceil(H/2) = %ld tile rows exceed 32-bit addressing", vrows);
+  const long tiles_m = (long)ceil_div((d->W + 1) / 2, BW) * ceil_div((int)vrows, BH);
+  p->tiles_n = ceil_div(d->cout_pad, p->channels_per_group);
+  KFN_REQUIRE(tiles_m * p->tiles_n < (1L << 31), "kfn_conv2d_winograd_fused: grid too large");
+  p->tiles_m = (int)tiles_m;
+  p->workgroups = p->tiles_m * p->tiles_n;
+  // wino3_kernel: the channel groups of a tile block adjacent (N fastest) or the tile blocks fastest; the other two have one order
+  const bool n_fast = d->wino_order == KFN_WINO_ORDER_N_FAST || (d->wino_order != KFN_WINO_ORDER_M_FAST && W3_DEFAULT_N_FAST);
+  p->n_group = (p->threads == 256 && n_fast) ? p->tiles_n : 1;
+  return KFN_OK;
 }
 
-// Launch of the 4-wave form (Cin % 32 == 0, Cout >= 128) or the two-wave form (cout_pad == 64, Cin % 16 == 0) for
-// a descriptor kfn_conv2d_winograd_fused has already validated.  Called from kfn_wino2.hip.
-int launch_wino3(const kfn_conv_desc* d, const float* x, const void* u2_packed, const float* bias, float* y,
+// Launch of the 4-wave or the two-wave form from kfn_conv2d_winograd_fused's plan.  Called from kfn_wino2.hip.
+int launch_wino3(const kfn_conv_desc* d, const kfn_wino_plan& p, const float* x, const void* u2_packed, const float* bias, float* y,
                  hipStream_t stream) {
-  const bool h16 = d->operand_dtype == KFN_OPERAND_F16;
+  const bool h16 = p.kernel == KFN_WINO_KERNEL_WINO3_F16;
   Wino3Args a;
   a.x = x; a.u2 = static_cast<const float*>(u2_packed); a.bias = bias; a.y = y;
   a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.ldx = d->ldx;
   a.Cout = d->Cout; a.cout_pad = d->cout_pad; a.ldy = d->ldy;
   a.Th = (d->H + 1) / 2; a.Tw = (d->W + 1) / 2;
-  const long vrows = (long)d->N * a.Th;
-  const long in_pix = (long)d->N * d->H * d->W;
-  // (the caller checked the per-image and weight byte ranges; the batch-wide row count is checked here so that a
-  // very large N cannot overflow vrows and the img0 / ty0 arithmetic derived from it)
-  KFN_REQUIRE(vrows < (1L << 30), "kfn_conv2d_winograd_fused: N*ceil(H/2) = %ld tile rows exceed 32-bit addressing", vrows);
-  a.vrows = (int)vrows;
+  a.vrows = d->N * a.Th;
   a.bw = ceil_div(a.Tw, BW);
-  const long tiles_m = (long)a.bw * ceil_div(a.vrows, BH);
-  const bool pair = !h16 && d->cout_pad == 64;          // the two-wave form: all of a layer's 33..64 output channels in one workgroup
-  a.tiles_n = ceil_div(d->cout_pad, pair ? 64 : 128);
-  KFN_REQUIRE(tiles_m * a.tiles_n < (1L << 31), "kfn_conv2d_winograd_fused: grid too large");
-  a.tiles_m = (int)tiles_m;
+  a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n;
   a.relu = d->relu;
-  a.n_fast = d->wino_order == KFN_WINO_ORDER_N_FAST ? 1 : (d->wino_order == KFN_WINO_ORDER_M_FAST ? 0 : W3_DEFAULT_N_FAST);
-  a.wide_store = (d->Cout % 4 == 0 && d->ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) ? 1 : 0;
+  a.n_fast = p.n_group > 1;
+  a.wide_store = p.wide_store;
+  const long in_pix = (long)d->N * d->H * d->W;
   a.x_bytes = (unsigned long long)(((in_pix - 1) * d->ldx + d->Cin) * 4L);
   a.y_bytes = (unsigned long long)(((in_pix - 1) * d->ldy + d->Cout) * 4L);
   a.u_bytes = (unsigned)(16L * d->cout_pad * d->Cin * (h16 ? 2L : 4L));
-  const dim3 grid((unsigned)(a.tiles_m * a.tiles_n));
-  if (pair) {
-    // per-lane patch offsets carry their out-of-image marks in bits 30 and 31: two images must stay below 1 GiB
-    KFN_REQUIRE(2L * d->H * d->W * d->ldx * 4L < (1L << 30), "kfn_conv2d_winograd_fused: image beyond 512 MiB in the two-wave form");
-    constexpr int lds = 4 * VLayout<false>::VBUF;
+  const dim3 grid((unsigned)p.workgroups), block((unsigned)p.threads);
+  if (p.kernel == KFN_WINO_KERNEL_WINO3_PAIR) {
     static std::atomic<uint64_t> attr_done2{0};
-    int rc = set_max_dynamic_lds(reinterpret_cast<const void*>(wino3_pair_kernel), lds, attr_done2);
+    int rc = set_max_dynamic_lds(reinterpret_cast<const void*>(wino3_pair_kernel), p.lds_bytes, attr_done2);
     if (rc != KFN_OK) return rc;
-    hipLaunchKernelGGL(wino3_pair_kernel, grid, dim3(128), lds, stream, a);
+    hipLaunchKernelGGL(wino3_pair_kernel, grid, block, p.lds_bytes, stream, a);
   } else if (h16) {
-    constexpr int lds = 8 * VLayout<true>::VBUF;
     static std::atomic<uint64_t> attr_done16{0};
-    int rc = set_max_dynamic_lds(reinterpret_cast<const void*>(wino3_kernel<true>), lds, attr_done16);
+    int rc = set_max_dynamic_lds(reinterpret_cast<const void*>(wino3_kernel<true>), p.lds_bytes, attr_done16);
     if (rc != KFN_OK) return rc;
-    hipLaunchKernelGGL(wino3_kernel<true>, grid, dim3(256), lds, stream, a);
+    hipLaunchKernelGGL(wino3_kernel<true>, grid, block, p.lds_bytes, stream, a);
   } else {
-    constexpr int lds = 8 * VLayout<false>::VBUF;
     static std::atomic<uint64_t> attr_done{0};
-    int rc = set_max_dynamic_lds(reinterpret_cast<const void*>(wino3_kernel<false>), lds, attr_done);
+    int rc = set_max_dynamic_lds(reinterpret_cast<const void*>(wino3_kernel<false>), p.lds_bytes, attr_done);
     if (rc != KFN_OK) return rc;
-    hipLaunchKernelGGL(wino3_kernel<false>, grid, dim3(256), lds, stream, a);
+    hipLaunchKernelGGL(wino3_kernel<false>, grid, block, p.lds_bytes, stream, a);
   }
-  KFN_LAUNCH_CHECK(pair ? "wino3_pair_kernel" : "wino3_kernel");
+  KFN_LAUNCH_CHECK(p.kernel == KFN_WINO_KERNEL_WINO3_PAIR ? "wino3_pair_kernel" : "wino3_kernel");
   return KFN_OK;
 }
 

@@ -812,62 +812,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const f32x4* __restr
 
 }  // namespace
 
-int kfn::wino_f43_lds_bytes(int wino_form) {
-  if (wino_form == KFN_WINO_FORM_F43_FOUR_WAVE) return LDS_V;
-  if (wino_form == KFN_WINO_FORM_F43_EIGHT_WAVE) return B_LDS;
-  return -1;
-}
-
-// Dynamic LDS per workgroup of the kernel a Winograd entry point launches for `desc` (stride 1: kfn_conv2d_winograd_f43
-// when wino_form names one of its two forms, else kfn_conv2d_winograd_fused's routing; stride 2: kfn_conv2d_winograd_s2),
-// so that a host can route around kernels a device's LDS cannot hold (kfn_device_info's lds_bytes_per_cu) instead of
-// failing in the first launch.  No device access.
-extern "C" int kfn_winograd_lds_bytes(const kfn_conv_desc* d, int* bytes) {
-  KFN_REQUIRE(d && bytes, "kfn_winograd_lds_bytes: null argument");
-  KFN_CONV_DESC_IN_LAYOUTS(d, "kfn_winograd_lds_bytes");
-  KFN_REQUIRE(d->kh == 3 && d->kw == 3 && (d->stride == 1 || d->stride == 2) && !d->transposed,
-              "kfn_winograd_lds_bytes: the Winograd kernels take 3x3 stride-1 / stride-2 convolutions only");
-  int b;
-  if (d->stride == 2) b = kfn::wino_s2_lds_bytes(d->wino_form, d->operand_dtype);
-  else if (d->wino_form == KFN_WINO_FORM_F43_FOUR_WAVE || d->wino_form == KFN_WINO_FORM_F43_EIGHT_WAVE) b = kfn::wino_f43_lds_bytes(d->wino_form);
-  else b = kfn::wino_fused_lds_bytes(d);
-  if (b < 0) return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_winograd_lds_bytes: no kernel for wino_form %d at stride %d", d->wino_form, d->stride);
-  *bytes = b;
-  return KFN_OK;
-}
-
-// Can the F(4x4,3x3) kernel take this layer?  (host-side routing; no device access.  Mirrors every check of the launcher
-// that does not need the pointers: what remains there is the 16-byte alignment of y / u4_packed / bias and 8-byte of x.)
-extern "C" int kfn_winograd_f43_supported(const kfn_conv_desc* d) {
-  kfn_conv_desc d_full;
-  if (!d || kfn::conv_desc_in(d, &d_full, "kfn_winograd_f43_supported", true) != KFN_OK) return 0;
-  d = &d_full;
-  if (d->kh != 3 || d->kw != 3 || d->stride != 1 || d->transposed) return 0;
-  if (d->x_layout != KFN_LAYOUT_NHWC || d->y_layout != KFN_LAYOUT_NHWC) {       // channel-blocked: the eight-wave kernel, dense tensors
-    if (d->wino_form == KFN_WINO_FORM_F43_FOUR_WAVE || (d->wino_form == 0 && !W4_DEFAULT_EIGHT_WAVE)) return 0;
-    if (d->x_layout == KFN_LAYOUT_C16 && d->ldx != d->Cin) return 0;
-    if (d->y_layout == KFN_LAYOUT_C16 && (d->Cout % 16 != 0 || d->ldy != d->Cout)) return 0;
-  }
-  if (d->x_dtype != KFN_ACT_F32 || d->y_dtype != KFN_ACT_F32 || d->operand_dtype != KFN_OPERAND_F32) return 0;
-  if (d->Cin <= 0 || d->Cin % 16 != 0) return 0;
-  if ((d->H + 3) / 4 < BH4) return 0;               // an 8-row tile block may straddle at most two images
-  if (d->epilogue != KFN_EPI_NONE) return 0;
-  if (d->N <= 0 || d->W <= 0 || d->Cout <= 0) return 0;
-  if (d->cout_pad % 32 != 0 || d->cout_pad < d->Cout || d->Cout % 4 != 0 || d->ldy % 4 != 0 || d->ldx % 2 != 0) return 0;
-  if (d->ldx < d->Cin || d->ldy < d->Cout) return 0;
-  if (2L * d->H * d->W * d->ldx * 4L >= (1L << 30)) return 0;            // two images of the input below 1 GiB
-  if (2L * d->H * d->W * d->ldy * 4L >= (1L << 31)) return 0;            // ... of the output below 2 GiB
-  if (36L * d->cout_pad * d->Cin * 4L >= (1L << 31)) return 0;           // the transformed kernel below 2 GiB
-  if ((long)d->N * ((d->H + 3) / 4) >= (1L << 30)) return 0;
-  return 1;
-}
-
 namespace {
 
-// Argument checks + geometry shared by kfn_conv2d_winograd_f43 and its split-K form.  `y` / `ldy` = where the kernel writes
-// (the output tensor, or one dense plane of the split-K workspace).
-int wino4_setup(const kfn_conv_desc* d, const float* x, const float* u4_packed, const float* bias, float* y, int ldy,
-                const char* who, Wino4Args* out) {
+// The plan of one wino4_kernel / wino4b_kernel launch.  `ldy` = the pixel stride the kernel writes with (the output tensor's,
+// or Cout for a dense plane of the split-K workspace), y_low4 = that buffer's address & 15.
+int f43_plan(const kfn_conv_desc* d, int ldy, int k_split, unsigned y_low4, const char* who, kfn_wino_plan* p) {
   KFN_REQUIRE(d->kh == 3 && d->kw == 3 && d->stride == 1 && !d->transposed, "%s: only 3x3 stride-1 SAME convolutions", who);
   KFN_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0, "%s: bad shape %dx%dx%d", who, d->N, d->H, d->W);
   KFN_REQUIRE(d->x_dtype == KFN_ACT_F32 && d->y_dtype == KFN_ACT_F32 && d->operand_dtype == KFN_OPERAND_F32 &&
@@ -875,44 +824,65 @@ int wino4_setup(const kfn_conv_desc* d, const float* x, const float* u4_packed, 
               "%s: fp32 operands and activations, no fused head epilogue", who);
   if (d->Cin <= 0 || d->Cin % 16 != 0)
     return kfn::fail(KFN_ERR_UNSUPPORTED, "%s: Cin=%d must be a multiple of 16", who, d->Cin);
-  if ((d->H + 3) / 4 < BH4)
+  if ((d->H + 3) / 4 < BH4)   // an 8-row tile block may straddle at most two images
     return kfn::fail(KFN_ERR_UNSUPPORTED, "%s: H=%d is below %d rows", who, d->H, 4 * BH4 - 3);
   KFN_REQUIRE(d->ldx >= d->Cin && d->ldx % 2 == 0 && d->Cout > 0 && ldy >= d->Cout && d->cout_pad >= d->Cout &&
                   d->cout_pad % 32 == 0,
               "%s: bad strides / channel counts", who);
-  if (d->Cout % 4 != 0 || ldy % 4 != 0 || (reinterpret_cast<uintptr_t>(y) & 15) != 0)
+  if (d->Cout % 4 != 0 || ldy % 4 != 0 || y_low4 != 0)   // 16-byte stores: there is no dword epilogue
     return kfn::fail(KFN_ERR_UNSUPPORTED, "%s: Cout and ldy must be multiples of 4 and y 16-byte aligned", who);
-  KFN_REQUIRE(((reinterpret_cast<uintptr_t>(x) & 7) | (reinterpret_cast<uintptr_t>(u4_packed) & 15) |
-               (bias ? (reinterpret_cast<uintptr_t>(bias) & 15) : 0)) == 0,
-              "%s: x must be 8-byte, u4_packed and bias 16-byte aligned", who);
-  const long img_b = (long)d->H * d->W * d->ldx * 4L;
-  const long out_b = (long)d->H * d->W * ldy * 4L;
-  if (2 * img_b >= (1L << 30) || 2 * out_b >= (1L << 31) || 36L * d->cout_pad * d->Cin * 4L >= (1L << 31))
+  // two images of the input below 1 GiB, of the output and the transformed kernel below 2 GiB
+  if (2L * d->H * d->W * d->ldx * 4L >= (1L << 30) || 2L * d->H * d->W * ldy * 4L >= (1L << 31) ||
+      36L * d->cout_pad * d->Cin * 4L >= (1L << 31))
     return kfn::fail(KFN_ERR_UNSUPPORTED, "%s: image or kernel beyond the 32-bit offsets of this form", who);
+  const long vrows = (long)d->N * ((d->H + 3) / 4);
+  KFN_REQUIRE(vrows < (1L << 30), "%s: N*ceil(H/4) = %ld tile rows exceed 32-bit addressing", who, vrows);
+  const long tiles_m = (long)kfn::ceil_div((d->W + 3) / 4, BW4) * kfn::ceil_div((int)vrows, BH4);
+  const int tiles_n = kfn::ceil_div(d->cout_pad, 64);
+  KFN_REQUIRE(tiles_m * tiles_n * k_split < (1L << 31), "%s: grid too large", who);
+  if (d->x_layout == KFN_LAYOUT_C16 && d->ldx != d->Cin)
+    return kfn::fail(KFN_ERR_UNSUPPORTED, "%s: a KFN_LAYOUT_C16 input is dense (ldx=%d, Cin=%d)", who, d->ldx, d->Cin);
+  if (d->y_layout == KFN_LAYOUT_C16 && (d->Cout % 16 != 0 || ldy != d->Cout))
+    return kfn::fail(KFN_ERR_UNSUPPORTED, "%s: a KFN_LAYOUT_C16 output is dense and Cout %% 16 == 0 (ldy=%d, Cout=%d)", who, ldy, d->Cout);
+  // kfn_conv_desc.wino_form: KFN_WINO_FORM_F43_FOUR_WAVE / _EIGHT_WAVE pick the kernel (A/B measurements); AUTO = the default
+  const bool eight = d->wino_form == KFN_WINO_FORM_F43_EIGHT_WAVE ||
+                     (d->wino_form != KFN_WINO_FORM_F43_FOUR_WAVE && W4_DEFAULT_EIGHT_WAVE);
+  if (!eight && (d->x_layout != KFN_LAYOUT_NHWC || d->y_layout != KFN_LAYOUT_NHWC))
+    return kfn::fail(KFN_ERR_UNSUPPORTED, "%s: the four-wave form reads and writes NHWC only", who);
+  const int n_super = d->Cin / (8 * CPS);
+  std::memset(p, 0, sizeof(*p));
+  p->kernel = eight ? KFN_WINO_KERNEL_WINO4B : KFN_WINO_KERNEL_WINO4;
+  p->threads = eight ? 512 : 256;
+  p->lds_bytes = eight ? B_LDS : LDS_V;
+  p->tiles_m = (int)tiles_m; p->tiles_n = tiles_n;
+  p->tiles_per_block = BW4 * BH4;
+  p->channels_per_group = 64;
+  p->k_split = k_split;
+  p->ss_per_split = kfn::ceil_div(n_super, k_split);
+  KFN_REQUIRE((long)(k_split - 1) * p->ss_per_split < n_super, "%s: k_split=%d leaves an empty split of %d super-steps", who, k_split, n_super);
+  p->workgroups = p->tiles_m * tiles_n * k_split;
+  // workgroup order: M fastest (1 group), all channel groups of a block adjacent (N fastest), or KFN_WINO_ORDER_GROUPS(n).
+  // AUTO: four groups (two when the layer has fewer) -- the input block then crosses the fabric a quarter as often and a
+  // weight slice is still shared by 8 CUs of the XCD: conv4b 6.28 -> 6.07 ms, conv5 3.26 -> 3.19, conv3b 6.46 -> 6.36,
+  // conv2b equal (same log); 8 groups and N fastest lose again (the weight slices no longer share an L2).
+  p->n_group = kfn::wino_n_group(d->wino_order, tiles_n, tiles_n % 4 == 0 ? 4 : (tiles_n % 2 == 0 ? 2 : 1), 1);
+  p->wide_store = 1;
+  return KFN_OK;
+}
+
+// The kernel arguments of a planned launch writing to y with pixel stride ldy.
+Wino4Args wino4_args(const kfn_conv_desc* d, const kfn_wino_plan& p, const float* x, const float* u4_packed, const float* bias,
+                     float* y, int ldy) {
   Wino4Args a;
   a.x = x; a.u4 = u4_packed; a.bias = bias; a.y = y;
   a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.ldx = d->ldx;
   a.Cout = d->Cout; a.cout_pad = d->cout_pad; a.ldy = ldy;
   a.Th = (d->H + 3) / 4; a.Tw = (d->W + 3) / 4;
-  const long vrows = (long)d->N * a.Th;
-  KFN_REQUIRE(vrows < (1L << 30), "%s: N*ceil(H/4) = %ld tile rows exceed 32-bit addressing", who, vrows);
-  a.vrows = (int)vrows;
+  a.vrows = d->N * a.Th;
   a.bw = kfn::ceil_div(a.Tw, BW4);
-  const long tiles_m = (long)a.bw * kfn::ceil_div(a.vrows, BH4);
-  a.tiles_n = kfn::ceil_div(d->cout_pad, 64);
-  KFN_REQUIRE(tiles_m * a.tiles_n < (1L << 31), "%s: grid too large", who);
-  a.tiles_m = (int)tiles_m;
+  a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n;
   a.relu = d->relu;
-  // workgroup order: M fastest (1 group), all channel groups of a block adjacent (N fastest), or KFN_WINO_ORDER_GROUPS(n).
-  // AUTO: four groups (two when the layer has fewer) -- the input block then crosses the fabric a quarter as often and a
-  // weight slice is still shared by 8 CUs of the XCD: conv4b 6.28 -> 6.07 ms, conv5 3.26 -> 3.19, conv3b 6.46 -> 6.36,
-  // conv2b equal (same log); 8 groups and N fastest lose again (the weight slices no longer share an L2).
-  int ng = 1;
-  if (d->wino_order == KFN_WINO_ORDER_AUTO) ng = a.tiles_n % 4 == 0 ? 4 : (a.tiles_n % 2 == 0 ? 2 : 1);
-  else if (d->wino_order == KFN_WINO_ORDER_N_FAST) ng = a.tiles_n;
-  else if (d->wino_order >= KFN_WINO_ORDER_GROUPS(1)) ng = d->wino_order - KFN_WINO_ORDER_GROUPS(0);
-  if (ng < 1 || ng > a.tiles_n || a.tiles_n % ng != 0) ng = 1;
-  a.n_group = ng;
+  a.n_group = p.n_group;
   const long in_pix = (long)d->N * d->H * d->W;
   a.x_bytes = (unsigned long long)(((in_pix - 1) * d->ldx + d->Cin) * 4L);
   a.y_bytes = (unsigned long long)(((in_pix - 1) * ldy + d->Cout) * 4L);
@@ -920,49 +890,109 @@ int wino4_setup(const kfn_conv_desc* d, const float* x, const float* u4_packed, 
   // cout_pad reads 32 channels past the matrix -- the range check returns zeros for them (their accumulators are never stored)
   a.u_bytes = (unsigned)(36L * d->cout_pad * d->Cin * 4L);
   const bool xb = d->x_layout == KFN_LAYOUT_C16, yb = d->y_layout == KFN_LAYOUT_C16;
-  if (xb && d->ldx != d->Cin)
-    return kfn::fail(KFN_ERR_UNSUPPORTED, "%s: a KFN_LAYOUT_C16 input is dense (ldx=%d, Cin=%d)", who, d->ldx, d->Cin);
-  if (yb && (d->Cout % 16 != 0 || ldy != d->Cout))
-    return kfn::fail(KFN_ERR_UNSUPPORTED, "%s: a KFN_LAYOUT_C16 output is dense and Cout %% 16 == 0 (ldy=%d, Cout=%d)", who, ldy, d->Cout);
-  a.x_img = (unsigned)img_b; a.x_pix = xb ? 64u : (unsigned)d->ldx * 4u; a.x_cb = xb ? (unsigned)(d->H * d->W) * 64u : 64u;
-  a.y_img = (unsigned)out_b; a.y_pix = yb ? 64u : (unsigned)ldy * 4u; a.y_cb = yb ? (unsigned)(d->H * d->W) * 64u : 64u;
-  a.k_split = 1;
-  a.ss_per_split = d->Cin / (8 * CPS);
-  a.y_split_bytes = 0;
-  *out = a;
-  return KFN_OK;
+  a.x_img = (unsigned)((long)d->H * d->W * d->ldx * 4L); a.x_pix = xb ? 64u : (unsigned)d->ldx * 4u; a.x_cb = xb ? (unsigned)(d->H * d->W) * 64u : 64u;
+  a.y_img = (unsigned)((long)d->H * d->W * ldy * 4L); a.y_pix = yb ? 64u : (unsigned)ldy * 4u; a.y_cb = yb ? (unsigned)(d->H * d->W) * 64u : 64u;
+  a.k_split = p.k_split;
+  a.ss_per_split = p.ss_per_split;
+  a.y_split_bytes = p.k_split > 1 ? (unsigned long long)in_pix * d->Cout * 4ull : 0;
+  return a;
 }
 
-int wino4b_launch(const Wino4Args& a, hipStream_t stream) {
-  static std::atomic<uint64_t> attr_done_b{0};
-  int rcb = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino4b_kernel), B_LDS, attr_done_b);
-  if (rcb != KFN_OK) return rcb;
-  hipLaunchKernelGGL(wino4b_kernel, dim3((unsigned)((long)a.tiles_m * a.tiles_n * a.k_split)), dim3(512), B_LDS, stream, a);
-  KFN_LAUNCH_CHECK("wino4b_kernel");
+// `a` = wino4_args of plan `p`, whose pointers the caller has checked
+int wino4_launch(const kfn_wino_plan& p, const Wino4Args& a, const char* who, hipStream_t stream) {
+  KFN_REQUIRE(((reinterpret_cast<uintptr_t>(a.x) & 7) | kfn::low4(a.u4) | kfn::low4(a.bias)) == 0,
+              "%s: x must be 8-byte, u4_packed and bias 16-byte aligned", who);
+  if (p.kernel == KFN_WINO_KERNEL_WINO4B) {
+    static std::atomic<uint64_t> attr_done_b{0};
+    int rcb = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino4b_kernel), p.lds_bytes, attr_done_b);
+    if (rcb != KFN_OK) return rcb;
+    hipLaunchKernelGGL(wino4b_kernel, dim3((unsigned)p.workgroups), dim3((unsigned)p.threads), p.lds_bytes, stream, a);
+    KFN_LAUNCH_CHECK("wino4b_kernel");
+    return KFN_OK;
+  }
+  static std::atomic<uint64_t> attr_done{0};
+  int rc = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino4_kernel), p.lds_bytes, attr_done);
+  if (rc != KFN_OK) return rc;
+  hipLaunchKernelGGL(wino4_kernel, dim3((unsigned)p.workgroups), dim3((unsigned)p.threads), p.lds_bytes, stream, a);
+  KFN_LAUNCH_CHECK("wino4_kernel");
   return KFN_OK;
 }
 
 }  // namespace
 
+// kfn_conv2d_winograd_f43 (k_split 0) and kfn_conv2d_winograd_f43_splitk (k_split >= 1: the eight-wave kernel; > 1: it writes
+// dense planes of the workspace, and y, which the reduce kernel then writes 16 bytes at a time, only has to allow that)
+int kfn::wino_f43_plan(const kfn_conv_desc* d, int k_split, unsigned y_low4, kfn_wino_plan* p) {
+  if (k_split == 0) return f43_plan(d, d->ldy, 1, y_low4, "kfn_conv2d_winograd_f43", p);
+  const char* who = "kfn_conv2d_winograd_f43_splitk";
+  KFN_REQUIRE(d->wino_form == KFN_WINO_FORM_AUTO || d->wino_form == KFN_WINO_FORM_F43_EIGHT_WAVE,
+              "%s: the eight-wave form only (weights packed per pair of positions)", who);
+  if (d->x_layout != KFN_LAYOUT_NHWC || d->y_layout != KFN_LAYOUT_NHWC)
+    return kfn::fail(KFN_ERR_UNSUPPORTED, "%s reads and writes NHWC only (x_layout %d, y_layout %d)", who, d->x_layout, d->y_layout);
+  const int n_super = d->Cin > 0 ? d->Cin / (8 * CPS) : 0;
+  KFN_REQUIRE(k_split >= 1 && k_split <= (n_super > 0 ? n_super : 1), "%s: k_split=%d outside 1..%d (Cin/16)", who, k_split, n_super);
+  kfn_conv_desc d8 = *d;
+  d8.wino_form = KFN_WINO_FORM_F43_EIGHT_WAVE;
+  if (k_split == 1) return f43_plan(&d8, d->ldy, 1, y_low4, who, p);
+  KFN_REQUIRE(d->ldy >= d->Cout && d->ldy % 4 == 0 && y_low4 == 0,
+              "%s: k_split > 1 needs a 16-byte aligned workspace of kfn_winograd_f43_splitk_workspace_bytes() "
+              "and a 16-byte aligned output with ldy %% 4 == 0", who);
+  return f43_plan(&d8, d->Cout, k_split, 0, who, p);
+}
+
+int kfn::wino_plan(const kfn_conv_desc* d, int k_split, int cu_count, unsigned y_low4, kfn_wino_plan* p) {
+  if (d->stride == 2) return kfn::wino_s2_plan(d, k_split, cu_count > 0 ? cu_count : 256, y_low4, p);
+  if (d->wino_form == KFN_WINO_FORM_F43_FOUR_WAVE || d->wino_form == KFN_WINO_FORM_F43_EIGHT_WAVE) return kfn::wino_f43_plan(d, k_split, y_low4, p);
+  if (k_split != 0) return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_fused has no split-K form (k_split=%d)", k_split);
+  if (d->x_layout != KFN_LAYOUT_NHWC || d->y_layout != KFN_LAYOUT_NHWC)   // (its launcher: conv_desc_in)
+    return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_fused reads and writes NHWC only (x_layout %d, y_layout %d)", d->x_layout, d->y_layout);
+  return kfn::wino_fused_plan(d, y_low4, p);
+}
+
+extern "C" int kfn_winograd_launch_plan(const kfn_conv_desc* d, int k_split, int cu_count, unsigned y_low_bits, kfn_wino_plan* plan) {
+  KFN_REQUIRE(d && plan, "kfn_winograd_launch_plan: null argument");
+  const int32_t sz = plan->struct_size;
+  KFN_REQUIRE(sz >= 8 && sz <= (int32_t)sizeof(kfn_wino_plan) && (sz & 3) == 0,
+              "kfn_winograd_launch_plan: kfn_wino_plan.struct_size = %d (this library: %d bytes) -- set it to sizeof(kfn_wino_plan)",
+              (int)sz, (int)sizeof(kfn_wino_plan));
+  KFN_CONV_DESC_IN_LAYOUTS(d, "kfn_winograd_launch_plan");
+  kfn_wino_plan p;
+  int rc = kfn::wino_plan(d, k_split, cu_count, y_low_bits & 15u, &p);
+  if (rc != KFN_OK) return rc;
+  p.struct_size = sz;
+  std::memcpy(plan, &p, (size_t)sz);
+  return KFN_OK;
+}
+
+// Dynamic LDS per workgroup of the kernel a Winograd entry point launches for `desc` (the plain entry point, an aligned
+// output, 256 CUs), so that a host can route around kernels a device's LDS cannot hold (kfn_device_info's lds_bytes_per_cu)
+// instead of failing in the first launch.  No device access.
+extern "C" int kfn_winograd_lds_bytes(const kfn_conv_desc* d, int* bytes) {
+  KFN_REQUIRE(d && bytes, "kfn_winograd_lds_bytes: null argument");
+  KFN_CONV_DESC_IN_LAYOUTS(d, "kfn_winograd_lds_bytes");
+  kfn_wino_plan p;
+  int rc = kfn::wino_plan(d, 0, 0, 0, &p);
+  if (rc != KFN_OK) return rc;
+  *bytes = p.lds_bytes;
+  return KFN_OK;
+}
+
+// Can the F(4x4,3x3) kernel take this layer?  = "kfn_conv2d_winograd_f43's plan succeeds for a 16-byte aligned output".  What
+// the launcher checks beyond it is the alignment of the pointers.  Host only; no device access.
+extern "C" int kfn_winograd_f43_supported(const kfn_conv_desc* d) {
+  kfn_conv_desc d_full;
+  kfn_wino_plan p;
+  return d && kfn::conv_desc_in(d, &d_full, "kfn_winograd_f43_supported", true) == KFN_OK && kfn::wino_f43_plan(&d_full, 0, 0, &p) == KFN_OK;
+}
+
 extern "C" int kfn_conv2d_winograd_f43(const kfn_conv_desc* d, const float* x, const float* u4_packed, const float* bias,
                                        float* y, void* stream) {
   KFN_REQUIRE(d && x && u4_packed && y, "kfn_conv2d_winograd_f43: null argument");
   KFN_CONV_DESC_IN_LAYOUTS(d, "kfn_conv2d_winograd_f43");
-  Wino4Args a;
-  int rc = wino4_setup(d, x, u4_packed, bias, y, d->ldy, "kfn_conv2d_winograd_f43", &a);
+  kfn_wino_plan p;
+  int rc = kfn::wino_f43_plan(d, 0, kfn::low4(y), &p);
   if (rc != KFN_OK) return rc;
-  // kfn_conv_desc.wino_form: KFN_WINO_FORM_F43_FOUR_WAVE / _EIGHT_WAVE pick the kernel (A/B measurements); AUTO = the default below
-  const bool eight = d->wino_form == KFN_WINO_FORM_F43_EIGHT_WAVE ||
-                     (d->wino_form != KFN_WINO_FORM_F43_FOUR_WAVE && W4_DEFAULT_EIGHT_WAVE);
-  if (!eight && (d->x_layout != KFN_LAYOUT_NHWC || d->y_layout != KFN_LAYOUT_NHWC))
-    return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_f43: the four-wave form reads and writes NHWC only");
-  if (eight) return wino4b_launch(a, (hipStream_t)stream);
-  static std::atomic<uint64_t> attr_done{0};
-  rc = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino4_kernel), LDS_V, attr_done);
-  if (rc != KFN_OK) return rc;
-  hipLaunchKernelGGL(wino4_kernel, dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(256), LDS_V, (hipStream_t)stream, a);
-  KFN_LAUNCH_CHECK("wino4_kernel");
-  return KFN_OK;
+  return wino4_launch(p, wino4_args(d, p, x, u4_packed, bias, y, d->ldy), "kfn_conv2d_winograd_f43", (hipStream_t)stream);
 }
 
 // ---- split-K form (round 5: BASELINE configs[1], one 480x640 frame): the layers whose launch has fewer workgroups than
@@ -979,36 +1009,21 @@ extern "C" int kfn_winograd_f43_splitk_workspace_bytes(const kfn_conv_desc* d, i
 
 extern "C" int kfn_conv2d_winograd_f43_splitk(const kfn_conv_desc* d, const float* x, const float* u4b_packed, const float* bias,
                                               float* y, float* workspace, int k_split, void* stream) {
-  KFN_REQUIRE(d && x && u4b_packed && y, "kfn_conv2d_winograd_f43_splitk: null argument");
-  KFN_CONV_DESC_IN(d, "kfn_conv2d_winograd_f43_splitk");
-  KFN_REQUIRE(d->wino_form == KFN_WINO_FORM_AUTO || d->wino_form == KFN_WINO_FORM_F43_EIGHT_WAVE,
-              "kfn_conv2d_winograd_f43_splitk: the eight-wave form only (weights packed per pair of positions)");
-  const int n_super = d->Cin > 0 ? d->Cin / (8 * CPS) : 0;
-  KFN_REQUIRE(k_split >= 1 && k_split <= (n_super > 0 ? n_super : 1), "kfn_conv2d_winograd_f43_splitk: k_split=%d outside 1..%d (Cin/16)",
-              k_split, n_super);
-  Wino4Args a;
-  if (k_split == 1) {
-    int rc = wino4_setup(d, x, u4b_packed, bias, y, d->ldy, "kfn_conv2d_winograd_f43_splitk", &a);
-    if (rc != KFN_OK) return rc;
-    return wino4b_launch(a, (hipStream_t)stream);
-  }
-  KFN_REQUIRE(workspace != nullptr && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && d->ldy >= d->Cout && d->ldy % 4 == 0 &&
-                  (reinterpret_cast<uintptr_t>(y) & 15) == 0,
-              "kfn_conv2d_winograd_f43_splitk: k_split > 1 needs a 16-byte aligned workspace of kfn_winograd_f43_splitk_workspace_bytes() "
-              "and a 16-byte aligned output with ldy %% 4 == 0");
-  int rc = wino4_setup(d, x, u4b_packed, nullptr, workspace, d->Cout, "kfn_conv2d_winograd_f43_splitk", &a);
+  const char* who = "kfn_conv2d_winograd_f43_splitk";
+  KFN_REQUIRE(d && x && u4b_packed && y, "%s: null argument", who);
+  KFN_CONV_DESC_IN(d, who);
+  kfn_wino_plan p;
+  int rc = kfn::wino_f43_plan(d, k_split < 1 ? -1 : k_split, kfn::low4(y), &p);
   if (rc != KFN_OK) return rc;
-  const long pixels = (long)d->N * d->H * d->W;
+  if (p.k_split == 1) return wino4_launch(p, wino4_args(d, p, x, u4b_packed, bias, y, d->ldy), who, (hipStream_t)stream);
+  KFN_REQUIRE(workspace != nullptr && kfn::low4(workspace) == 0,
+              "%s: k_split > 1 needs a 16-byte aligned workspace of kfn_winograd_f43_splitk_workspace_bytes() "
+              "and a 16-byte aligned output with ldy %% 4 == 0", who);
+  Wino4Args a = wino4_args(d, p, x, u4b_packed, nullptr, workspace, d->Cout);
   a.relu = 0;
-  a.k_split = k_split;
-  a.ss_per_split = kfn::ceil_div(n_super, k_split);
-  KFN_REQUIRE((long)(k_split - 1) * a.ss_per_split < n_super, "kfn_conv2d_winograd_f43_splitk: k_split=%d leaves an empty split of %d super-steps",
-              k_split, n_super);
-  a.y_split_bytes = (unsigned long long)pixels * d->Cout * 4ull;
-  KFN_REQUIRE((long)a.tiles_m * a.tiles_n * k_split < (1L << 31), "kfn_conv2d_winograd_f43_splitk: grid too large");
-  rc = wino4b_launch(a, (hipStream_t)stream);
+  rc = wino4_launch(p, a, who, (hipStream_t)stream);
   if (rc != KFN_OK) return rc;
-  return kfn::launch_splitk_reduce(workspace, k_split, pixels, bias, d->relu, y, d->Cout, d->ldy, (hipStream_t)stream);
+  return kfn::launch_splitk_reduce(workspace, k_split, (long)d->N * d->H * d->W, bias, d->relu, y, d->Cout, d->ldy, (hipStream_t)stream);
 }
 
 int kfn::launch_splitk_reduce(const float* ws, int k_split, long pixels, const float* bias, int relu, float* y, int Cout, int ldy,

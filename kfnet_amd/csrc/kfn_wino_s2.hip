@@ -694,45 +694,24 @@ __global__ __launch_bounds__(512, 1) void wino_s2b_kernel(WinoS2Args p) {
 
 }  // namespace
 
-// Can the polyphase kernel take this layer?  (host-side routing; no device access)
-int kfn::wino_s2_lds_bytes(int wino_form, int operand_dtype) {
-  if (wino_form == KFN_WINO_FORM_S2_F42) return operand_dtype == KFN_OPERAND_F32 ? kfn::wino_s2c_lds_bytes() : -1;
-  if (wino_form == KFN_WINO_FORM_S2_EIGHT_WAVE) return operand_dtype == KFN_OPERAND_F32 ? SB_LDS : -1;
-  if (wino_form != KFN_WINO_FORM_AUTO) return -1;
-  return operand_dtype == KFN_OPERAND_F16 ? VLayoutS2<true>::LDS : VLayoutS2<false>::LDS;
-}
-
-extern "C" int kfn_winograd_s2_supported(const kfn_conv_desc* d) {
-  kfn_conv_desc d_full;
-  if (!d || kfn::conv_desc_in(d, &d_full, "kfn_winograd_s2_supported", true) != KFN_OK) return 0;
-  if ((d_full.x_layout != KFN_LAYOUT_NHWC || d_full.y_layout != KFN_LAYOUT_NHWC) && d_full.wino_form != KFN_WINO_FORM_S2_F42) return 0;
-  d = &d_full;
-  if (d->wino_form == KFN_WINO_FORM_S2_F42) return kfn::wino_s2c_supported(d);
-  if (d->x_dtype != KFN_ACT_F32 || d->y_dtype != KFN_ACT_F32) return 0;
-  if (d->kh != 3 || d->kw != 3 || d->stride != 2 || d->transposed) return 0;
-  if (d->H <= 0 || d->W <= 0 || (d->H & 1) || (d->W & 1)) return 0;     // 'same' pads after the image only
-  if (d->Cin <= 0 || d->Cin % SS_CH != 0) return 0;
-  if ((d->H / 2 + 1) / 2 < BH) return 0;   // a 4-row tile block may straddle at most two images
-  if (d->epilogue != KFN_EPI_NONE || (d->operand_dtype != KFN_OPERAND_F32 && d->operand_dtype != KFN_OPERAND_F16)) return 0;
-  if (d->cout_pad % 32 != 0) return 0;
-  return 1;
-}
-
 namespace {
-// `d` normalised; y / ldy = where the kernel writes (the output tensor, or plane 0 of the split-K workspace); k_split > 1:
-// the eight-wave kernel on k_split copies of the tile grid, raw partial sums (the caller passes bias = nullptr, relu = 0)
-int s2_launch(const kfn_conv_desc* d, const float* x, const void* u2_packed, const float* bias, float* y, int ldy, int relu,
-              int k_split, void* stream) {
+
+// The plan of one wino_s2_kernel / wino_s2b_kernel launch.  `ldy` = the pixel stride the kernel writes with (the output
+// tensor's, or Cout for a dense plane of the split-K workspace), y_low4 = that buffer's address & 15; k_split > 1: the
+// eight-wave kernel on k_split copies of the tile grid.
+int s2_plan(const kfn_conv_desc* d, int ldy, int k_split, unsigned y_low4, kfn_wino_plan* p) {
+  if (d->x_layout != KFN_LAYOUT_NHWC || d->y_layout != KFN_LAYOUT_NHWC)
+    return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_s2: only the F(4,2) form (KFN_WINO_FORM_S2_F42) takes KFN_LAYOUT_C16 activations");
   KFN_REQUIRE(d->x_dtype == KFN_ACT_F32 && d->y_dtype == KFN_ACT_F32,
               "kfn_conv2d_winograd_s2: fp32 activations in memory only (x_dtype / y_dtype = KFN_ACT_F16 is implemented by kfn_conv2d_nhwc)");
   KFN_REQUIRE(d->kh == 3 && d->kw == 3 && d->stride == 2 && !d->transposed,
               "kfn_conv2d_winograd_s2: only 3x3 stride-2 SAME convolutions");
   KFN_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0, "kfn_conv2d_winograd_s2: bad shape %dx%dx%d", d->N, d->H, d->W);
-  if ((d->H & 1) || (d->W & 1))
+  if ((d->H & 1) || (d->W & 1))   // 'same' pads after the image only
     return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_s2: H=%d W=%d must be even", d->H, d->W);
   if (d->Cin <= 0 || d->Cin % SS_CH != 0)
     return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_s2: Cin=%d must be a multiple of %d", d->Cin, SS_CH);
-  if ((d->H / 2 + 1) / 2 < BH)
+  if ((d->H / 2 + 1) / 2 < BH)   // a 4-row tile block may straddle at most two images
     return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_s2: H=%d is below %d rows", d->H, 4 * BH - 2);
   KFN_REQUIRE(d->ldx >= d->Cin && d->ldx % 4 == 0 && d->Cout > 0 && ldy >= d->Cout &&
                   d->cout_pad >= d->Cout && d->cout_pad % 32 == 0,
@@ -740,88 +719,129 @@ int s2_launch(const kfn_conv_desc* d, const float* x, const void* u2_packed, con
   KFN_REQUIRE(d->epilogue == KFN_EPI_NONE && (d->operand_dtype == KFN_OPERAND_F32 || d->operand_dtype == KFN_OPERAND_F16),
               "kfn_conv2d_winograd_s2: fp32 or fp16 operands, no fused head epilogue");
   const bool h16 = d->operand_dtype == KFN_OPERAND_F16;
+  const int Ho = d->H / 2, Wo = d->W / 2;
+  KFN_REQUIRE(2L * d->H * d->W * d->ldx * 4L < (1L << 31) && 2L * Ho * Wo * ldy * 4L < (1L << 31) &&
+                  16L * d->cout_pad * d->Cin * 4L < (1L << 31),
+              "kfn_conv2d_winograd_s2: image or kernel beyond 2 GiB of 32-bit offsets");
+  const long vrows = (long)d->N * ((Ho + 1) / 2);
+  KFN_REQUIRE(vrows < (1L << 30), "kfn_conv2d_winograd_s2: N*ceil(H/4) = %ld tile rows exceed 32-bit addressing", vrows);
+  const long tiles_m = (long)kfn::ceil_div((Wo + 1) / 2, BW) * kfn::ceil_div((int)vrows, BH);
+  const int tiles_n = kfn::ceil_div(d->cout_pad, NT);
+  KFN_REQUIRE(tiles_m * tiles_n < (1L << 31), "kfn_conv2d_winograd_s2: grid too large");
+  const int n_super = d->Cin / SS_CH;
+  std::memset(p, 0, sizeof(*p));
+  p->tiles_m = (int)tiles_m; p->tiles_n = tiles_n;
+  p->tiles_per_block = BW * BH;
+  p->channels_per_group = NT;
+  p->k_split = k_split;
+  p->ss_per_split = kfn::ceil_div(n_super, k_split);
+  KFN_REQUIRE((long)(k_split - 1) * p->ss_per_split < n_super, "kfn_conv2d_winograd_s2_splitk: k_split=%d leaves an empty split of %d super-steps",
+              k_split, n_super);
+  KFN_REQUIRE(tiles_m * tiles_n * k_split < (1L << 31), "kfn_conv2d_winograd_s2_splitk: grid too large");
+  p->workgroups = p->tiles_m * tiles_n * k_split;
+  // AUTO: two channel groups of a tile block adjacent (round 4, profiles/r04_wino4_microbench.log: conv4a 7.19 ms against
+  // 7.34 with all eight adjacent and 7.29 with the tile blocks fastest; conv3a / conv2a within 1 % of each other)
+  const int all = S2_DEFAULT_N_FAST ? tiles_n : 1;
+  p->n_group = kfn::wino_n_group(d->wino_order, tiles_n, tiles_n % 2 == 0 ? 2 : all, all);
+  p->wide_store = (d->Cout % 4 == 0 && ldy % 4 == 0 && y_low4 == 0) ? 1 : 0;
+  if (d->wino_form == KFN_WINO_FORM_S2_EIGHT_WAVE || k_split > 1) {
+    // the eight-wave form: fp32 operands only, weights packed per pair of fragments (graph.pack_winograd_s2_kernel_b)
+    if (h16) return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_s2: the eight-wave form takes fp32 operands only");
+    p->kernel = KFN_WINO_KERNEL_S2B; p->threads = 512; p->lds_bytes = SB_LDS;
+  } else {
+    p->kernel = h16 ? KFN_WINO_KERNEL_S2_F16 : KFN_WINO_KERNEL_S2; p->threads = 64 * NWAVE;
+    p->lds_bytes = h16 ? VLayoutS2<true>::LDS : VLayoutS2<false>::LDS;
+  }
+  return KFN_OK;
+}
+
+// Launch of plan `p`, the kernel writing to y with pixel stride ldy (split-K: raw partial sums, bias = nullptr, relu = 0).
+int s2_launch(const kfn_conv_desc* d, const kfn_wino_plan& p, const float* x, const void* u2_packed, const float* bias, float* y,
+              int ldy, int relu, void* stream) {
   KFN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(u2_packed)) & 15) == 0,
               "kfn_conv2d_winograd_s2: buffers must be 16-byte aligned");
-  const long img_b = (long)d->H * d->W * d->ldx * 4L;
-  const long out_b = (long)(d->H / 2) * (d->W / 2) * ldy * 4L;
-  KFN_REQUIRE(2 * img_b < (1L << 31) && 2 * out_b < (1L << 31) && 16L * d->cout_pad * d->Cin * 4L < (1L << 31),
-              "kfn_conv2d_winograd_s2: image or kernel beyond 2 GiB of 32-bit offsets");
+  const bool h16 = p.kernel == KFN_WINO_KERNEL_S2_F16;
   WinoS2Args a;
   a.x = x; a.u2 = static_cast<const float*>(u2_packed); a.bias = bias; a.y = y;
   a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.ldx = d->ldx;
   a.Cout = d->Cout; a.cout_pad = d->cout_pad; a.ldy = ldy;
   a.Ho = d->H / 2; a.Wo = d->W / 2;
   a.Th = (a.Ho + 1) / 2; a.Tw = (a.Wo + 1) / 2;
-  const long vrows = (long)d->N * a.Th;
-  a.vrows = (int)vrows;
+  a.vrows = d->N * a.Th;
   a.bw = kfn::ceil_div(a.Tw, BW);
-  const long tiles_m = (long)a.bw * kfn::ceil_div(a.vrows, BH);
-  a.tiles_n = kfn::ceil_div(d->cout_pad, NT);
-  KFN_REQUIRE(tiles_m * a.tiles_n < (1L << 31), "kfn_conv2d_winograd_s2: grid too large");
-  a.tiles_m = (int)tiles_m;
+  a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n;
   a.relu = relu;
-  {
-    // AUTO: two channel groups of a tile block adjacent (round 4, profiles/r04_wino4_microbench.log: conv4a 7.19 ms against
-    // 7.34 with all eight adjacent and 7.29 with the tile blocks fastest; conv3a / conv2a within 1 % of each other)
-    int ng = a.tiles_n % 2 == 0 ? 2 : (S2_DEFAULT_N_FAST ? a.tiles_n : 1);
-    if (d->wino_order == KFN_WINO_ORDER_N_FAST) ng = a.tiles_n;
-    else if (d->wino_order == KFN_WINO_ORDER_M_FAST) ng = 1;
-    else if (d->wino_order >= KFN_WINO_ORDER_GROUPS(1)) ng = d->wino_order - KFN_WINO_ORDER_GROUPS(0);
-    if (ng < 1 || ng > a.tiles_n || a.tiles_n % ng != 0) ng = S2_DEFAULT_N_FAST ? a.tiles_n : 1;
-    a.n_group = ng;
-  }
-  a.wide_store = (d->Cout % 4 == 0 && ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0) ? 1 : 0;
+  a.n_group = p.n_group;
+  a.wide_store = p.wide_store;
   const long in_pix = (long)d->N * d->H * d->W, out_pix = (long)d->N * a.Ho * a.Wo;
   a.x_bytes = (unsigned long long)(((in_pix - 1) * d->ldx + d->Cin) * 4L);
   a.y_bytes = (unsigned long long)(((out_pix - 1) * ldy + d->Cout) * 4L);
   a.u_bytes = (unsigned)(16L * d->cout_pad * d->Cin * (h16 ? 2L : 4L));
-  a.k_split = 1;
-  a.ss_per_split = d->Cin / SS_CH;
-  a.y_split_bytes = 0;
-  if (k_split > 1) {
-    const int n_super = d->Cin / SS_CH;
-    a.k_split = k_split;
-    a.ss_per_split = kfn::ceil_div(n_super, k_split);
-    KFN_REQUIRE((long)(k_split - 1) * a.ss_per_split < n_super, "kfn_conv2d_winograd_s2_splitk: k_split=%d leaves an empty split of %d super-steps",
-                k_split, n_super);
-    a.y_split_bytes = (unsigned long long)out_pix * d->Cout * 4ull;
-    KFN_REQUIRE((long)a.tiles_m * a.tiles_n * k_split < (1L << 31), "kfn_conv2d_winograd_s2_splitk: grid too large");
-  }
-  const dim3 grid((unsigned)((long)a.tiles_m * a.tiles_n * a.k_split)), block(64 * NWAVE);
-  if (d->wino_form == KFN_WINO_FORM_S2_EIGHT_WAVE || k_split > 1) {
-    // the eight-wave form: fp32 operands only, weights packed per pair of fragments (graph.pack_winograd_s2_kernel_b)
-    if (h16) return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_s2: the eight-wave form takes fp32 operands only");
+  a.k_split = p.k_split;
+  a.ss_per_split = p.ss_per_split;
+  a.y_split_bytes = p.k_split > 1 ? (unsigned long long)out_pix * d->Cout * 4ull : 0;
+  const dim3 grid((unsigned)p.workgroups), block((unsigned)p.threads);
+  if (p.kernel == KFN_WINO_KERNEL_S2B) {
     static std::atomic<uint64_t> attr_done_b{0};
-    int rc = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino_s2b_kernel), SB_LDS, attr_done_b);
+    int rc = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino_s2b_kernel), p.lds_bytes, attr_done_b);
     if (rc != KFN_OK) return rc;
-    hipLaunchKernelGGL(wino_s2b_kernel, grid, dim3(512), SB_LDS, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(wino_s2b_kernel, grid, block, p.lds_bytes, (hipStream_t)stream, a);
     KFN_LAUNCH_CHECK("wino_s2b_kernel");
     return KFN_OK;
   }
   if (h16) {
     static std::atomic<uint64_t> attr_done16{0};
-    int rc = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino_s2_kernel<true>), VLayoutS2<true>::LDS, attr_done16);
+    int rc = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino_s2_kernel<true>), p.lds_bytes, attr_done16);
     if (rc != KFN_OK) return rc;
-    hipLaunchKernelGGL(wino_s2_kernel<true>, grid, block, VLayoutS2<true>::LDS, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(wino_s2_kernel<true>, grid, block, p.lds_bytes, (hipStream_t)stream, a);
   } else {
     static std::atomic<uint64_t> attr_done{0};
-    int rc = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino_s2_kernel<false>), VLayoutS2<false>::LDS, attr_done);
+    int rc = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino_s2_kernel<false>), p.lds_bytes, attr_done);
     if (rc != KFN_OK) return rc;
-    hipLaunchKernelGGL(wino_s2_kernel<false>, grid, block, VLayoutS2<false>::LDS, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(wino_s2_kernel<false>, grid, block, p.lds_bytes, (hipStream_t)stream, a);
   }
   KFN_LAUNCH_CHECK("wino_s2_kernel");
   return KFN_OK;
 }
 }  // namespace
 
+// kfn_conv2d_winograd_s2 (k_split 0; the F(4,2) form: kfn_wino_s2c.hip) and kfn_conv2d_winograd_s2_splitk (k_split >= 1: the
+// eight-wave kernel; > 1: it writes dense planes of the workspace, and y, which the reduce kernel then writes 16 bytes at a
+// time, only has to allow that)
+int kfn::wino_s2_plan(const kfn_conv_desc* d, int k_split, int cu_count, unsigned y_low4, kfn_wino_plan* p) {
+  if (k_split == 0)
+    return d->wino_form == KFN_WINO_FORM_S2_F42 ? kfn::wino_s2c_plan(d, cu_count, y_low4, p) : s2_plan(d, d->ldy, 1, y_low4, p);
+  KFN_REQUIRE((d->wino_form == KFN_WINO_FORM_AUTO || d->wino_form == KFN_WINO_FORM_S2_EIGHT_WAVE) && d->operand_dtype == KFN_OPERAND_F32,
+              "kfn_conv2d_winograd_s2_splitk: the eight-wave form only (fp32 operands, weights packed per pair of fragments)");
+  const int n_super = d->Cin > 0 ? d->Cin / SS_CH : 0;
+  KFN_REQUIRE(k_split >= 1 && k_split <= (n_super > 0 ? n_super : 1), "kfn_conv2d_winograd_s2_splitk: k_split=%d outside 1..%d (Cin/16)",
+              k_split, n_super);
+  kfn_conv_desc d8 = *d;
+  d8.wino_form = KFN_WINO_FORM_S2_EIGHT_WAVE;
+  if (k_split == 1) return s2_plan(&d8, d->ldy, 1, y_low4, p);
+  KFN_REQUIRE(d->Cout % 4 == 0 && d->ldy >= d->Cout && d->ldy % 4 == 0 && y_low4 == 0,
+              "kfn_conv2d_winograd_s2_splitk: k_split > 1 needs a 16-byte aligned workspace of kfn_winograd_s2_splitk_workspace_bytes(), "
+              "Cout %% 4 == 0 and a 16-byte aligned output with ldy %% 4 == 0");
+  return s2_plan(&d8, d->Cout, k_split, 0, p);
+}
+
+// Can kfn_conv2d_winograd_s2 take this layer?  = "its plan succeeds for a 16-byte aligned output" (which the F(4,2) form
+// needs; for the others an unaligned one only selects the dword store path).  Host only; no device access.
+extern "C" int kfn_winograd_s2_supported(const kfn_conv_desc* d) {
+  kfn_conv_desc d_full;
+  kfn_wino_plan p;
+  return d && kfn::conv_desc_in(d, &d_full, "kfn_winograd_s2_supported", true) == KFN_OK && kfn::wino_s2_plan(&d_full, 0, 256, 0, &p) == KFN_OK;
+}
+
 extern "C" int kfn_conv2d_winograd_s2(const kfn_conv_desc* d, const float* x, const void* u2_packed, const float* bias,
                                       float* y, void* stream) {
   KFN_REQUIRE(d && x && u2_packed && y, "kfn_conv2d_winograd_s2: null argument");
   KFN_CONV_DESC_IN_LAYOUTS(d, "kfn_conv2d_winograd_s2");
   if (d->wino_form == KFN_WINO_FORM_S2_F42) return kfn::launch_wino_s2c(d, x, u2_packed, bias, y, stream);   // kfn_wino_s2c.hip
-  if (d->x_layout != KFN_LAYOUT_NHWC || d->y_layout != KFN_LAYOUT_NHWC)
-    return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_s2: only the F(4,2) form (KFN_WINO_FORM_S2_F42) takes KFN_LAYOUT_C16 activations");
-  return s2_launch(d, x, u2_packed, bias, y, d->ldy, d->relu, 1, stream);
+  kfn_wino_plan p;
+  int rc = kfn::wino_s2_plan(d, 0, 0, kfn::low4(y), &p);
+  if (rc != KFN_OK) return rc;
+  return s2_launch(d, p, x, u2_packed, bias, y, d->ldy, d->relu, stream);
 }
 
 // ---- split-K form of the eight-wave kernel (round 5; cf. kfn_conv2d_winograd_f43_splitk): BASELINE configs[1]'s conv4a launches
@@ -838,19 +858,14 @@ extern "C" int kfn_conv2d_winograd_s2_splitk(const kfn_conv_desc* d, const float
                                              float* y, float* workspace, int k_split, void* stream) {
   KFN_REQUIRE(d && x && u2b_packed && y, "kfn_conv2d_winograd_s2_splitk: null argument");
   KFN_CONV_DESC_IN(d, "kfn_conv2d_winograd_s2_splitk");
-  KFN_REQUIRE((d->wino_form == KFN_WINO_FORM_AUTO || d->wino_form == KFN_WINO_FORM_S2_EIGHT_WAVE) && d->operand_dtype == KFN_OPERAND_F32,
-              "kfn_conv2d_winograd_s2_splitk: the eight-wave form only (fp32 operands, weights packed per pair of fragments)");
-  const int n_super = d->Cin > 0 ? d->Cin / SS_CH : 0;
-  KFN_REQUIRE(k_split >= 1 && k_split <= (n_super > 0 ? n_super : 1), "kfn_conv2d_winograd_s2_splitk: k_split=%d outside 1..%d (Cin/16)",
-              k_split, n_super);
-  kfn_conv_desc d8 = *d;
-  d8.wino_form = KFN_WINO_FORM_S2_EIGHT_WAVE;
-  if (k_split == 1) return s2_launch(&d8, x, u2b_packed, bias, y, d->ldy, d->relu, 1, stream);
-  KFN_REQUIRE(workspace != nullptr && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && d->Cout % 4 == 0 && d->ldy >= d->Cout &&
-                  d->ldy % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0,
+  kfn_wino_plan p;
+  int rc = kfn::wino_s2_plan(d, k_split < 1 ? -1 : k_split, 0, kfn::low4(y), &p);
+  if (rc != KFN_OK) return rc;
+  if (p.k_split == 1) return s2_launch(d, p, x, u2b_packed, bias, y, d->ldy, d->relu, stream);
+  KFN_REQUIRE(workspace != nullptr && kfn::low4(workspace) == 0,
               "kfn_conv2d_winograd_s2_splitk: k_split > 1 needs a 16-byte aligned workspace of kfn_winograd_s2_splitk_workspace_bytes(), "
               "Cout %% 4 == 0 and a 16-byte aligned output with ldy %% 4 == 0");
-  int rc = s2_launch(&d8, x, u2b_packed, nullptr, workspace, d->Cout, 0, k_split, stream);
+  rc = s2_launch(d, p, x, u2b_packed, nullptr, workspace, d->Cout, 0, stream);
   if (rc != KFN_OK) return rc;
   const long pixels = (long)d->N * (d->H / 2) * (d->W / 2);
   return kfn::launch_splitk_reduce(workspace, k_split, pixels, bias, d->relu, y, d->Cout, d->ldy, (hipStream_t)stream);

@@ -716,33 +716,66 @@ __global__ __launch_bounds__(512, 1) void wino_s2c_pkernel(S2cArgs p) {
 
 }  // namespace
 
-int kfn::wino_s2c_lds_bytes() { return LDS_P > LDS_BYTES ? LDS_P : LDS_BYTES; }
-
-// pointer-free routing check of the F(4,2) form (kfn_winograd_s2_supported answers it for wino_form = KFN_WINO_FORM_S2_F42)
-int kfn::wino_s2c_supported(const kfn_conv_desc* d) {
-  if (d->x_dtype != KFN_ACT_F32 || d->y_dtype != KFN_ACT_F32 || d->operand_dtype != KFN_OPERAND_F32) return 0;
-  if (d->kh != 3 || d->kw != 3 || d->stride != 2 || d->transposed || d->epilogue != KFN_EPI_NONE) return 0;
-  if (d->H <= 0 || d->W <= 0 || (d->H & 7) || (d->W & 7)) return 0;          // whole 4x4 output tiles; pad after the image only
-  if (d->H / 8 < 4) return 0;                                                 // a 4-row tile block straddles at most two images
-  if (d->Cin <= 0 || d->Cin % SS_CH != 0 || d->cout_pad % 32 != 0) return 0;
-  if (d->Cout % 4 != 0 || d->ldy % 4 != 0 || d->ldx % 2 != 0) return 0;      // 16-byte stores, 8-byte gathers
-  if (d->x_layout == KFN_LAYOUT_C16 && d->ldx != d->Cin) return 0;            // channel-blocked tensors are dense
-  if (d->y_layout == KFN_LAYOUT_C16 && (d->Cout % 16 != 0 || d->ldy != d->Cout)) return 0;
-  return 1;
-}
-
-int kfn::launch_wino_s2c(const kfn_conv_desc* d, const float* x, const void* u_packed, const float* bias, float* y, void* stream) {
-  if (!wino_s2c_supported(d))
+// The plan of kfn_conv2d_winograd_s2's F(4,2) form (wino_form = KFN_WINO_FORM_S2_F42).
+int kfn::wino_s2c_plan(const kfn_conv_desc* d, int cu_count, unsigned y_low4, kfn_wino_plan* p) {
+  const bool ok =
+      d->x_dtype == KFN_ACT_F32 && d->y_dtype == KFN_ACT_F32 && d->operand_dtype == KFN_OPERAND_F32 &&
+      d->kh == 3 && d->kw == 3 && d->stride == 2 && !d->transposed && d->epilogue == KFN_EPI_NONE &&
+      d->H > 0 && d->W > 0 && !(d->H & 7) && !(d->W & 7) &&           // whole 4x4 output tiles; pad after the image only
+      d->H / 8 >= 4 &&                                                  // a 4-row tile block straddles at most two images
+      d->Cin > 0 && d->Cin % SS_CH == 0 && d->cout_pad % 32 == 0 &&
+      d->Cout % 4 == 0 && d->ldy % 4 == 0 && d->ldx % 2 == 0 &&         // 16-byte stores, 8-byte gathers
+      !(d->x_layout == KFN_LAYOUT_C16 && d->ldx != d->Cin) &&           // channel-blocked tensors are dense
+      !(d->y_layout == KFN_LAYOUT_C16 && (d->Cout % 16 != 0 || d->ldy != d->Cout));
+  if (!ok)
     return kfn::fail(KFN_ERR_UNSUPPORTED, "kfn_conv2d_winograd_s2 (F(4,2) form): needs fp32, 3x3 stride 2, H and W multiples of 8 with H >= 32, "
                      "Cin %% 16 == 0, Cout %% 4 == 0, ldy %% 4 == 0, KFN_LAYOUT_C16 tensors dense with C %% 16 == 0 (got H=%d W=%d Cin=%d ldx=%d Cout=%d ldy=%d, "
                      "x_layout %d, y_layout %d)", d->H, d->W, d->Cin, d->ldx, d->Cout, d->ldy, d->x_layout, d->y_layout);
   KFN_REQUIRE(d->N > 0 && d->ldx >= d->Cin && d->ldy >= d->Cout && d->cout_pad >= d->Cout, "kfn_conv2d_winograd_s2 (F(4,2) form): bad strides / channel counts");
-  KFN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(u_packed) | reinterpret_cast<uintptr_t>(y)) & 15) == 0,
-              "kfn_conv2d_winograd_s2 (F(4,2) form): buffers must be 16-byte aligned");
-  const long img_b = (long)d->H * d->W * d->ldx * 4L;
-  const long out_b = (long)(d->H / 2) * (d->W / 2) * d->ldy * 4L;
-  KFN_REQUIRE(2 * img_b < (1L << 31) && 2 * out_b < (1L << 31) && (long)NFRAG * d->cout_pad * d->Cin * 4L < (1L << 31),
+  KFN_REQUIRE(y_low4 == 0, "kfn_conv2d_winograd_s2 (F(4,2) form): buffers must be 16-byte aligned");   // there is no dword epilogue
+  const int Ho = d->H / 2, Wo = d->W / 2;
+  KFN_REQUIRE(2L * d->H * d->W * d->ldx * 4L < (1L << 31) && 2L * Ho * Wo * d->ldy * 4L < (1L << 31) &&
+                  (long)NFRAG * d->cout_pad * d->Cin * 4L < (1L << 31),
               "kfn_conv2d_winograd_s2 (F(4,2) form): image or kernel beyond 2 GiB of 32-bit offsets");
+  const long vrows = (long)d->N * (Ho / 4);
+  KFN_REQUIRE(vrows < (1L << 30), "kfn_conv2d_winograd_s2 (F(4,2) form): N*H/8 = %ld tile rows exceed 32-bit addressing", vrows);
+  const long tiles_m = (long)kfn::ceil_div(Wo / 4, 4) * kfn::ceil_div((int)vrows, 4);
+  const int tiles_n = kfn::ceil_div(d->cout_pad, NT);
+  KFN_REQUIRE(tiles_m * tiles_n < (1L << 31), "kfn_conv2d_winograd_s2 (F(4,2) form): grid too large");
+  std::memset(p, 0, sizeof(*p));
+  p->tiles_m = (int)tiles_m; p->tiles_n = tiles_n;
+  p->tiles_per_block = 16;
+  p->channels_per_group = NT;
+  p->n_group = kfn::wino_n_group(d->wino_order, tiles_n, tiles_n % 2 == 0 ? 2 : tiles_n, tiles_n);
+  p->wide_store = 1;
+  p->k_split = 1;
+  p->ss_per_split = d->Cin / SS_CH;
+  p->threads = 512;
+  // the persistent form: one workgroup per CU walking its share of the tile blocks (needs two super-steps of look-ahead inside a
+  // block; launches that do not even fill the chip once keep one workgroup per block)
+  // MEASURED (batch 20, same box, two runs each): conv2a (4 super-steps) 2.66 -> 2.53 ms, conv3a (16) 4.01 -> 3.93, conv4a (32) 3.81 ->
+  // 3.81.  What a block still costs beyond its super-steps (15 of conv2a's 54 us) is the issue of its 131 KB of output stores (a
+  // timing build without them: -8 % on conv2a in either form) and the consumers' epilogue, which persistence cannot hide.  (The
+  // first build spilled 31 block-level VGPRs whose reloads queued behind the prefetches in flight: lane_now().)
+  const bool persistent = p->ss_per_split >= 2 && p->ss_per_split <= PERSIST_MAX_SS && tiles_m * tiles_n >= 2L * cu_count;
+  p->kernel = persistent ? KFN_WINO_KERNEL_S2C_PERSISTENT : KFN_WINO_KERNEL_S2C;
+  p->lds_bytes = persistent ? LDS_P : LDS_BYTES;
+  p->workgroups = persistent ? cu_count : p->tiles_m * tiles_n;
+  return KFN_OK;
+}
+
+int kfn::launch_wino_s2c(const kfn_conv_desc* d, const float* x, const void* u_packed, const float* bias, float* y, void* stream) {
+  static int n_cu = 0;
+  if (n_cu == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+  }
+  kfn_wino_plan p;
+  int rc = kfn::wino_s2c_plan(d, n_cu, kfn::low4(y), &p);
+  if (rc != KFN_OK) return rc;
+  KFN_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(u_packed)) & 15) == 0,
+              "kfn_conv2d_winograd_s2 (F(4,2) form): buffers must be 16-byte aligned");
   S2cArgs a;
   a.x = x; a.u = static_cast<const float*>(u_packed); a.bias = bias; a.y = y;
   a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.ldx = d->ldx;
@@ -751,51 +784,29 @@ int kfn::launch_wino_s2c(const kfn_conv_desc* d, const float* x, const void* u_p
   a.Th = a.Ho / 4; a.Tw = a.Wo / 4;
   a.vrows = d->N * a.Th;
   a.bw = kfn::ceil_div(a.Tw, 4);
-  const long tiles_m = (long)a.bw * kfn::ceil_div(a.vrows, 4);
-  a.tiles_n = kfn::ceil_div(d->cout_pad, NT);
-  KFN_REQUIRE(tiles_m * a.tiles_n < (1L << 31), "kfn_conv2d_winograd_s2 (F(4,2) form): grid too large");
-  a.tiles_m = (int)tiles_m;
+  a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n;
   a.relu = d->relu;
-  {
-    int ng = a.tiles_n % 2 == 0 ? 2 : a.tiles_n;
-    if (d->wino_order == KFN_WINO_ORDER_N_FAST) ng = a.tiles_n;
-    else if (d->wino_order == KFN_WINO_ORDER_M_FAST) ng = 1;
-    else if (d->wino_order >= KFN_WINO_ORDER_GROUPS(1)) ng = d->wino_order - KFN_WINO_ORDER_GROUPS(0);
-    if (ng < 1 || ng > a.tiles_n || a.tiles_n % ng != 0) ng = a.tiles_n;
-    a.n_group = ng;
-  }
+  a.n_group = p.n_group;
   const long in_pix = (long)d->N * d->H * d->W, out_pix = (long)d->N * a.Ho * a.Wo;
   a.x_bytes = (unsigned long long)(((in_pix - 1) * d->ldx + d->Cin) * 4L);
   a.y_bytes = (unsigned long long)(((out_pix - 1) * d->ldy + d->Cout) * 4L);
   a.u_bytes = (unsigned)((long)NFRAG * d->cout_pad * d->Cin * 4L);
   const bool xb = d->x_layout == KFN_LAYOUT_C16, yb = d->y_layout == KFN_LAYOUT_C16;
-  a.x_img = (unsigned)img_b; a.x_pix = xb ? 64u : (unsigned)d->ldx * 4u; a.x_cb = xb ? (unsigned)(d->H * d->W) * 64u : 64u;
-  a.y_img = (unsigned)out_b; a.y_pix = yb ? 64u : (unsigned)d->ldy * 4u; a.y_cb = yb ? (unsigned)(a.Ho * a.Wo) * 64u : 64u;
-  const long nwg = (long)a.tiles_m * a.tiles_n;
-  // the persistent form: one workgroup per CU walking its share of the tile blocks (needs two super-steps of look-ahead inside a
-  // block; launches that do not even fill the chip once keep one workgroup per block)
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
-  // MEASURED (batch 20, same box, two runs each): conv2a (4 super-steps) 2.66 -> 2.53 ms, conv3a (16) 4.01 -> 3.93, conv4a (32) 3.81 ->
-  // 3.81.  What a block still costs beyond its super-steps (15 of conv2a's 54 us) is the issue of its 131 KB of output stores (a
-  // timing build without them: -8 % on conv2a in either form) and the consumers' epilogue, which persistence cannot hide.  (The
-  // first build spilled 31 block-level VGPRs whose reloads queued behind the prefetches in flight: lane_now().)
-  if (d->Cin / SS_CH >= 2 && d->Cin / SS_CH <= PERSIST_MAX_SS && nwg >= 2L * n_cu) {
+  a.x_img = (unsigned)((long)d->H * d->W * d->ldx * 4L); a.x_pix = xb ? 64u : (unsigned)d->ldx * 4u; a.x_cb = xb ? (unsigned)(d->H * d->W) * 64u : 64u;
+  a.y_img = (unsigned)((long)a.Ho * a.Wo * d->ldy * 4L); a.y_pix = yb ? 64u : (unsigned)d->ldy * 4u; a.y_cb = yb ? (unsigned)(a.Ho * a.Wo) * 64u : 64u;
+  const dim3 grid((unsigned)p.workgroups), block((unsigned)p.threads);
+  if (p.kernel == KFN_WINO_KERNEL_S2C_PERSISTENT) {
     static std::atomic<uint64_t> attr_done_p{0};
-    int rcp = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino_s2c_pkernel), LDS_P, attr_done_p);
+    int rcp = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino_s2c_pkernel), p.lds_bytes, attr_done_p);
     if (rcp != KFN_OK) return rcp;
-    hipLaunchKernelGGL(wino_s2c_pkernel, dim3((unsigned)n_cu), dim3(512), LDS_P, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(wino_s2c_pkernel, grid, block, p.lds_bytes, (hipStream_t)stream, a);
     KFN_LAUNCH_CHECK("wino_s2c_pkernel");
     return KFN_OK;
   }
   static std::atomic<uint64_t> attr_done{0};
-  int rc = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino_s2c_kernel), LDS_BYTES, attr_done);
+  rc = kfn::set_max_dynamic_lds(reinterpret_cast<const void*>(wino_s2c_kernel), p.lds_bytes, attr_done);
   if (rc != KFN_OK) return rc;
-  hipLaunchKernelGGL(wino_s2c_kernel, dim3((unsigned)nwg), dim3(512), LDS_BYTES, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(wino_s2c_kernel, grid, block, p.lds_bytes, (hipStream_t)stream, a);
   KFN_LAUNCH_CHECK("wino_s2c_kernel");
   return KFN_OK;
 }

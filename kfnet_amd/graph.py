@@ -472,6 +472,38 @@ def best_split_k(workgroups, n_super, out_bytes, ss_us, max_split=8, cus=256, on
     return best if best_t < 0.9 * base else 1
 
 
+class DenseGeometry(object):
+    """What winograd_plan reads of a Tensor, for a dense fp32 NHWC tensor that does not exist (yet)."""
+    ch_off, layout, dtype, graph = 0, 'nhwc', 'f32', None
+
+    def __init__(self, shape):
+        self.shape = tuple(shape)
+        self.ld = self.shape[3]
+
+
+def winograd_plan(x, y, stride, wino_form=0, operand_dtype=_lib.OPERAND_F32, k_split=0):
+    """The launch plan (_lib.WinoPlan: kernel, grid, padded tile and channel counts, LDS) of the Winograd kernel that a 3x3
+    convolution x -> y would run on, or None when the launcher refuses the layer or the kernel needs more LDS than the
+    graph's device has (Graph.lds_bytes_per_cu; on such a part the caller falls through to its next route instead of
+    failing in the first launch).  x, y: Tensors or DenseGeometry -- shape, ld, ch_off, layout, dtype.  The library picks
+    the family from stride and wino_form (kfn_winograd_launch_plan); k_split 0 = the plain entry point, >= 1 = the split-K
+    one.  Every rule is the launcher's own; the one thing stated here is the tensor-level form of "y is 16-byte aligned":
+    the channel offset of its window is a multiple of 4 (its storage is, and its pixel stride is the plan's to judge)."""
+    n, h, w, cin = x.shape
+    cout = y.shape[3]
+    g = x.graph
+    d = _lib.ConvDesc(N=n, H=h, W=w, Cin=cin, ldx=x.ld, Cout=cout, cout_pad=-(-cout // 32) * 32, ldy=y.ld, kh=3, kw=3,
+                      stride=stride, operand_dtype=operand_dtype, wino_form=wino_form,
+                      x_dtype=_lib.ACT_F16 if x.dtype == 'f16' else _lib.ACT_F32,
+                      y_dtype=_lib.ACT_F16 if y.dtype == 'f16' else _lib.ACT_F32,
+                      x_layout=_lib.LAYOUT_C16 if x.layout == 'c16' else _lib.LAYOUT_NHWC,
+                      y_layout=_lib.LAYOUT_C16 if y.layout == 'c16' else _lib.LAYOUT_NHWC)
+    plan = _lib.winograd_launch_plan(d, k_split, getattr(g, 'cu_count', 256), 4 * (y.ch_off % 4))
+    if plan is None or (g is not None and plan.lds_bytes > g.lds_bytes_per_cu):
+        return None
+    return plan
+
+
 class ConvOp(Op):
     def __init__(self, name, x, y, kernel, bias, kh, kw, stride, relu, transposed=False,
                  epilogue=_lib.EPI_NONE, config=_lib.CFG_AUTO, operand_dtype=_lib.OPERAND_F32):
@@ -578,7 +610,7 @@ class ConvOp(Op):
         if self.operand_dtype == _lib.OPERAND_F16 and io != (False, False):
             prec = self.PREC_F16_IO[io]
             if io == (True, True) and bk.value == 16 and cfg.value in (_lib.CFG_128x256, _lib.CFG_256x256):
-                prec = 7      # weights global -> LDS directly (mirror of the AUTO rule in kfn_conv2d_nhwc)
+                prec = 7      # weights global -> LDS directly (kfn_conv2d_nhwc's AUTO rule, which kfn_conv2d_plan does not report)
             if io == (True, True) and bk.value == 16 and cfg.value == _lib.CFG_256x256_W8:
                 prec = 8      # ... and the activation tile too (the eight-wave tile's AUTO rule)
             return 'conv_mfma_kernel<%d, %d, %d, %d, %d, 0, %d>' % (t + (bk.value if io[1] else 16, prec))
@@ -654,60 +686,60 @@ class WinogradConvOp(ConvOp):
         _lib.check(rc, 'kfn_conv2d_winograd[%s]' % self.name)
 
 
-class WinogradFusedConvOp(ConvOp):
-    """3x3 stride-1 SAME conv through kfn_conv2d_winograd_fused: all 16 Winograd positions of a tile
-    block in registers, input and output transforms in the kernel -- one launch, no workspace.  The library
-    picks the form: four waves sharing one input transform through LDS (wino3_kernel, 128 output channels
-    per workgroup) when Cout >= 128 and Cin % 32 == 0, two waves sharing it (wino3_pair_kernel) for 33 .. 64 output
-    channels with Cin % 16 == 0, else one wave per 32 output channels (wino2_kernel)."""
+class PlannedWinogradOp(ConvOp):
+    """A convolution on one of the single-launch Winograd entry points.  Which kernel it runs on, its grid and the tile and
+    channel counts the grid pads the layer to are the library's launch plan of the op's own descriptor
+    (kfn_winograd_launch_plan: the function the launchers launch from); nothing here restates a launcher's rule."""
 
-    @staticmethod
-    def supported(x_shape, cin, cout, operand_dtype=_lib.OPERAND_F32):
-        n, h, w, _ = x_shape
-        if operand_dtype == _lib.OPERAND_F16:      # fp16 operands: the four-wave form only
-            return cin % 64 == 0 and cout >= 128 and (h + 1) // 2 >= 4
-        return cin % 16 == 0 and (h + 1) // 2 >= 4
+    # MFMA products per Winograd tile and input channel: F(2x2,3x3) 16, F(4x4,3x3) 36, polyphase F(2,2) 25, polyphase F(4,2) 81
+    POSITIONS = {_lib.WINO_KERNEL_WINO2_WIDE: 16, _lib.WINO_KERNEL_WINO2_DWORD: 16, _lib.WINO_KERNEL_WINO3: 16,
+                 _lib.WINO_KERNEL_WINO3_F16: 16, _lib.WINO_KERNEL_WINO3_PAIR: 16, _lib.WINO_KERNEL_WINO4: 36,
+                 _lib.WINO_KERNEL_WINO4B: 36, _lib.WINO_KERNEL_S2: 25, _lib.WINO_KERNEL_S2_F16: 25, _lib.WINO_KERNEL_S2B: 25,
+                 _lib.WINO_KERNEL_S2C: 81, _lib.WINO_KERNEL_S2C_PERSISTENT: 81}
+    REDUCE_KERNEL = None      # second launch of the class's split-K form
+    k_split = 1
 
-    def four_wave(self):
-        """Mirror of the routing rule in kfn_conv2d_winograd_fused (kfn_wino2.hip)."""
-        return self.y.shape[3] >= 128 and self.x.shape[3] % 32 == 0
-
-    def two_wave(self):
-        """The second routing rule of kfn_conv2d_winograd_fused: all of a layer's 33 .. 64 output channels in one
-        workgroup of two waves (two images of the input below 1 GiB: the patch offsets carry their marks above)."""
-        n, h, w, cin = self.x.shape
-        return (not self.four_wave() and self.operand_dtype == _lib.OPERAND_F32 and 32 < self.y.shape[3] <= 64
-                and cin % 16 == 0 and 2 * h * w * self.x.ld * 4 < (1 << 30))
+    def plan(self, required=True):
+        """The plan of the frames this op actually runs (Graph.active), through the entry point launch() calls.  A layer the
+        launcher refuses: KfnError, or None when the caller asks (routing.after_binding does, to move the op elsewhere)."""
+        plan = _lib.winograd_launch_plan(self.desc(), self.k_split if self.k_split > 1 else 0,
+                                         getattr(self.x.graph, 'cu_count', 256), 4 * (self.y.ch_off % 4))
+        if plan is None and required:
+            _lib.check(-1, 'kfn_winograd_launch_plan[%s]' % self.name)
+        return plan
 
     def kernel_name(self, lib):
-        if self.operand_dtype == _lib.OPERAND_F16:
-            return 'wino3_kernel<true>'
-        if self.two_wave():
-            return 'wino3_pair_kernel'
-        return 'wino3_kernel' if self.four_wave() else 'wino2_kernel'
-
-    def mfma_flops(self):
-        """FLOPs the MFMAs execute: 16 positions x (tile blocks padded to 8x4 tiles, batch rows packed) x
-        output channels padded to the workgroup's column block."""
-        n, ho, wo, cout = self.y.shape
-        n = _scaled(n, self.x.graph)
-        th, tw = (ho + 1) // 2, (wo + 1) // 2
-        tiles = (-(-tw // 8) * 8) * (-(-(n * th) // 4) * 4)
-        cpad = -(-cout // 32) * 32
-        if self.four_wave():
-            cpad = -(-cpad // 128) * 128
-        return 2.0 * 16 * tiles * cpad * self.x.shape[3]
+        plan = self.plan()
+        name = _lib.WINO_KERNEL_NAMES[plan.kernel]
+        return name if plan.k_split == 1 else '%s[split-K %d] + %s' % (name, plan.k_split, self.REDUCE_KERNEL)
 
     def workgroups(self, lib=None):
-        """Blocks of 8 x 4 tiles of 2x2 pixels (the tile rows of the batch packed) x column blocks of 128 (four waves), 64
-        (two waves: the whole layer) or 32 (one wave) output channels."""
-        n, ho, wo, cout = self.y.shape
-        n = _scaled(n, self.x.graph)
-        th, tw = (ho + 1) // 2, (wo + 1) // 2
-        blocks = (-(-tw // 8)) * (-(-(n * th) // 4))
-        cpad = -(-cout // 32) * 32
-        per = 128 if (self.four_wave() or self.operand_dtype == _lib.OPERAND_F16) else (64 if self.two_wave() else 32)
-        return blocks * (-(-cpad // per))
+        """Tile blocks x channel groups x split-K runs (the persistent F(4,2) kernel walks them with one workgroup per CU)."""
+        plan = self.plan()
+        return plan.tiles_m * plan.tiles_n * plan.k_split
+
+    def mfma_flops(self):
+        """FLOPs the MFMAs execute: positions x tiles x output channels x input channels, the tiles padded to whole tile
+        blocks (batch rows packed) and the output channels to the workgroup's column block."""
+        plan = self.plan()
+        return (2.0 * self.POSITIONS[plan.kernel] * plan.tiles_m * plan.tiles_per_block
+                * plan.tiles_n * plan.channels_per_group * self.x.shape[3])
+
+
+class WinogradFusedConvOp(PlannedWinogradOp):
+    """3x3 stride-1 SAME conv through kfn_conv2d_winograd_fused: all 16 Winograd positions of a tile
+    block in registers, input and output transforms in the kernel -- one launch, no workspace.  The library
+    picks the form (csrc/kfn_wino3.hip, wino_fused_plan): four waves sharing one input transform through LDS (wino3_kernel,
+    128 output channels per workgroup), two waves sharing it (wino3_pair_kernel, 33 .. 64 output channels), else one wave per
+    32 output channels (wino2_kernel)."""
+
+    def four_wave(self):
+        """Does the plan name wino3_kernel (either operand type)?"""
+        return self.plan().kernel in (_lib.WINO_KERNEL_WINO3, _lib.WINO_KERNEL_WINO3_F16)
+
+    def two_wave(self):
+        """Does the plan name wino3_pair_kernel?"""
+        return self.plan().kernel == _lib.WINO_KERNEL_WINO3_PAIR
 
     def launch(self, lib, stream, phases=3):
         d = self.desc()
@@ -716,7 +748,7 @@ class WinogradFusedConvOp(ConvOp):
         _lib.check(rc, 'kfn_conv2d_winograd_fused[%s]' % self.name)
 
 
-class WinogradF43ConvOp(ConvOp):
+class WinogradF43ConvOp(PlannedWinogradOp):
     """3x3 stride-1 SAME conv through kfn_conv2d_winograd_f43 (csrc/kfn_wino4.hip): F(4x4,3x3), one launch, no workspace.
     eight_wave (Graph.winograd_f43_eight_wave, the default): wino4b_kernel -- two waves per SIMD on 16x16x4 MFMA tiles, 36
     accumulators of 4 registers per wave, weights packed per pair of positions (pack_winograd_f43_kernel_b); else
@@ -735,6 +767,8 @@ class WinogradF43ConvOp(ConvOp):
         40 workgroups on 256 CUs)."""
         return best_split_k(workgroups, cin // 16, out_bytes, cls.SS_US, max_split, cus)
 
+    REDUCE_KERNEL = 'wino4_splitk_reduce_kernel'
+
     def desc(self):
         d = ConvOp.desc(self)
         d.wino_form = _lib.WINO_FORM_F43_EIGHT_WAVE if self.eight_wave else _lib.WINO_FORM_F43_FOUR_WAVE
@@ -744,43 +778,13 @@ class WinogradF43ConvOp(ConvOp):
         return type(self) is WinogradF43ConvOp and self.eight_wave and self.k_split <= 1
 
     @staticmethod
-    def supported(x_shape, cin, cout, ldx=None, ldy=None, y_ch_off=0):
-        """Mirror of kfn_winograd_f43_supported (+ the launcher's 16-byte alignment of y, which for a tensor is "pixel
-        stride and channel offset multiples of 4": a concat slice at an odd offset must take another route -- the fused
-        F(2x2) and stride-2 kernels have a dword-store path for it, this kernel has not)."""
-        n, h, w, _ = x_shape
-        ldx = cin if ldx is None else ldx
-        ldy = cout if ldy is None else ldy
-        return (cin % 16 == 0 and (h + 3) // 4 >= 8 and cout % 4 == 0 and ldx % 2 == 0 and ldx >= cin and ldy >= cout
-                and ldy % 4 == 0 and y_ch_off % 4 == 0
-                and 2 * h * w * ldx * 4 < (1 << 30) and 2 * h * w * ldy * 4 < (1 << 31)
-                and 36 * (-(-cout // 32) * 32) * cin * 4 < (1 << 31))
-
-    @staticmethod
     def workgroups(x_shape, cout):
-        """Workgroups of the launch: blocks of 4 x 8 tiles (the tile rows of the batch's images packed) x 64 channels."""
-        n, h, w, _ = x_shape
-        th, tw = (h + 3) // 4, (w + 3) // 4
-        return (-(-tw // 4)) * (-(-(n * th) // 8)) * (-(-cout // 64))
+        """Workgroups of an unsplit launch on a dense input of this shape (0: the kernel does not take it)."""
+        plan = winograd_plan(DenseGeometry(x_shape), DenseGeometry(tuple(x_shape[:3]) + (cout,)), 1, _lib.WINO_FORM_F43_EIGHT_WAVE)
+        return plan.tiles_m * plan.tiles_n if plan is not None else 0
 
     def launch_workgroups(self):
-        n, h, w, _ = self.x.shape
-        return self.workgroups((_scaled(n, self.x.graph), h, w, 0), self.y.shape[3]) * max(1, self.k_split)
-
-    def kernel_name(self, lib):
-        if self.k_split > 1:
-            return 'wino4b_kernel[split-K %d] + wino4_splitk_reduce_kernel' % self.k_split
-        return 'wino4b_kernel' if self.eight_wave else 'wino4_kernel'
-
-    def mfma_flops(self):
-        """FLOPs the MFMAs execute: 36 positions x (tile blocks padded to 4x8 tiles of 4x4 pixels, batch rows packed) x
-        output channels padded to the workgroup's 64."""
-        n, ho, wo, cout = self.y.shape
-        n = _scaled(n, self.x.graph)
-        th, tw = (ho + 3) // 4, (wo + 3) // 4
-        tiles = (-(-tw // 4) * 4) * (-(-(n * th) // 8) * 8)
-        cpad = -(-cout // 64) * 64
-        return 2.0 * 36 * tiles * cpad * self.x.shape[3]
+        return self.plan().workgroups
 
     def workspace_bytes(self):
         n, ho, wo, cout = self.y.shape
@@ -838,7 +842,7 @@ class Conv64RowsF16Op(ConvOp):
         _lib.check(rc, 'kfn_conv3x3_c64_f16[%s]' % self.name)
 
 
-class WinogradS2ConvOp(ConvOp):
+class WinogradS2ConvOp(PlannedWinogradOp):
     """3x3 stride-2 SAME conv of an even-sized image through kfn_conv2d_winograd_s2 (polyphase + F(2,2):
     25 MFMA streams into 9 accumulators per 2x2 outputs instead of 36 direct taps).  Three forms, fp32 operands only beyond
     the first:
@@ -848,6 +852,8 @@ class WinogradS2ConvOp(ConvOp):
       pack_winograd_s2_kernel_b) instead of wino_s2_kernel; k_split > 1: kfn_conv2d_winograd_s2_splitk with a private workspace."""
 
     SS_US = 5.3      # one super-step of wino_s2b_kernel: 200 MFMAs of 32 cycles on each of two waves per SIMD
+
+    REDUCE_KERNEL = 'splitk_reduce_kernel'
 
     def desc(self):
         d = ConvOp.desc(self)
@@ -859,64 +865,6 @@ class WinogradS2ConvOp(ConvOp):
 
     def takes_c16(self):
         return type(self) is WinogradS2ConvOp and self.f42
-
-    @staticmethod
-    def supported(x_shape, cin, cout):
-        n, h, w, _ = x_shape
-        return cin % 16 == 0 and h % 2 == 0 and w % 2 == 0 and (h // 2 + 1) // 2 >= 4
-
-    @staticmethod
-    def f42_supported(x_shape, cin, cout, ldy=None, y_ch_off=0):
-        """kfn::wino_s2c_supported's pointer-free conditions (csrc/kfn_wino_s2c.hip)."""
-        n, h, w, _ = x_shape
-        ldy = cout if ldy is None else ldy
-        return (cin % 16 == 0 and h % 8 == 0 and w % 8 == 0 and h >= 32 and cout % 4 == 0 and ldy % 4 == 0 and y_ch_off % 4 == 0)
-
-    @staticmethod
-    def f42_workgroups(y_shape):
-        """Blocks of 4 x 4 tiles of 4x4 OUTPUT pixels (batch rows packed) x column blocks of 128 output channels."""
-        n, ho, wo, cout = y_shape
-        th, tw = -(-ho // 4), -(-wo // 4)
-        return (-(-tw // 4)) * (-(-(n * th) // 4)) * (-(-cout // 128))
-
-    @staticmethod
-    def base_workgroups(y_shape):
-        """Blocks of 8 x 4 tiles of 2x2 OUTPUT pixels (batch rows packed) x column blocks of 128 output channels."""
-        n, ho, wo, cout = y_shape
-        th, tw = (ho + 1) // 2, (wo + 1) // 2
-        return (-(-tw // 8)) * (-(-(n * th) // 4)) * (-(-cout // 128))
-
-    def kernel_name(self, lib):
-        if self.f42:
-            # (the launcher's rule, csrc/kfn_wino_s2c.hip: the persistent form for 2 .. 64 super-steps and at least two workgroups per CU)
-            ss = self.x.shape[3] // 16
-            return 'wino_s2c_pkernel' if 2 <= ss <= 64 and self.workgroups() >= 2 * getattr(self.x.graph, 'cu_count', 256) else 'wino_s2c_kernel'
-        if self.k_split > 1:
-            return 'wino_s2b_kernel[split-K %d] + splitk_reduce_kernel' % self.k_split
-        if self.eight_wave:
-            return 'wino_s2b_kernel'
-        return 'wino_s2_kernel<true>' if self.operand_dtype == _lib.OPERAND_F16 else 'wino_s2_kernel'
-
-    def mfma_flops(self):
-        """FLOPs the MFMAs execute: 25 products per 2x2-output tile and input channel, tile blocks padded to
-        8x4 tiles (batch rows packed), output channels padded to the workgroup's 128."""
-        n, ho, wo, cout = self.y.shape
-        n = _scaled(n, self.x.graph)
-        if self.f42:      # 81 products per 4x4-output tile and input channel, blocks of 4x4 tiles
-            th, tw = -(-ho // 4), -(-wo // 4)
-            tiles = (-(-tw // 4) * 4) * (-(-(n * th) // 4) * 4)
-            return 2.0 * 81 * tiles * (-(-cout // 128) * 128) * self.x.shape[3]
-        th, tw = (ho + 1) // 2, (wo + 1) // 2
-        tiles = (-(-tw // 8) * 8) * (-(-(n * th) // 4) * 4)
-        return 2.0 * 25 * tiles * (-(-cout // 128) * 128) * self.x.shape[3]
-
-    def workgroups(self, lib=None):
-        """Workgroups of this op's launch: of the frames it actually runs, every split-K run counted."""
-        n, ho, wo, cout = self.y.shape
-        shape = (_scaled(n, self.x.graph), ho, wo, cout)
-        if self.f42:
-            return self.f42_workgroups(shape)
-        return self.base_workgroups(shape) * max(1, self.k_split)
 
     @classmethod
     def best_k_split(cls, workgroups, cin, out_bytes, max_split=8, cus=256):
@@ -1537,17 +1485,6 @@ class Graph(object):
         self.f16_activation_scopes = ('ScoreNet',)
         self.f16x3_min_channels = 64
         self.active = (1, 1)  # (frames in this launch, frames the graph was built for)
-
-    def winograd_lds_fits(self, stride, cin, cout, wino_form=0, operand_dtype=_lib.OPERAND_F32):
-        """Does the Winograd kernel that would be launched for this 3x3 layer fit this device's LDS?  (kfn_winograd_lds_bytes
-        against lds_bytes_per_cu: the F(4x4,3x3) and four-wave forms need 144-157 KB of the 160 KiB a gfx950 CU has; on a
-        part with less Network.conv falls through to the next route instead of failing in the first launch.)"""
-        d = _lib.ConvDesc(N=1, H=64, W=64, Cin=cin, ldx=cin, Cout=cout, cout_pad=-(-cout // 32) * 32, ldy=cout, kh=3, kw=3,
-                          stride=stride, operand_dtype=operand_dtype, wino_form=wino_form)
-        nb = C.c_int(0)
-        if _lib.load().kfn_winograd_lds_bytes(C.byref(d), C.byref(nb)) != _lib.KFN_OK:
-            return False
-        return nb.value <= self.lds_bytes_per_cu
 
     # -- construction -------------------------------------------------------------------
     def placeholder(self, shape, dtype='f32', name=None):

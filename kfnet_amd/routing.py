@@ -12,7 +12,7 @@ from .graph import (Conv64RowsF16Op, ConvOp, WindowFcConvOp, WinogradConvOp, Win
                     WinogradS2ConvOp, as_f16, as_f16x3, pack_bias, pack_bias_x4, pack_conv64_rows_kernel, pack_conv_kernel,
                     pack_conv_kernel_chunked, pack_window_fc_kernel, pack_winograd_f43_kernel, pack_winograd_f43_kernel_b,
                     pack_winograd_fused_kernel, pack_winograd_kernel, pack_winograd_s2_kernel, pack_winograd_s2_kernel_b,
-                    pack_winograd_s2_kernel_c)
+                    pack_winograd_s2_kernel_c, winograd_plan)
 
 # eight_wave / k_split / f42: None = the class has no such option.  workspace: None, 'shared' (the graph's two-kernel Winograd
 # workspace: those layers run one after the other) or 'private' (split-K: the two towers run on two streams, a shared one
@@ -38,7 +38,8 @@ def direct(op):
 
 def choose(g, x, y, k, stride, biased):
     """The route of a new k x k convolution x -> y.  Reads the graph's switches, the two tensors' geometry (shape, ld, ch_off,
-    dtype) and g.winograd_lds_fits; constructs nothing."""
+    dtype) and, for the Winograd routes, the library's launch plan of the layer (graph.winograd_plan: is it taken, does its
+    kernel fit this device's LDS, how many workgroups); constructs nothing."""
     n, h, w, cin = x.shape
     filters = y.shape[3]
     F16 = _lib.OPERAND_F16
@@ -47,13 +48,13 @@ def choose(g, x, y, k, stride, biased):
     # (measured, 16 frames: conv3b 2.07 vs 2.31 ms direct fp16, conv4b 1.81 vs 2.59, conv5 1.00 vs 1.25; at
     #  Cin = 256 the direct kernel is as fast -- conv2b 2.56 vs 2.48 -- and stays)
     if (f16 and f32_io and k == 3 and stride == 1 and g.winograd_fused and cin >= 512
-            and WinogradFusedConvOp.supported(x.shape, cin, filters, F16)):
+            and winograd_plan(x, y, 1, operand_dtype=F16) is not None):
         # BASELINE config 5: the four-wave Winograd kernel on fp16 MFMAs (transform in fp32, V and U rounded to fp16)
         return Route(WinogradFusedConvOp, as_f16(pack_winograd_fused_kernel), operand_dtype=F16)
     # (the fp16 instantiation of the polyphase stride-2 kernel exists and is tested, but at fp16 MFMA rates it is
     #  latency-bound and the direct fp16 kernel is faster: conv3a 1.20 vs 1.68 ms -- Graph.winograd_s2_f16 = False)
     if (f16 and f32_io and k == 3 and stride == 2 and g.winograd_s2_f16 and cin >= 64
-            and filters >= 128 and WinogradS2ConvOp.supported(x.shape, cin, filters)):
+            and filters >= 128 and winograd_plan(x, y, 2, operand_dtype=F16) is not None):
         return Route(WinogradS2ConvOp, as_f16(pack_winograd_s2_kernel), operand_dtype=F16, eight_wave=False, k_split=1, f42=False)
     if (f16 and k == 3 and stride == 1 and h == 2 and w == 2 and g.window_fc and biased and (4 * cin) % 32 == 0
             and filters % 8 == 0 and f32_io):
@@ -78,21 +79,21 @@ def choose(g, x, y, k, stride, biased):
     fmin = g.winograd_fused_min_channels
     fused_ok = (k == 3 and stride == 1 and g.winograd_fused and fmin and cin >= fmin and filters >= fmin
                 and cin <= g.winograd_fused_max_channels
-                and min(h, w) >= 8 and WinogradFusedConvOp.supported(x.shape, cin, filters)
-                and g.winograd_lds_fits(1, cin, filters))
+                and min(h, w) >= 8 and winograd_plan(x, y, 1) is not None)
     # A launch of fewer than winograd_f43_min_workgroups workgroups (of 32 tiles x 64 channels, one per CU) leaves
     # most of the 256 CUs idle and the smaller F(2x2,3x3) workgroups win -- single frames only (batch 1, F(4x4) ->
     # F(2x2): conv5 80 workgroups 0.287 -> 0.238 ms, conv6 40: 0.151 -> 0.123, feat5 40: 0.031 -> 0.022; from 160
     # workgroups up F(4x4) is ahead: conv4b at batch 1 0.288 against 0.479; profiles/r04_wino4_microbench.log, r4z)
     e8 = bool(g.winograd_f43_eight_wave)
-    wgs = WinogradF43ConvOp.workgroups((n, h, w, cin), filters)
+    plan = None
+    if k == 3 and stride == 1 and g.winograd_fused and f43:
+        plan = winograd_plan(x, y, 1, _lib.WINO_FORM_F43_EIGHT_WAVE if e8 else _lib.WINO_FORM_F43_FOUR_WAVE)
+    wgs = plan.tiles_m * plan.tiles_n if plan is not None else 0
     ksplit = 1
-    if e8 and g.winograd_f43_max_k_split > 1:
+    if plan is not None and e8 and g.winograd_f43_max_k_split > 1:
         ksplit = WinogradF43ConvOp.best_k_split(wgs, cin, n * h * w * filters * 4, g.winograd_f43_max_k_split)
     f43_fills = (not fused_ok or wgs * ksplit >= g.winograd_f43_min_workgroups)
-    if (k == 3 and stride == 1 and g.winograd_fused and f43 and cin >= f43 and filters >= f43 and f43_fills
-            and WinogradF43ConvOp.supported(x.shape, cin, filters, x.ld, y.ld, y.ch_off)
-            and g.winograd_lds_fits(1, cin, filters, _lib.WINO_FORM_F43_EIGHT_WAVE if e8 else _lib.WINO_FORM_F43_FOUR_WAVE)):
+    if plan is not None and cin >= f43 and filters >= f43 and f43_fills:
         return Route(WinogradF43ConvOp, pack_winograd_f43_kernel_b if e8 else pack_winograd_f43_kernel,
                      eight_wave=e8, k_split=ksplit, workspace='private' if ksplit > 1 else None)
     # (measured, 16-frame batch, single-kernel vs two-kernel form: conv1b 2.3 ms vs 3.3 direct, conv2b 5.60 vs
@@ -102,16 +103,16 @@ def choose(g, x, y, k, stride, biased):
     smin = g.winograd_s2_min_channels
     # 3x3 stride-2 layers (SCoordNet conv2a / conv3a / conv4a): polyphase + F(2,2), 25/36 of the direct MFMAs
     e8 = bool(g.winograd_s2_eight_wave)
-    if (k == 3 and stride == 2 and smin and cin >= smin and filters >= 128
-            and WinogradS2ConvOp.supported(x.shape, cin, filters)
-            and g.winograd_lds_fits(2, cin, filters, _lib.WINO_FORM_S2_EIGHT_WAVE if e8 else 0)):
-        if (g.winograd_s2_f42 and WinogradS2ConvOp.f42_supported(x.shape, cin, filters)
-                and WinogradS2ConvOp.f42_workgroups(y.shape) >= g.winograd_s2_f42_min_workgroups
-                and g.winograd_lds_fits(2, cin, filters, _lib.WINO_FORM_S2_F42)):
+    plan = None
+    if k == 3 and stride == 2 and smin and cin >= smin and filters >= 128:
+        plan = winograd_plan(x, y, 2, _lib.WINO_FORM_S2_EIGHT_WAVE if e8 else 0)
+    if plan is not None:
+        f42 = winograd_plan(x, y, 2, _lib.WINO_FORM_S2_F42) if g.winograd_s2_f42 else None
+        if f42 is not None and f42.tiles_m * f42.tiles_n >= g.winograd_s2_f42_min_workgroups:
             return Route(WinogradS2ConvOp, pack_winograd_s2_kernel_c, eight_wave=False, k_split=1, f42=True)
         ksplit = 1
         if e8 and g.winograd_s2_max_k_split > 1 and filters % 4 == 0:
-            ksplit = WinogradS2ConvOp.best_k_split(WinogradS2ConvOp.base_workgroups(y.shape), cin,
+            ksplit = WinogradS2ConvOp.best_k_split(plan.tiles_m * plan.tiles_n, cin,
                                                    y.shape[0] * y.shape[1] * y.shape[2] * filters * 4, g.winograd_s2_max_k_split)
         return Route(WinogradS2ConvOp, pack_winograd_s2_kernel_b if e8 else pack_winograd_s2_kernel,
                      eight_wave=e8, k_split=ksplit, f42=False, workspace='private' if ksplit > 1 else None)
@@ -133,16 +134,16 @@ def after_binding(op):
     if isinstance(op, WinogradF43ConvOp):
         # an output the F(4x4,3x3) launcher would now reject: the fused F(2x2,3x3) kernel (dword stores for unaligned
         # outputs) or the direct one
-        if op.supported(x.shape, cin, cout, x.ld, y.ld, y.ch_off):
+        if op.plan(required=False) is not None:
             return None
-        if WinogradFusedConvOp.supported(x.shape, cin, cout) and min(h, w) >= 8:
+        if winograd_plan(x, y, 1) is not None and min(h, w) >= 8:
             return Route(WinogradFusedConvOp, pack_winograd_fused_kernel)
         return direct(op)
     if isinstance(op, WinogradS2ConvOp):
         # the F(4,2) form and the split-K form store 16 bytes at a time; the F(2,2) eight-wave form has a dword-store path
-        if op.f42 and not op.f42_supported(x.shape, cin, cout, y.ld, y.ch_off):
+        if op.f42 and op.plan(required=False) is None:
             return Route(WinogradS2ConvOp, pack_winograd_s2_kernel_b, eight_wave=True, k_split=1, f42=False)
-        if op.k_split > 1 and (y.ld % 4 != 0 or y.ch_off % 4 != 0):
+        if op.k_split > 1 and op.plan(required=False) is None:
             #  kfn_conv2d_winograd_s2_splitk needs a 16-byte aligned output with ldy % 4 == 0: same kernel, same
             # weights, unsplit
             return Route(WinogradS2ConvOp, op.kernel.pack, op.bias.pack if op.bias is not None else pack_bias,

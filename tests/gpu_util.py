@@ -74,6 +74,23 @@ def run_conv(x, w, b, stride=1, relu=False, transposed=False, epilogue=0, config
     return out
 
 
+def winograd_fields(kind, x_shape, co, relu=False, form=0, ldx_pad=0, ldy_pad=8, config=0, x_layout='nhwc', y_layout='nhwc',
+                    order=0, x_off=0, y_off=0, f16=False):
+    """The descriptor fields of a run_winograd launch (same arguments) and where the two windows start, in floats: (fields,
+    x_off, y_off).  No device access: tests/test_wino_modes_host.py asks the library for the launch plan of the same fields."""
+    n, h, w, ci = x_shape
+    stride = 2 if kind == 's2' else 1
+    if x_layout == 'c16':
+        ldx_pad = x_off = 0
+    if y_layout == 'c16':
+        ldy_pad = y_off = 0
+    assert 0 <= x_off <= ldx_pad and 0 <= y_off <= ldy_pad
+    fields = dict(N=n, H=h, W=w, Cin=ci, ldx=ci + ldx_pad, Cout=co, cout_pad=-(-co // 32) * 32, ldy=co + ldy_pad, kh=3, kw=3,
+                  stride=stride, relu=int(relu), wino_form=form, config=config, wino_order=order, operand_dtype=int(f16),
+                  x_layout=_lib.LAYOUT_C16 if x_layout == 'c16' else 0, y_layout=_lib.LAYOUT_C16 if y_layout == 'c16' else 0)
+    return fields, x_off, y_off
+
+
 def run_winograd(kind, x, wt, b, relu=False, form=0, ldx_pad=0, ldy_pad=8, config=0, x_layout='nhwc', y_layout='nhwc',
                  order=0, x_off=0, y_off=0, x_fill=9.0, f16=False, k_split=None, relaunch=None):
     """One launch of a minimal-filtering entry point on x [N,H,W,Cin] fp32 with the TF-layout 3x3 kernel wt:
@@ -96,17 +113,10 @@ def run_winograd(kind, x, wt, b, relu=False, form=0, ldx_pad=0, ldy_pad=8, confi
     lib = _lib.load()
     n, h, w, ci = x.shape
     co = wt.shape[3]
-    stride = 2 if kind == 's2' else 1
+    fields, x_off, y_off = winograd_fields(kind, x.shape, co, relu, form, ldx_pad, ldy_pad, config, x_layout, y_layout, order,
+                                           x_off, y_off, f16)
+    ldx, ldy, stride = fields['ldx'], fields['ldy'], fields['stride']
     ho, wo = -(-h // stride), -(-w // stride)
-    if x_layout == 'c16':
-        ldx_pad = x_off = 0
-    if y_layout == 'c16':
-        ldy_pad = y_off = 0
-    assert 0 <= x_off <= ldx_pad and 0 <= y_off <= ldy_pad
-    ldx, ldy = ci + ldx_pad, co + ldy_pad
-    fields = dict(N=n, H=h, W=w, Cin=ci, ldx=ldx, Cout=co, cout_pad=-(-co // 32) * 32, ldy=ldy, kh=3, kw=3,
-                  stride=stride, relu=int(relu), wino_form=form, config=config, wino_order=order, operand_dtype=int(f16),
-                  x_layout=_lib.LAYOUT_C16 if x_layout == 'c16' else 0, y_layout=_lib.LAYOUT_C16 if y_layout == 'c16' else 0)
     if x_layout == 'c16':
         xb = np.ascontiguousarray(x.reshape(n, h, w, ci // 16, 16).transpose(0, 3, 1, 2, 4)).reshape(n * h * w, ci)
     else:

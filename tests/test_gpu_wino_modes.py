@@ -42,12 +42,8 @@ def _note(line):
 def _run(c, x, w, b, relaunch=None, **change):
     from tests.gpu_util import run_winograd
     c = c._replace(**change)
-    _, kind, form, f16, split, _ = WM.KERNELS[c.kernel]
-    ldx, x_off, ldy, y_off = WM.view_strides(c)
-    xl, yl = WM.LAYOUTS[c.layout]
-    return run_winograd(kind, x, w, b, relu=bool(c.relu), form=form, ldx_pad=ldx - c.cin, ldy_pad=ldy - c.cout, x_layout=xl, y_layout=yl,
-                        order=WM.ORDERS[c.order], x_off=x_off, y_off=y_off, x_fill=1e6, f16=f16, k_split=c.ksplit if split else None,
-                        relaunch=relaunch)
+    _, kind, _, _, split, _ = WM.KERNELS[c.kernel]
+    return run_winograd(kind, x, w, b, x_fill=1e6, k_split=c.ksplit if split else None, relaunch=relaunch, **WM.launch_args(c))
 
 
 def _one(i, c):

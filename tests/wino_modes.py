@@ -5,8 +5,9 @@ The minimal-filtering entry points (csrc/kfn_wino2.hip, kfn_wino3.hip, kfn_wino4
 steered by many descriptor fields at once: the form, the workgroup order, ReLU, bias, channel windows on either side, the
 layout, split-K -- and, silently, by Cout % 4, ldy % 4 and the alignment of y, which pick between the 16-byte and the
 dword store epilogue.  As in tests/conv_modes.py every field is a FACTOR with a few LEVELS, RULES restate what the
-launchers accept (kfn_winograd_fused_supported and the routing of kfn_conv2d_winograd_fused; wino4_setup; s2_launch;
-wino_s2c_supported; the two split-K entry points; nothing else), and conv_modes.Table draws cases until every pair of
+launchers accept (their launch plans: wino_fused_plan, wino_f43_plan, wino_s2_plan, wino_s2c_plan, which state the two split-K
+entry points too; nothing else -- tests/test_wino_modes_host.py holds the table against them through kfn_winograd_launch_plan),
+and conv_modes.Table draws cases until every pair of
 levels that the rules allow together occurs in one.  EXTRA adds what pairs alone do not guarantee (see there).  Nothing
 below touches the GPU."""
 import collections
@@ -86,6 +87,15 @@ def _dword_ok(kernel, ks):
     return kernel in DWORD_KERNELS or (kernel == 's2bk' and ks == 1)
 
 
+def launch_args(c):
+    """The keyword arguments of gpu_util.run_winograd / winograd_fields for case c (everything but the data and the split)."""
+    _, _, form, f16, _, _ = KERNELS[c.kernel]
+    ldx, x_off, ldy, y_off = view_strides(c)
+    xl, yl = LAYOUTS[c.layout]
+    return dict(relu=bool(c.relu), form=form, ldx_pad=ldx - c.cin, ldy_pad=ldy - c.cout, x_layout=xl, y_layout=yl,
+                order=ORDERS[c.order], x_off=x_off, y_off=y_off, f16=f16)
+
+
 RULES = (
     (('kernel', 'img'), lambda k, i: i in IMAGES[FAMILY[k]]),
     (('kernel', 'cout'), lambda k, co: (32 < co <= 64) if k == 'w3p' else (co >= 128 if k in ('w3', 'w3h') else True)),
@@ -144,7 +154,7 @@ def falls_back(kernel, tiles_n, order):
 
 
 def n_group(kernel, tiles_n, order):
-    """wino4_setup / s2_launch / launch_wino_s2c: channel groups of one tile block that are adjacent in the grid.  w3 / w3h
+    """wino_f43_plan / wino_s2_plan / wino_s2c_plan: channel groups of one tile block that are adjacent in the grid.  w3 / w3h
     know M fastest (1) and N fastest (tiles_n) only, every other value being their default, M fastest; w2 and w3p (one
     group) ignore the field: None."""
     if kernel in FAST_KERNELS:
@@ -208,7 +218,7 @@ PERSIST_MAX_SS = 64
 
 
 def s2c_persistent(n, h, w, cin, cout, cu):
-    """launch_wino_s2c's rule for wino_s2c_pkernel: 2 <= Cin/16 <= 64 and at least two workgroups per CU."""
+    """wino_s2c_plan's rule for wino_s2c_pkernel: 2 <= Cin/16 <= 64 and at least two workgroups per CU."""
     tiles_m = -(-(w // 8) // 4) * -(-(n * (h // 8)) // 4)
     tiles_n = -(-(-(-cout // 32) * 32) // 128)
     return 2 <= cin // 16 <= PERSIST_MAX_SS and tiles_m * tiles_n >= 2 * cu
