@@ -66,7 +66,9 @@ extern "C" {
  * kfn_reloc_search, kfn_reloc_seed and kfn_reloc_settle (a lost tracker relocalised from fern-coded keyframes), and
  * kfn_kalman_scan_plan (which of the scan's instantiations a grid launches; host only), and kfn_conv2d_grad_weights_plan
  * (tiles and runs of pixels of a weight-gradient launch; host only), and kfn_winograd_launch_plan (kfn_wino_plan: what a
- * Winograd entry point launches for a descriptor, the struct its launcher launches from; host only). */
+ * Winograd entry point launches for a descriptor, the struct its launcher launches from; host only), and
+ * kfn_kabsch_scratch_bytes, kfn_kabsch_ransac, kfn_kabsch_hypotheses and kfn_kabsch_select (poses from the records and a
+ * depth frame: RANSAC-Kabsch). */
 #define KFN_ABI_VERSION 13
 
 const char* kfn_last_error(void);
@@ -737,6 +739,57 @@ int kfn_pnp_ransac_guided(const kfn_pnp_desc* desc, const kfn_pnp_sample_desc* s
 int kfn_pnp_hypotheses_guided(const kfn_pnp_desc* desc, const kfn_pnp_sample_desc* sample, const float* records,
                               int32_t* samples, float* hyp_poses, int32_t* counts, uint64_t* cum, int32_t* n, void* scratch,
                               void* stream);
+
+/* ---- poses with depth: RANSAC-Kabsch (added exports, the ABI number stays 13) ------------------------------------------
+ * kfn_kabsch_ransac is the sibling of kfn_pnp_ransac for RGB-D frames ("Poses with depth").  Next to the records
+ * it reads cam_points [B,h,w,ldp] = (Xc, Yc, Zc, mask): the camera-frame point, in metres, of the pixel that cell (r, c)
+ * observes -- what kfn_depth_labels writes at stride 8 under the identity pose.  Every candidate cell is a 3-D/3-D
+ * correspondence (camera point p, scene point x), and the pose is the rigid alignment x ~ R p + t, camera to world:
+ *   candidates    1/sigma > min_confidence, x finite, mask == 1 and p finite; raster order; at most 32768 cells
+ *   sampling      kfn_pnp_ransac's hash; draws continue to 3 distinct indices, at most 16 draws
+ *   hypothesis    the least-squares rigid transform of the three pairs, det R = +1, in fp64 (Horn's quaternion form, cyclic
+ *                 Jacobi on the symmetric 4x4); invalid if |(p1 - p0) x (p2 - p0)| < 1e-6 m^2 for the camera or the scene
+ *                 triangle, or if the two largest eigenvalues lie within 1e-9 of the largest magnitude; [R|t] stored in fp32
+ *   scoring       inlier iff |R p + t - x|^2 < inlier_m^2 (fp32, strict)
+ *   selection     most inliers, ties to the lowest hypothesis index
+ *   refinement    up to refine_iters rounds in fp64: the inliers of the current pose (strict <), then the closed form over
+ *                 them with weights w = 1 (weighted = 0) or w = 1 / (sigma^2 + point_sigma^2) (weighted = 1), sigma =
+ *                 1 / record[3]; a round with the inlier set of the round before ends the loop; fewer than 3 inliers or an
+ *                 undetermined rotation keeps the previous pose and ends it
+ *   poses         [B,16] camera-to-world, row-major; NaN where status != KFN_PNP_OK
+ *   cov           [B,36] = (sum w J^T J)^-1 over the final inliers at the final pose, J = [-[q]x | I], q = R^T (x - t), w =
+ *                 1 / (sigma^2 + point_sigma^2) in both modes: kfn_pnp_ransac_unc's coordinates (omega, tau), symmetric to the
+ *                 last bit; NaN where status != KFN_PNP_OK, with fewer than 3 inliers or a failed Cholesky factorisation
+ *   quality       [B,2] = (sum w |R p + t - x|^2 over the final inliers, 3 * inliers - 6); NaN where status != KFN_PNP_OK
+ *   info          [B,4] = (status KFN_PNP_*, candidates, final inliers, selected hypothesis or -1)
+ * cov and quality may be NULL.  Bit-identical from launch to launch; a frame's pose depends neither on its batch nor on its
+ * position in it (frame = t0 + b).  No floating-point atomics. */
+typedef struct kfn_kabsch_desc {
+  int32_t struct_size;     /* = sizeof(kfn_kabsch_desc) as the caller compiled it */
+  int32_t B, h, w;         /* frames, grid rows, grid columns (h * w <= 32768) */
+  int32_t ld;              /* floats per cell in `records`, >= 4 */
+  int32_t ldp;             /* floats per cell in `cam_points`, >= 4 */
+  int32_t t0;              /* global index of frame 0 of this call (the sampling counter) */
+  uint32_t seed;
+  int32_t hypotheses;      /* 1 .. KFN_PNP_MAX_HYPOTHESES */
+  int32_t refine_iters;    /* rounds of the closed-form refinement, 0 .. 100 */
+  int32_t min_points;      /* fewer candidates: KFN_PNP_TOO_FEW_POINTS; >= 3 */
+  float min_confidence;    /* 20; >= 0 */
+  float inlier_m;          /* 0.10: the inlier distance in metres */
+  int32_t weighted;        /* 0: w = 1 in the refinement; 1: w = 1 / (sigma^2 + point_sigma^2) */
+  float point_sigma;       /* > 0, metres: the floor of a point's standard deviation (0.01) */
+} kfn_kabsch_desc;
+#define KFN_KABSCH_DESC_INIT {(int32_t)sizeof(kfn_kabsch_desc), 0, 0, 0, 4, 4, 0, 0u, 256, 10, 16, 20.0f, 0.10f, 0, 0.01f}
+int kfn_kabsch_scratch_bytes(const kfn_kabsch_desc* desc, size_t* bytes);
+int kfn_kabsch_ransac(const kfn_kabsch_desc* desc, const float* records, const float* cam_points, float* poses, float* cov,
+                      float* quality, int32_t* info, void* scratch, void* stream);
+/* Probe of the first two stages: samples [B,H,3] candidate indices (-1: no 3 distinct in 16 draws, or too few candidates),
+ * hyp_poses [B,H,12] = [R | t] camera-to-world in fp32 (NaN: invalid), counts [B,H] inliers (-1: invalid). */
+int kfn_kabsch_hypotheses(const kfn_kabsch_desc* desc, const float* records, const float* cam_points, int32_t* samples,
+                          float* hyp_poses, int32_t* counts, void* stream);
+/* Probe of the selection rule on its own: best [B] = the first index of the maximum of counts [B,hypotheses], -1 where
+ * every count is negative -- what info[:,3] reports. */
+int kfn_kabsch_select(const int32_t* counts, int B, int hypotheses, int32_t* best, void* stream);
 
 /* Random-walk error-state filter over a sequence of such poses, one sequence per lane, fp64, serial over t.  State: (R, p)
  * camera-to-world and P (6x6, the body-frame coordinates (dtheta, drho) above).  flags [S,T]:

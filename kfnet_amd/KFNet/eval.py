@@ -29,7 +29,10 @@ distance errors in cm, NIS-in-band fraction) and the final summary are printed
 (kfnet_amd/KFNet/pose_filter.py PoseTracker); it writes `pose_smooth_<i>.txt`.
 `--pose` also solves every frame's camera pose on the device (kfnet_amd/KFNet/pnp.py) and writes `pose_<i>.txt` next to
 each `coord_<i>.npy`.  `--pose_sampling confidence | confidence2 [--pose_confidence_cap]` draws its hypotheses by the
-records' confidence (DESIGN.md 5c "Guided sampling"), in the sharded runs too.
+records' confidence (DESIGN.md 5c "Guided sampling"), in the sharded runs too.  `--pose_depth` implies `--pose` and solves
+every frame as a 3-D/3-D alignment of its records with its depth map, read from `depth_list.txt` in `--input_folder` (what
+`labels make` writes; kfnet_amd/KFNet/kabsch.py, DESIGN.md 5c "Poses with depth"); it composes with `--pose_weighted` and
+`--pose_smooth`, and in the sharded runs every rank decodes its own frames' depth.
 """
 import argparse
 import os

@@ -10,6 +10,8 @@ a git-lfs pointer; this module is that last stage, with the reference's command-
                                   [--smooth [--rot_sigma 0.02 --trans_sigma 0.02 --gate 22.46 --max_rejects 3
                                              --sequence_length N
                                              --motion {walk,velocity} --rts --rot_rate_sigma 0.05 --trans_rate_sigma 0.05]]
+                                  [--depth_list <depth_list> [--inlier_m 0.10 --point_sigma 0.01
+                                                             --depth_focal_x F --depth_focal_y F --depth_u U --depth_v V]]
 
 writes one `pose_<i>.txt` (4x4 camera-to-world, the 7-Scenes `frame-*.pose.txt` format; NaN where no pose was found)
 per listed map, i = the map's position in the list.  With --gt (one pose file per map) it prints every frame's rotation
@@ -24,8 +26,13 @@ pose tracker instead (kfn_pose_track, DESIGN.md 5c "Pose tracker"): --motion vel
 per frame, --rts smooths each sequence backwards as well, and `pose_smooth_<i>.txt` then holds the smoothed pose; with
 --covariance the tracker also writes `pose_smooth_cov_<i>.txt`.  --sampling confidence / confidence2 draws the four cells
 of every hypothesis in proportion to the maps' confidence above --min_confidence, or to its square, capped at
---confidence_cap (kfn_pnp_ransac_guided, DESIGN.md 5c "Guided sampling").  Without these flags the program does and prints
-what it always did.
+--confidence_cap (kfn_pnp_ransac_guided, DESIGN.md 5c "Guided sampling").  --depth_list (one 16-bit depth PNG per map, in
+millimetres: the depth_list.txt that `labels make` writes) solves every frame as a 3-D/3-D alignment of the map with its
+back-projected depth frame instead (KFNet.kabsch.KabschSolver, DESIGN.md 5c "Poses with depth"): --inlier_m is the inlier
+distance in metres, --point_sigma the floor of a point's standard deviation, any --depth_* flag registers the depth
+camera to the colour camera as `labels make` does; --gt, --weighted, --covariance, --smooth, --motion and --rts work as
+before, while --inlier_px, --pixel_sigma and a --sampling other than uniform belong to PnP and are refused.  Without these
+flags the program does and prints what it always did.
 """
 import argparse
 import ctypes as C
@@ -228,19 +235,22 @@ def pose_errors(est, gt):
     return rot, trans
 
 
-def solve_in_batches(solver, records, batch=64, t0=0):
-    """records [T,h,w,4] (numpy) -> (poses [T,4,4], info [T,4]); frame k is solved as global frame t0 + k."""
+def solve_in_batches(solver, records, batch=64, t0=0, depth=None):
+    """records [T,h,w,4] (numpy) -> (poses [T,4,4], info [T,4]); frame k is solved as global frame t0 + k.  `depth` [T,..]:
+    the frames' depth maps or camera points, for a KabschSolver."""
     T = records.shape[0]
     poses = np.full((T, 4, 4), np.nan, np.float32)
     info = np.zeros((T, 4), np.int32)
     for lo in range(0, T, batch):
-        p, i = solver.solve(records[lo:lo + batch], t0=t0 + lo)
+        extra = () if depth is None else (depth[lo:lo + batch],)
+        p, i = solver.solve(records[lo:lo + batch], *extra, t0=t0 + lo)
         poses[lo:lo + batch], info[lo:lo + batch] = p, i
     return poses, info
 
 
-def solve_unc_in_batches(solver, records, batch=64, t0=0):
-    """solve_in_batches for PnPSolver.solve_unc: (poses [T,4,4], cov [T,6,6], quality [T,2], info [T,4])."""
+def solve_unc_in_batches(solver, records, batch=64, t0=0, depth=None):
+    """solve_in_batches for PnPSolver.solve_unc or KabschSolver.solve_unc: (poses [T,4,4], cov [T,6,6], quality [T,2],
+    info [T,4])."""
     T = records.shape[0]
     poses = np.full((T, 4, 4), np.nan, np.float32)
     cov = np.full((T, 6, 6), np.nan, np.float32)
@@ -248,7 +258,8 @@ def solve_unc_in_batches(solver, records, batch=64, t0=0):
     info = np.zeros((T, 4), np.int32)
     for lo in range(0, T, batch):
         hi = lo + batch
-        poses[lo:hi], cov[lo:hi], quality[lo:hi], info[lo:hi] = solver.solve_unc(records[lo:hi], t0=t0 + lo)
+        extra = () if depth is None else (depth[lo:hi],)
+        poses[lo:hi], cov[lo:hi], quality[lo:hi], info[lo:hi] = solver.solve_unc(records[lo:hi], *extra, t0=t0 + lo)
     return poses, cov, quality, info
 
 
@@ -308,7 +319,7 @@ def main(argv=None):
     ap.add_argument('--hypotheses', type=int, default=256)
     ap.add_argument('--batch', type=int, default=64, help='frames per kfn_pnp_ransac launch')
     ap.add_argument('--refine_iters', type=int, default=10)
-    ap.add_argument('--inlier_px', type=float, default=10.)
+    ap.add_argument('--inlier_px', type=float, default=None, help='inlier threshold of PnP in full-resolution pixels (10)')
     ap.add_argument('--min_confidence', type=float, default=20.)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--weighted', action='store_true', help='weigh the refinement by the propagated uncertainty')
@@ -334,7 +345,36 @@ def main(argv=None):
                          'above --min_confidence (confidence) or to its square (confidence2)')
     ap.add_argument('--confidence_cap', type=float, default=None,
                     help='--sampling confidence / confidence2: confidences above it weigh as it does (1000)')
+    ap.add_argument('--depth_list', default='',
+                    help='text file: one depth PNG per map; poses by RANSAC-Kabsch on the maps and their depth frames')
+    ap.add_argument('--inlier_m', type=float, default=None, help='--depth_list: inlier distance in metres (0.10)')
+    ap.add_argument('--point_sigma', type=float, default=None,
+                    help='--depth_list: floor of a point\'s standard deviation in metres (0.01)')
+    ap.add_argument('--depth_focal_x', type=float, default=None,
+                    help='--depth_list: any --depth_* flag registers the depth camera to the colour camera')
+    ap.add_argument('--depth_focal_y', type=float, default=None)
+    ap.add_argument('--depth_u', type=float, default=None)
+    ap.add_argument('--depth_v', type=float, default=None)
     a = ap.parse_args(argv)
+    depth_only = [k for k in ('inlier_m', 'point_sigma', 'depth_focal_x', 'depth_focal_y', 'depth_u', 'depth_v')
+                  if getattr(a, k) is not None]
+    if a.depth_list:
+        refused = [k for k in ('inlier_px', 'pixel_sigma') if getattr(a, k) is not None]
+        if a.sampling != 'uniform':
+            refused.append('sampling %s' % a.sampling)
+        if refused:
+            print('--depth_list solves 3-D/3-D alignments: --%s belongs to PnP' % ', --'.join(refused))
+            return 1
+        for k, v in (('inlier_m', a.inlier_m), ('point_sigma', a.point_sigma)):
+            if v is not None and not v > 0.0:
+                print('--%s must be > 0' % k)
+                return 1
+        if not a.min_confidence >= 0.0:
+            print('--depth_list needs --min_confidence >= 0')
+            return 1
+    elif depth_only:
+        ap.error('--%s needs --depth_list' % depth_only[0])
+    inlier_px = 10. if a.inlier_px is None else a.inlier_px
     if a.confidence_cap is not None and a.sampling == 'uniform':
         ap.error('--confidence_cap needs --sampling confidence or confidence2')
     guided = dict(sampling=a.sampling, confidence_cap=1000. if a.confidence_cap is None else a.confidence_cap)
@@ -385,13 +425,31 @@ def main(argv=None):
         if r.shape != (h, w, 4):
             print('%s: expected a [%d,%d,4] map, got %s' % (p, h, w, r.shape))
             return 1
-    solver = PnPSolver(h, w, a.focal_x, a.focal_y, a.u, a.v, hypotheses=a.hypotheses, refine_iters=a.refine_iters,
-                       seed=a.seed, min_confidence=a.min_confidence, inlier_px=a.inlier_px, weighted=a.weighted,
-                       pixel_sigma=1.0 if a.pixel_sigma is None else a.pixel_sigma, **guided)
-    if uncertain:
-        poses, cov, _, info = solve_unc_in_batches(solver, np.stack(records), max(1, a.batch))
+    depth = None
+    if a.depth_list:
+        from ..labels import DepthCamera, load_depth
+        from .kabsch import KabschSolver
+        depth_paths = [p for p in read_lines(a.depth_list) if p]
+        if len(depth_paths) != len(paths):
+            print('--depth_list lists %d depth maps for %d coordinate files' % (len(depth_paths), len(paths)))
+            return 1
+        try:
+            camera = DepthCamera(a.focal_x, a.focal_y, a.u, a.v, a.depth_focal_x, a.depth_focal_y, a.depth_u, a.depth_v)
+            depth = load_depth(depth_paths, (8 * h, 8 * w), max(1, a.thread_num))
+        except ValueError as e:
+            print(e)
+            return 1
+        solver = KabschSolver(h, w, camera, hypotheses=a.hypotheses, refine_iters=a.refine_iters, seed=a.seed,
+                              min_confidence=a.min_confidence, inlier_m=0.10 if a.inlier_m is None else a.inlier_m,
+                              weighted=a.weighted, point_sigma=0.01 if a.point_sigma is None else a.point_sigma)
     else:
-        poses, info = solve_in_batches(solver, np.stack(records), max(1, a.batch))
+        solver = PnPSolver(h, w, a.focal_x, a.focal_y, a.u, a.v, hypotheses=a.hypotheses, refine_iters=a.refine_iters,
+                           seed=a.seed, min_confidence=a.min_confidence, inlier_px=inlier_px, weighted=a.weighted,
+                           pixel_sigma=1.0 if a.pixel_sigma is None else a.pixel_sigma, **guided)
+    if uncertain:
+        poses, cov, _, info = solve_unc_in_batches(solver, np.stack(records), max(1, a.batch), depth=depth)
+    else:
+        poses, info = solve_in_batches(solver, np.stack(records), max(1, a.batch), depth=depth)
     os.makedirs(a.output_folder, exist_ok=True)
     for i in range(len(paths)):
         write_pose(os.path.join(a.output_folder, 'pose_%d.txt' % i), poses[i])

@@ -11,7 +11,9 @@ scope.  `--synthetic T` / `--random_weights` replace the images / the checkpoint
 pose_cov_<i>.txt; `--pose_smooth` (single-process runs) is --pose_weighted, and at the end the poses are tracked under
 `--pose_motion` (walk) and smoothed backwards in sequences of `--pose_sequence_length` frames (default: the whole run), into
 pose_smooth_<i>.txt (modes.write_smoothed_poses); `--pose_sampling confidence | confidence2 [--pose_confidence_cap]` draws
---pose's hypotheses by the records' confidence (DESIGN.md 5c "Guided sampling"), in the sharded runs too.
+--pose's hypotheses by the records' confidence (DESIGN.md 5c "Guided sampling"), in the sharded runs too; `--pose_depth`
+implies --pose and solves every frame from its records and its depth map of depth_list.txt in --input_folder (RANSAC-Kabsch,
+DESIGN.md 5c "Poses with depth"), composing with --pose_weighted and --pose_smooth, sharded runs included.
 With label_list.txt every frame's median distance error d_m (cm) is printed, then the median / mean / stddev over d_m.
 
 Under `python -m torch.distributed.run --nproc-per-node N -m kfnet_amd.SCoordNet.eval ...` every rank processes a

@@ -107,6 +107,14 @@ class PnPSampleDesc(SizedStructure):
     _fields_ = [('struct_size', C.c_int32), ('mode', C.c_int32), ('confidence_cap', C.c_float)]
 
 
+class KabschDesc(SizedStructure):
+    """kfn_kabsch_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
+    _fields_ = [('struct_size', C.c_int32), ('B', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('ld', C.c_int32),
+                ('ldp', C.c_int32), ('t0', C.c_int32), ('seed', C.c_uint32), ('hypotheses', C.c_int32),
+                ('refine_iters', C.c_int32), ('min_points', C.c_int32), ('min_confidence', C.c_float), ('inlier_m', C.c_float),
+                ('weighted', C.c_int32), ('point_sigma', C.c_float)]
+
+
 class PoseFilterDesc(SizedStructure):
     """kfn_pose_filter_desc (include/kfnet_hip.h); `struct_size` is filled in here."""
     _fields_ = [('struct_size', C.c_int32), ('S', C.c_int32), ('T', C.c_int32), ('rot_sigma', C.c_float),
@@ -391,6 +399,11 @@ SYMBOLS = {
     'kfn_reloc_search': (_i, [C.POINTER(RelocDesc)] + [_vp] * 5),
     'kfn_reloc_seed': (_i, [C.POINTER(RelocDesc)] + [_vp] * 4),
     'kfn_reloc_settle': (_i, [C.POINTER(RelocDesc)] + [_vp] * 9),
+    # poses from the records and a depth frame: RANSAC-Kabsch (added exports, ABI 13)
+    'kfn_kabsch_scratch_bytes': (_i, [C.POINTER(KabschDesc), C.POINTER(_sz)]),
+    'kfn_kabsch_ransac': (_i, [C.POINTER(KabschDesc)] + [_vp] * 8),
+    'kfn_kabsch_hypotheses': (_i, [C.POINTER(KabschDesc)] + [_vp] * 6),
+    'kfn_kabsch_select': (_i, [_vp, _i, _i, _vp, _vp]),
 }
 
 _lib = None

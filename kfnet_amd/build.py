@@ -55,6 +55,9 @@ EXTRA = {
     'kfn_track.hip': ['-ffp-contract=off'],
     # relocalisation from fern-coded keyframes: integer tests and copies of fp64 poses, built like the tracker it sits in
     'kfn_reloc.hip': ['-ffp-contract=off'],
+    # RANSAC-Kabsch: fp64 sums, Jacobi rotations and the covariance rounded product by product like the pose filter; the fp32
+    # scoring fuses by explicit fmaf only (DESIGN.md 5c "Poses with depth")
+    'kfn_kabsch.hip': ['-ffp-contract=off'],
 }
 
 

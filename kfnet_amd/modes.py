@@ -8,7 +8,8 @@ File contracts (float32 .npy, one per frame, [h,w,C] on the label grid h = ceil(
   flow_<i>.npy   [h,w,3] = (u, v, 1/sigma_trans) for the pair (i-1, i), i = 1..N-1: cell (r, c) of frame i comes from
                  cell (r + v, c + u) of frame i-1 (grid cells); flow_list.txt lists them in order, so line k pairs with
                  images k and k+1 of image_list.txt (vis/vis_optical_flow_list.py's arguments)
-  pose_<i>.txt   --pose: the camera-to-world pose solved from coord_<i>.npy (kfnet_amd/KFNet/pnp.py)
+  pose_<i>.txt   --pose: the camera-to-world pose solved from coord_<i>.npy (kfnet_amd/KFNet/pnp.py); --pose_depth: from
+                 coord_<i>.npy and the frame's depth map of depth_list.txt (kfnet_amd/KFNet/kabsch.py)
   pose_cov_<i>.txt   --pose_weighted: that pose refined with the records' uncertainty as weights, and its 6x6 covariance
   pose_smooth_<i>.txt   --pose_smooth: the --pose_weighted poses tracked and smoothed in time (single-process runs)
 """
@@ -156,6 +157,42 @@ def add_pose_flags(ap):
                          'confidence above the threshold (confidence) or to its square (confidence2)')
     ap.add_argument('--pose_confidence_cap', type=float, default=None,
                     help='--pose_sampling confidence / confidence2: confidences above it weigh as it does (1000)')
+    ap.add_argument('--pose_depth', action='store_true',
+                    help='--pose from the records and the frames\' depth maps (RANSAC-Kabsch, KFNet/kabsch.py): reads '
+                         'depth_list.txt from --input_folder, as `labels make` writes it')
+
+
+class DepthPoseOptions(object):
+    """The run functions' `pose` for a --pose_depth run: the run's depth maps, one path per frame."""
+
+    def __init__(self, weighted, depth_paths):
+        self.weighted, self.depth_paths = bool(weighted), list(depth_paths)
+
+
+class DepthPoseSolver(object):
+    """--pose_depth's solver: a KabschSolver (KFNetDataSpec intrinsics) over a run's depth list, with PnPSolver's calling
+    shape.  The frames of a call are the global frames t0, t0 + 1, ..: their depth maps are decoded here, by whichever
+    process solves them, so a sharded rank reads its own frames' depth alone."""
+
+    def __init__(self, h, w, depth_paths, weighted=False):
+        from .KFNet.KFNet import KFNetDataSpec
+        from .KFNet.kabsch import KabschSolver
+        from .labels import DepthCamera
+        spec = KFNetDataSpec()
+        self.solver = KabschSolver(h, w, DepthCamera(spec.focal_x, spec.focal_y, spec.u, spec.v), weighted=weighted)
+        self.weighted, self.depth_paths = bool(weighted), list(depth_paths)
+
+    def _depth(self, n, t0):
+        from .labels import load_depth
+        if t0 + n > len(self.depth_paths):
+            raise ValueError('depth_list.txt lists %d depth maps; frame %d has none' % (len(self.depth_paths), t0 + n - 1))
+        return load_depth(self.depth_paths[t0:t0 + n], (8 * self.solver.h, 8 * self.solver.w))
+
+    def solve(self, records, t0=0):
+        return self.solver.solve(records, self._depth(int(records.shape[0]), t0), t0=t0)
+
+    def solve_unc(self, records, t0=0):
+        return self.solver.solve_unc(records, self._depth(int(records.shape[0]), t0), t0=t0)
 
 
 class PoseOptions(object):
@@ -171,6 +208,17 @@ def pose_argument(a, ap=None):
     --pose_confidence_cap without --pose or one of its stronger forms, are argparse errors.  The sampling counter is the
     global frame index, so the sharded runs take the two sampling flags unchanged."""
     guided = getattr(a, 'pose_sampling', None) not in (None, 'uniform')
+    depth_paths = None
+    if getattr(a, 'pose_depth', False):
+        a.pose = True
+        path = os.path.join(getattr(a, 'input_folder', '') or '', 'depth_list.txt')
+        problem = ('--pose_depth draws three cells uniformly: --pose_sampling %s belongs to PnP' % a.pose_sampling if guided
+                   else None if os.path.isfile(path) else '--pose_depth needs depth_list.txt in --input_folder (%s)' % path)
+        if problem is not None:
+            if ap is None:
+                raise ValueError(problem)
+            ap.error(problem)
+        depth_paths = [p for p in read_lines(path) if p]
     if ap is not None:
         for name in ('pose_sampling', 'pose_confidence_cap'):
             if getattr(a, name) is not None and not (a.pose or a.pose_weighted or a.pose_smooth):
@@ -192,6 +240,8 @@ def pose_argument(a, ap=None):
         a.pose_weighted = True
     if a.pose_weighted:
         a.pose = True
+    if depth_paths is not None:
+        return DepthPoseOptions(a.pose_weighted, depth_paths)
     if guided and a.pose:
         return PoseOptions(a.pose_weighted, a.pose_sampling,
                            1000. if a.pose_confidence_cap is None else a.pose_confidence_cap)
@@ -216,8 +266,10 @@ def pose_solver(h, w, weighted=False, sampling='uniform', confidence_cap=1000.):
 
 
 def solver_of(pose, h, w):
-    """The run functions' `pose` -> its solver: True or POSE_WEIGHTED or a PoseOptions (pose_solver), a PnPSolver (itself),
-    anything false (None)."""
+    """The run functions' `pose` -> its solver: True or POSE_WEIGHTED or a PoseOptions (pose_solver), a DepthPoseOptions
+    (DepthPoseSolver), a PnPSolver (itself), anything false (None)."""
+    if isinstance(pose, DepthPoseOptions):
+        return DepthPoseSolver(h, w, pose.depth_paths, pose.weighted)
     if isinstance(pose, PoseOptions):
         return pose_solver(h, w, pose.weighted, pose.sampling, pose.confidence_cap)
     if pose is True or pose == POSE_WEIGHTED:

@@ -10,7 +10,8 @@ the record launch).  Several --batch values show where an engine stops scaling w
 `--engines pose` times the pose stage instead: ms per PnPSolver.solve of --frames records on a 60x80 grid (20 % outliers,
 per-cell sigma 0.5-4 cm) against solve_unc unweighted and weighted, in the same JSON line under "pose_ms"; and, under
 "pose_sampling_ms", solve with uniform sampling at 256 hypotheses against guided sampling (both weights) at 256 and at 64,
-the five taken in turns; and, under "pose_track_ms", ms per call of PoseFilter.run and of PoseTracker.run (both models,
+the five taken in turns; and, under "pose_depth_ms", KabschSolver.solve and its weighted solve_unc on the same records with
+their camera points (5 mm depth noise) against PnPSolver's, the four taken in turns; and, under "pose_track_ms", ms per call of PoseFilter.run and of PoseTracker.run (both models,
 with and without the backward pass) at S x T = 1 x 1000, 8 x 500 and 64 x 64, the five taken in turns.
 """
 import argparse
@@ -54,6 +55,44 @@ def time_pose_sampling(frames, reps, warmup, h=60, w=80, hypotheses=256):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             call(dev)
+            e1.record()
+            e1.synchronize()
+            if turn >= max(warmup, 1):
+                total[name] += e0.elapsed_time(e1)
+    return {name: round(v / reps, 3) for name, v in total.items()}
+
+
+def _pose_cam_points(frames, h, w):
+    """The camera points [frames,h,w,4] of _pose_records' frames (its first draw is the depth; camera = scene frame), with
+    5 mm of noise in depth, mask 1."""
+    import numpy as np
+    import torch
+    z = np.random.default_rng(0).uniform(0.5, 5.0, size=(frames, h, w))
+    z = z + np.random.default_rng(1).normal(scale=0.005, size=z.shape)
+    rr, cc = np.meshgrid(np.arange(h), np.arange(w), indexing='ij')
+    cam = np.stack([(cc * 8 - 320.) / 525. * z, (rr * 8 - 240.) / 525. * z, z, np.ones_like(z)], axis=-1)
+    return torch.from_numpy(cam.astype(np.float32)).cuda()
+
+
+def time_pose_depth(frames, reps, warmup, h=60, w=80):
+    """ms per call of KabschSolver.solve / solve_unc (weighted) and of PnPSolver's on the same records, resident on the
+    device with their camera points; the four calls take turns, each timed with its own pair of events, and the mean over
+    `reps` turns is reported."""
+    import torch
+    from kfnet_amd.KFNet.kabsch import KabschSolver
+    from kfnet_amd.KFNet.pnp import PnPSolver
+    dev, cam = _pose_records(frames, h, w), _pose_cam_points(frames, h, w)
+    kabsch, kabsch_w = KabschSolver(h, w), KabschSolver(h, w, weighted=True)
+    pnp, pnp_w = PnPSolver(h, w), PnPSolver(h, w, weighted=True)
+    calls = {'pnp_solve': lambda: pnp.solve(dev), 'kabsch_solve': lambda: kabsch.solve(dev, cam),
+             'pnp_solve_unc_weighted': lambda: pnp_w.solve_unc(dev),
+             'kabsch_solve_unc_weighted': lambda: kabsch_w.solve_unc(dev, cam)}
+    total = {name: 0.0 for name in calls}
+    for turn in range(max(warmup, 1) + reps):
+        for name, call in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            call()
             e1.record()
             e1.synchronize()
             if turn >= max(warmup, 1):
@@ -148,6 +187,7 @@ def main():
         a.engines.remove('pose')
         out['pose_ms'] = time_pose_stage(a.frames, a.reps, a.warmup)
         out['pose_sampling_ms'] = time_pose_sampling(a.frames, a.reps, a.warmup)
+        out['pose_depth_ms'] = time_pose_depth(a.frames, a.reps, a.warmup)
         out['pose_track_ms'] = time_pose_track(a.reps, a.warmup)
     for name in a.engines:
         out['fps'][name] = {}
